@@ -17,6 +17,8 @@ Prints ONE JSON line (rank 0) with the driver's contract fields plus
                  dense MFMA peak of the arithmetic it runs on, with its algorithmic bytes / FLOPs per launch
   exact_f32    : the same step with every contraction on v_mfma_f32_32x32x2_f32, same --steps / --warmup, own roofline
   cpu_baseline : the oracle (CPU restatement) timed on the host cores on a bounded sample (N=1 run only)
+
+--dump-outputs DIR writes what the last timed step of --precision computed (loss, parameter gradients) to DIR/*.npy.
 """
 from __future__ import annotations
 
@@ -180,6 +182,34 @@ def cpu_baseline(frames_per_view: int = 8, steps: int = 3):
                       f"{steps} timed step(s) after 1 warm-up, {dt:.2f} s/step, scaled per frame to a 16-frame clip"}
 
 
+DUMP_PER_TENSOR = 16384      # gradient elements sampled per parameter tensor by --dump-outputs (829 tensors: <= 19 MB in all)
+
+
+def dump_outputs(out_dir: str, loss: float, named_params, per_tensor: int = DUMP_PER_TENSOR, seed: int = 0) -> None:
+    """--dump-outputs: what the timed step handed its caller in the last timed step -- the loss and every parameter gradient --
+    as .npy files, so that two builds can be compared output for output.  The gradients are 224 M elements, so they are kept as a
+    fixed, seeded sample of at most `per_tensor` elements per tensor (the same positions on every run) plus the exact L2 norm of
+    every tensor:
+      loss.npy          float64 scalar
+      grad_norms.npy    float64 [tensors with a gradient], parameter order
+      grads_sample.npy  float32, the sampled elements of those tensors concatenated in parameter order (sorted positions)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    samples, norms = [], []
+    for _, p in named_params:
+        if p.grad is None:
+            continue
+        g = p.grad.detach().reshape(-1)
+        k = min(g.numel(), per_tensor)
+        idx = np.sort(rng.choice(g.numel(), size=k, replace=False)) if k < g.numel() else np.arange(k)
+        samples.append(g[torch.from_numpy(idx).to(g.device)].float())
+        norms.append(g.double().norm())
+    np.save(os.path.join(out_dir, "loss.npy"), np.array(loss, dtype=np.float64))
+    np.save(os.path.join(out_dir, "grad_norms.npy"), torch.stack(norms).cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "grads_sample.npy"), torch.cat(samples).cpu().numpy().astype(np.float32))
+
+
 def self_launch(n: int, script: str = None, argv=None) -> int:
     """`python bench.py --gpus N` from a plain shell: start N fresh rank processes (one per GPU; RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* in their environment, the same contract torch.distributed.run uses) BEFORE anything in this
@@ -228,7 +258,12 @@ def main():
                     help="contraction kernels: bf16x6 = split-bf16 (six bf16 MFMAs per fp32 product, fp32-equivalent results, "
                          "passes the same parity gates), f16x3 = amax-scaled split-fp16 (three fp16 MFMAs per product, same gates; "
                          "default) or f32 = exact v_mfma_f32_32x32x2_f32")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of --precision, write the loss and the parameter gradients of the last timed step "
+                         "to DIR/*.npy (gradients as a fixed seeded sample; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args.gpus))       # plain `python bench.py --gpus N`: this process never touches a GPU
@@ -364,6 +399,8 @@ def main():
         loss_val = float(loss)
         if not (loss_val == loss_val and abs(loss_val) != float("inf")):
             raise SystemExit(f"non-finite loss {loss_val} ({precision})")
+        if args.dump_outputs and precision == args.precision and rank == 0:
+            dump_outputs(args.dump_outputs, loss_val, model.named_parameters())     # before any later step overwrites p.grad
         allreduce_ms = round(reducer.last_allreduce_ms(), 3) if (world > 1 and sg is not None and reducer.last_allreduce_ms() is not None) else None
         comm = None
         if world > 1 and sg is None:
