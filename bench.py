@@ -12,11 +12,19 @@ Synthetic data: images U[0,1), targets Bernoulli(0.3), generated on device (seed
 default-init under torch.manual_seed(0) with the W_z BatchNorm gamma re-drawn N(1, 0.1) so the attention
 branch is live.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
-  roofline     : dominant kernel's executed MFMA FLOP/s (HIP events around every launch, on the launch stream) vs the
-                 dense MFMA peak of the arithmetic it runs on, with its algorithmic bytes / FLOPs per launch
-  exact_f32    : the same step with every contraction on v_mfma_f32_32x32x2_f32, same --steps / --warmup, own roofline
-  cpu_baseline : the oracle (CPU restatement) timed on the host cores on a bounded sample (N=1 run only)
+A plain run sets up, runs the W warm-up and K timed steps of --precision, writes --dump-outputs if given and prints
+ONE JSON line (rank 0): the driver's contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step) and
+what the timed loop itself yields (host enqueue time, loss, peak memory, configuration).
+
+--full adds everything that takes work of its own after the timed steps (the --no-* options drop single parts of it):
+  roofline       : dominant kernel's executed MFMA FLOP/s (HIP events around every launch, on the launch stream) vs the
+                   dense MFMA peak of the arithmetic it runs on, with its algorithmic bytes / FLOPs per launch
+  fusion_block   : one TPAVIModule forward + backward alone on the GPU, its MFMA utilisation (N=1 run only)
+  exact_f32      : the same step with every contraction on v_mfma_f32_32x32x2_f32, same --steps / --warmup, own roofline
+  config3_f16 / config3_bf16 : the 16-bit configurations (BASELINE.json configs[2]), same --steps / --warmup
+  optimizer_step : the fused Adam kernel and the weight-image refresh it triggers
+  graph_replay_ms_per_step (or eager_ms_per_step with --graph) : the launch mode that was not timed, in a child process
+  cpu_baseline   : the oracle (CPU restatement) timed on the host cores on a bounded sample (N=1 run only)
 
 --dump-outputs DIR writes what the last timed step of --precision computed (loss, parameter gradients) to DIR/*.npy.
 """
@@ -243,6 +251,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure everything else: per-kernel roofline, "
+                    "fusion block, exact-fp32 and 16-bit legs, optimizer step, the other launch mode, CPU baseline (see the module "
+                    "docstring; the --no-* options below drop parts of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-exact-f32", action="store_true", help="skip the secondary exact-fp32 measurement")
     ap.add_argument("--no-config3", action="store_true", help="skip the fp16-arithmetic leg (BASELINE.json configs[2])")
@@ -264,6 +275,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if os.environ.get("GLF_BENCH_DUMP") and not args.full:
+        ap.error("GLF_BENCH_DUMP writes the per-launch tables of the roofline pass, which only --full runs")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args.gpus))       # plain `python bench.py --gpus N`: this process never touches a GPU
@@ -348,9 +361,9 @@ def main():
 
     def run_leg(precision: str):
         """W untimed warm-up steps, then EXACTLY K timed steps between two fences (no per-launch events inside the timed
-        region).  Then, outside the timed region, the per-kernel figures: 1 untimed + up to 2 steps on ONE stream with a
-        HIP event pair around every contraction launch (on side streams a launch's event interval would include the time
-        it shared the chip with other streams' kernels)."""
+        region).  Then, with --full, outside the timed region, the per-kernel figures: 1 untimed + up to 2 steps on ONE
+        stream with a HIP event pair around every contraction launch (on side streams a launch's event interval would include
+        the time it shared the chip with other streams' kernels)."""
         ops.set_precision(precision)
         ops.reset_weight_images()                  # the previous leg's weight images are not this leg's per-update work
         if precision != args.precision:
@@ -432,6 +445,10 @@ def main():
             fence()
             with open(os.environ["GLF_BENCH_CPROFILE"] + "." + precision + ".txt", "w") as fh:
                 pstats.Stats(pr, stream=fh).sort_stats("tottime").print_stats(45)
+        leg = {"precision": precision, "dt": dt, "loss": loss_val, "prof": [], "iso_steps": 0, "host": host, "host_first": host_first,
+               "allreduce_ms": allreduce_ms, "comm": comm}
+        if not args.full:
+            return leg
         streams = ops.STREAMS
         ops.STREAMS = False
         step()
@@ -447,7 +464,8 @@ def main():
         fence()
         ops.PROFILER = None
         ops.STREAMS = streams
-        return {"precision": precision, "dt": dt, "loss": loss_val, "prof": prof, "iso_steps": iso_steps, "host": host, "host_first": host_first, "allreduce_ms": allreduce_ms, "comm": comm}
+        leg.update(prof=prof, iso_steps=iso_steps)
+        return leg
 
     def roofline_of(leg):
         precision, prof, psteps, dt = leg["precision"], leg["prof"], leg["iso_steps"], leg["dt"]
@@ -574,57 +592,60 @@ def main():
         print(json.dumps(fusion_block_leg(args.precision)))
         return
     main_leg = run_leg(args.precision)
-    fusion_main = fusion_block_leg(args.precision) if (world == 1 and not args.no_fusion_block) else None
+    full = args.full
+    fusion_main = fusion_block_leg(args.precision) if (full and world == 1 and not args.no_fusion_block) else None
     # second leg with the SAME --steps / --warmup: the strictly-fp32 step (v_mfma_f32_32x32x2_f32 everywhere), its own roofline
-    exact_leg = run_leg("f32") if (args.precision != "f32" and not args.no_exact_f32) else None
+    exact_leg = run_leg("f32") if (full and args.precision != "f32" and not args.no_exact_f32) else None
     # third leg, same --steps / --warmup: BASELINE.json configs[2] (16-bit MFMA arithmetic): fp16 operands, one MFMA per product
-    c3_leg = run_leg("f16") if (args.precision == "f16x3" and not args.no_config3) else None
+    c3_leg = run_leg("f16") if (full and args.precision == "f16x3" and not args.no_config3) else None
     # fourth leg: BASELINE.json configs[2] AS STATED -- bf16 storage of activations / saved tensors / activation gradients (ops16)
-    s16_leg = run_leg("bf16") if (args.precision == "f16x3" and not args.no_bf16) else None
+    s16_leg = run_leg("bf16") if (full and args.precision == "f16x3" and not args.no_bf16) else None
     s16_peak_mem = round(torch.cuda.max_memory_allocated() / 2**30, 2) if s16_leg is not None else None
     fusion_s16 = fusion_block_leg("bf16") if (s16_leg is not None and world == 1 and not args.no_fusion_block) else None
     ops.set_precision(args.precision)
 
-    # secondary figure (outside the metric, which excludes the optimizer): the fused Adam step over
-    # the gradients of the last backward -- HBM-bound, 16 B read + 12 B written per element
-    from glfusion_amd.optim import Adam
-    opt = Adam(model.parameters(), lr=3e-4, weight_decay=1e-5)              # main.py:162-165
-    if any(p.grad is None for p in params if p.requires_grad) and main_leg is not None:
-        step()                                                             # (the graph legs release their static gradients)
-    opt.step()
-    torch.cuda.synchronize()
-    ev0, ev1, ev2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-    refresh, ops.refresh_weights = ops.refresh_weights, (lambda: None)     # time the Adam kernel alone ...
-    import glfusion_amd.optim as _optim
-    _optim.refresh_weights = ops.refresh_weights
-    ev0.record()
-    for _ in range(5):
+    optimizer_step = None
+    if full:
+        # secondary figure (outside the metric, which excludes the optimizer): the fused Adam step over
+        # the gradients of the last backward -- HBM-bound, 16 B read + 12 B written per element
+        from glfusion_amd.optim import Adam
+        opt = Adam(model.parameters(), lr=3e-4, weight_decay=1e-5)              # main.py:162-165
+        if any(p.grad is None for p in params if p.requires_grad) and main_leg is not None:
+            step()                                                             # (the graph legs release their static gradients)
         opt.step()
-    ev1.record()
-    ops.refresh_weights = _optim.refresh_weights = refresh                 # ... and the weight-image refresh it triggers
-    for _ in range(5):
-        ops.refresh_weights()
-    ev2.record()
-    torch.cuda.synchronize()
-    adam_ms = ev0.elapsed_time(ev1) / 5
-    refresh_ms = ev1.elapsed_time(ev2) / 5
-    adam_elems = sum(p.numel() for p in model.parameters() if p.grad is not None)
-    optimizer_step = {"kernel": "adam_kernel (glf_adam_step, one launch for all parameters)", "ms": round(adam_ms, 3),
-                      "elements": adam_elems, "achieved": round(28.0 * adam_elems / adam_ms / 1e6, 1), "peak": HBM_PEAK_GBS,
-                      "unit": "GB/s", "frac": round(28.0 * adam_elems / adam_ms / 1e6 / HBM_PEAK_GBS, 4), "bound": "hbm",
-                      "weights_refresh_ms": round(refresh_ms, 3),
-                      "weights_refresh": "glf_weights_refresh: every weight-derived image (layouts, maxima, pre-split fp16 images) in 4 launches; "
-                                         "part of the timed step"}
+        torch.cuda.synchronize()
+        ev0, ev1, ev2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        refresh, ops.refresh_weights = ops.refresh_weights, (lambda: None)     # time the Adam kernel alone ...
+        import glfusion_amd.optim as _optim
+        _optim.refresh_weights = ops.refresh_weights
+        ev0.record()
+        for _ in range(5):
+            opt.step()
+        ev1.record()
+        ops.refresh_weights = _optim.refresh_weights = refresh                 # ... and the weight-image refresh it triggers
+        for _ in range(5):
+            ops.refresh_weights()
+        ev2.record()
+        torch.cuda.synchronize()
+        adam_ms = ev0.elapsed_time(ev1) / 5
+        refresh_ms = ev1.elapsed_time(ev2) / 5
+        adam_elems = sum(p.numel() for p in model.parameters() if p.grad is not None)
+        optimizer_step = {"kernel": "adam_kernel (glf_adam_step, one launch for all parameters)", "ms": round(adam_ms, 3),
+                          "elements": adam_elems, "achieved": round(28.0 * adam_elems / adam_ms / 1e6, 1), "peak": HBM_PEAK_GBS,
+                          "unit": "GB/s", "frac": round(28.0 * adam_elems / adam_ms / 1e6 / HBM_PEAK_GBS, 4), "bound": "hbm",
+                          "weights_refresh_ms": round(refresh_ms, 3),
+                          "weights_refresh": "glf_weights_refresh: every weight-derived image (layouts, maxima, pre-split fp16 images) in 4 launches; "
+                                             "part of the timed step"}
 
     # the launch mode that was NOT timed, for comparison (outside the metric), in a CHILD process: a capture that goes wrong takes
-    # the child down, not this line.  Same workload, --steps 5 --warmup 2, main leg only.
+    # the child down, not this line.  Same workload, --steps 5 --warmup 2: a plain run, main leg only.
     other_ms = None
-    if world == 1 and rank == 0 and not args.no_other_mode:
+    if full and world == 1 and rank == 0 and not args.no_other_mode:
         import subprocess
         gc.collect()
         torch.cuda.empty_cache()
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "2", "--clips", str(args.clips), "--precision", args.precision,
-               "--no-exact-f32", "--no-config3", "--no-bf16", "--no-cpu-baseline", "--no-other-mode"] + ([] if use_graph else ["--graph"])
+        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "2", "--clips", str(args.clips), "--precision", args.precision] + \
+              ([] if use_graph else ["--graph"])
         # (the child must not inherit a profiler's preload: under rocprofv3 it would write into the parent's output directory)
         env = {k: v for k, v in os.environ.items() if k not in ("GLF_BENCH_GRAPH", "GLF_BENCH_DUMP", "RANK", "WORLD_SIZE", "LOCAL_RANK")
                and not k.startswith(("ROCP", "ROCPROF", "ROCTRACER")) and not (k == "LD_PRELOAD" and "rocprof" in v.lower())}
@@ -648,8 +669,6 @@ def main():
             "host_enqueue_ms_first_step_idle_queue": round(main_leg["host_first"] * 1e3, 2),
             "launch": ("one hipGraph replay per step (forward + loss + backward + weight-image refresh recorded once; every kernel "
                        "runs on every replay)" if use_graph else "eager: every kernel launched from Python (incl. the weight-image refresh)"),
-            ("eager_ms_per_step" if use_graph else "graph_replay_ms_per_step"):
-                (round(other_ms, 2) if other_ms is not None else None),
             "dtype": {"f32": "f32", "bf16x6": "f32 (split-bf16 x6 MFMA, fp32 accumulate: fp32-equivalent)",
                       "f16x3": "f32 (amax-scaled split-fp16 x3 MFMA, fp32 accumulate: fp32-equivalent)",
                       "f16": "f16 operands (amax-scaled, one MFMA per product), fp32 accumulate, fp32 storage: NOT fp32-equivalent "
@@ -670,7 +689,7 @@ def main():
                          "f16x3": "fp32 operands and results; each product = 3 fp16 MFMAs on an amax-scaled 2-way split (22 bits), fp32 "
                                   "accumulate; K=2048 GEMM error vs fp64 7e-7 (exact fp32 kernel 3e-7); every parity gate of tests/ "
                                   "(masks / Dice within 1e-4 of the fp32 reference, gradients within its fp32-vs-fp64 noise) passes "
-                                  "under this mode; the exact-fp32 step is reported as exact_f32",
+                                  "under this mode; the exact-fp32 step is reported as exact_f32 (--full)",
                          "f16": "fp32 tensors in HBM; every contraction operand is rounded to fp16 (11 bits) after a per-tensor power-of-two "
                                 "scale, one MFMA per product, fp32 accumulate; parity is judged at the looser tolerance written in "
                                 "tests/test_gpu_model.py::test_f16_mode_parity, never as the fp32 headline",
@@ -678,8 +697,10 @@ def main():
                                  "statistics, one bf16 MFMA per product, fp32 accumulate; parity at the tolerances written in tests/test_gpu_s16.py, "
                                  "never as the fp32 headline"}[args.precision],
             "loss": main_leg["loss"], "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 2),
-            "roofline": roofline_of(main_leg),
         }
+        if full:
+            out["eager_ms_per_step" if use_graph else "graph_replay_ms_per_step"] = round(other_ms, 2) if other_ms is not None else None
+            out["roofline"] = roofline_of(main_leg)
         if fusion_main is not None:
             out["fusion_block"] = fusion_main
         if exact_leg is not None:
@@ -705,8 +726,9 @@ def main():
                                            "v_mfma_f32_32x32x16_bf16 per product on operands staged global -> LDS by LDS-DMA; NOT fp32-equivalent and "
                                            "never the headline (tolerances: tests/test_gpu_s16.py)",
                                    "roofline": roofline_of(s16_leg), "fusion_block": fusion_s16}
-        out["optimizer_step"] = optimizer_step
-        if world == 1 and not args.no_cpu_baseline:
+        if optimizer_step is not None:
+            out["optimizer_step"] = optimizer_step
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,16 +1,17 @@
 # the round's judged artefacts: default bench line, kernel stats of the same command, one-stream kernel stats, HBM traffic passes
 export PYTHONUNBUFFERED=1
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/../.." && pwd)
+export OUT=${OUT:-/tmp/bench_out}; mkdir -p $OUT      # where the outputs go
 cd $R
-timeout -k 10 900 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err; tail -1 gpurun_out/bench_default.json | cut -c1-400
-GLF_BENCH_DUMP=$R/gpurun_out/per_shape timeout -k 10 400 python bench.py --steps 4 --warmup 2 --no-config3 --no-cpu-baseline > gpurun_out/bench_dump.json 2>/dev/null
+timeout -k 10 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.json | cut -c1-400
+GLF_BENCH_DUMP=$OUT/per_shape timeout -k 10 400 python bench.py --steps 4 --warmup 2 --full --no-config3 --no-cpu-baseline > $OUT/bench_dump.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/ks1 -o p --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --no-config3 --no-cpu-baseline --no-exact-f32 > /tmp/ks1.log 2>&1 || tail -3 /tmp/ks1.log
-cp $(find /tmp/ks1 -name "*kernel_stats.csv" | head -1) $R/gpurun_out/ks_streams.csv
-GLF_STREAMS=0 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/ks0 -o p --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --no-config3 --no-cpu-baseline --no-exact-f32 > /tmp/ks0.log 2>&1 || tail -3 /tmp/ks0.log
-cp $(find /tmp/ks0 -name "*kernel_stats.csv" | head -1) $R/gpurun_out/ks_one_stream.csv
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/ks1 -o p --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --full --no-config3 --no-cpu-baseline --no-exact-f32 > /tmp/ks1.log 2>&1 || tail -3 /tmp/ks1.log
+cp $(find /tmp/ks1 -name "*kernel_stats.csv" | head -1) $OUT/ks_streams.csv
+GLF_STREAMS=0 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/ks0 -o p --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --full --no-config3 --no-cpu-baseline --no-exact-f32 > /tmp/ks0.log 2>&1 || tail -3 /tmp/ks0.log
+cp $(find /tmp/ks0 -name "*kernel_stats.csv" | head -1) $OUT/ks_one_stream.csv
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 500 rocprofv3 --pmc $c --kernel-trace -d /tmp/pmc_$c -o p --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-config3 --no-cpu-baseline --no-exact-f32 > /tmp/pmc_$c.log 2>&1 || tail -3 /tmp/pmc_$c.log
+  timeout -k 10 500 rocprofv3 --pmc $c --kernel-trace -d /tmp/pmc_$c -o p --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --full --no-config3 --no-cpu-baseline --no-exact-f32 > /tmp/pmc_$c.log 2>&1 || tail -3 /tmp/pmc_$c.log
 done
-python3 $R/profiles/summarize_pmc.py $(find /tmp/pmc_FETCH_SIZE -name "*counter_collection.csv" | head -1) $(find /tmp/pmc_WRITE_SIZE -name "*counter_collection.csv" | head -1) > $R/gpurun_out/pmc_hbm_traffic.csv
-head -8 $R/gpurun_out/pmc_hbm_traffic.csv
+python3 $R/profiles/summarize_pmc.py $(find /tmp/pmc_FETCH_SIZE -name "*counter_collection.csv" | head -1) $(find /tmp/pmc_WRITE_SIZE -name "*counter_collection.csv" | head -1) > $OUT/pmc_hbm_traffic.csv
+head -8 $OUT/pmc_hbm_traffic.csv

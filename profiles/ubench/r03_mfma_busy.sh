@@ -1,10 +1,11 @@
 # MFMA-busy of every contraction kernel of the C2 step (final round-3 code): rocprofv3 --pmc in its own pass, --kernel-trace only.
 export PYTHONUNBUFFERED=1
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/../.." && pwd)
+export OUT=${OUT:-/tmp/bench_out}; mkdir -p $OUT      # where the outputs go
 cd /tmp && export TMPDIR=/tmp
-GLF_STREAMS=0 timeout -k 10 500 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d /tmp/mb -o p --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-config3 --no-cpu-baseline --no-exact-f32 --no-other-mode > /tmp/mb.log 2>&1 || { tail -3 /tmp/mb.log; exit 1; }
+GLF_STREAMS=0 timeout -k 10 500 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d /tmp/mb -o p --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-config3 --no-cpu-baseline --no-exact-f32 --no-other-mode --full > /tmp/mb.log 2>&1 || { tail -3 /tmp/mb.log; exit 1; }
 f=$(find /tmp/mb -name "*counter_collection.csv" | head -1)
-python3 - "$f" <<'PY' | tee $R/gpurun_out/mfma_busy_step.txt
+python3 - "$f" <<'PY' | tee $OUT/mfma_busy_step.txt
 import collections, csv, re, sys
 agg = collections.defaultdict(lambda: collections.defaultdict(float))
 disp = collections.defaultdict(set)

@@ -1,12 +1,14 @@
 export PYTHONUNBUFFERED=1
-cd $GRAFT_REPO_ROOT
-GLF_BENCH_DUMP=$GRAFT_REPO_ROOT/gpurun_out/per_shape timeout -k 10 400 python bench.py --steps 4 --warmup 2 --no-config3 --no-cpu-baseline --no-exact-f32 $1 > gpurun_out/bench_dump.json 2> gpurun_out/bench_dump.err || tail -5 gpurun_out/bench_dump.err
+R=$(cd "$(dirname "$0")/../.." && pwd)
+export OUT=${OUT:-/tmp/bench_out}; mkdir -p $OUT      # where the outputs go
+cd $R
+GLF_BENCH_DUMP=$OUT/per_shape timeout -k 10 400 python bench.py --steps 4 --warmup 2 --no-config3 --no-cpu-baseline --no-exact-f32 --full $1 > $OUT/bench_dump.json 2> $OUT/bench_dump.err || tail -5 $OUT/bench_dump.err
 python - <<'PY'
-import csv, json
-d = json.load(open("gpurun_out/bench_dump.json"))
+import csv, json, os
+d = json.load(open(os.environ["OUT"] + "/bench_dump.json"))
 r = d["roofline"]
 print("ms/step", d["ms_per_step"], "frac", r["frac"], "avg_launch_ms", r["avg_launch_ms"], "all frac", r["all_contractions"]["mfma_frac_of_peak"], "contr s/step", r["all_contractions"]["s_per_step"])
-rows = list(csv.DictReader(open("gpurun_out/per_shape.f16x3.csv")))
+rows = list(csv.DictReader(open(os.environ["OUT"] + "/per_shape.f16x3.csv")))
 tot = sum(float(x["ms_per_step"]) for x in rows)
 print("sum of per-shape ms/step", round(tot, 1))
 for x in rows[:45]:

@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r04
 mkdir -p $O
 PARTS=${@:-ks shapes pmc busy bench}
-COMMON="--no-config3 --no-cpu-baseline --no-exact-f32 --no-other-mode --no-bf16 --no-fusion-block"
+COMMON="--full --no-config3 --no-cpu-baseline --no-exact-f32 --no-other-mode --no-bf16 --no-fusion-block"
 cd /tmp && export TMPDIR=/tmp
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 
@@ -64,6 +64,6 @@ if has bench; then
   cd $R
   # the bench line quotes the stamped PMC figures: put this call's passes where bench.py looks for them (profiles/), as they will be committed
   cp $O/r04_bench_c2_*_pmc_hbm_traffic.* $O/r04_fusion_block_*_mfma_busy.* $R/profiles/ 2>/dev/null
-  timeout -k 10 900 python bench.py > $O/r04_bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
+  timeout -k 10 900 python bench.py --full > $O/r04_bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
   tail -1 $O/r04_bench_default.json | cut -c1-400
 fi
