@@ -18,7 +18,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ._lib import GemmParams, TpaviParams, WJ_CVT_BF16, check, lib
+from ._lib import AttnParams, GemmParams, TpaviParams, WJ_CVT_BF16, check, lib
 from . import ops as _o
 
 BF = torch.bfloat16
@@ -744,6 +744,16 @@ def transpose16(x: torch.Tensor, rows: int, cols: int, batch: int = 1) -> torch.
 # ----------------------------------------------------------------------------------------
 # the fusion block (TPAVIModule.forward, ours.py:845-917), dot mode
 # ----------------------------------------------------------------------------------------
+def _attn_params16(n: int, L: int, ci: int) -> AttnParams:
+    """glf_attn_params of the fused 16-bit softmax attention: theta / phi / g / dtheta / dphi / dg are column slices of the
+    [rows][3 ci] qkv / dqkv buffers, y and dy dense [rows][ci]."""
+    ap = AttnParams()
+    ap.frames, ap.L, ap.ci = n, L, ci
+    ap.ldq = ap.ldk = ap.ldv = ap.ldd = 3 * ci
+    ap.ldy = ap.lddy = ci
+    return ap
+
+
 class Tpavi16Fn(Function):
     @staticmethod
     def forward(ctx, x, th_w, th_b, ph_w, ph_b, g_w, g_b, wz_w, wz_b, bn_g, bn_b, ln_g, ln_b, rmean, rvar, nbt, training: bool,
@@ -752,8 +762,8 @@ class Tpavi16Fn(Function):
         x = _contig(_chk16(x, "TPAVI input"))
         if x.dim() != 5:
             raise RuntimeError("TPAVI input must be [N, V, h, w, C]")
-        if mode != "dot":
-            raise RuntimeError("glfusion_amd: 16-bit storage builds TPAVI mode 'dot' (the shipped model); 'embedded' runs under the fp32-storage precisions")
+        if mode not in ("dot", "embedded"):
+            raise RuntimeError(f"glfusion_amd: 16-bit storage builds TPAVI modes 'dot' and 'embedded' (got {mode!r})")
         n, v, h, w_, c = x.shape
         L = v * h * w_
         rows = n * L
@@ -766,7 +776,7 @@ class Tpavi16Fn(Function):
         Wcat, bcat = _qkv_weights((th_w, ph_w, g_w, th_b, ph_b, g_b))
         c3 = 3 * ci
         qkv = torch.empty(rows, c3, dtype=BF, device=dev)
-        if BLOCK_CALLS and _o.PROFILER is None:
+        if BLOCK_CALLS and _o.PROFILER is None and mode == "dot":
             # the whole block as ONE C call (include/glfusion.h: glf_s16_tpavi_fwd); the composed sequence below is the same launches,
             # kept for the per-contraction profiler hooks (tests/test_gpu_s16.py checks the two bit for bit)
             tp = TpaviParams(n, L, c, ci, int(training), bn_eps, momentum, ln_eps)
@@ -782,18 +792,25 @@ class Tpavi16Fn(Function):
                                         _p(rmean), _p(rvar), _p(nbt), _p(ln_g), _p(ln_b), _p(z), _p(qkv), _p(attT), _p(y), _p(wz), _p(mean), _p(invstd),
                                         _p(rmu), _p(rrs), C.byref(tp), _p(ws), nws, _stream()), "s16_tpavi_fwd")
             ctx.save_for_backward(x, qkv, attT, y, wz, mean, invstd, rmu, rrs, Wcat, zW, bn_g, bn_b, ln_g)
-            ctx.cfg = (n, L, c, ci, training, tuple(th_w.shape), tuple(wz_w.shape))
+            ctx.cfg = (n, L, c, ci, training, tuple(th_w.shape), tuple(wz_w.shape), mode)
             ctx.owners = (wz_w,)
             ctx.tp = tp
             return z
         gemm16("nt", x, weight16(Wcat, Wcat, "w"), qkv, M=rows, N=c3, K=c, lda=c, ldb=c, ldc=c3, bias=bcat)
         th, ph, g = qkv[:, 0:ci], qkv[:, ci:2 * ci], qkv[:, 2 * ci:]
         bq = L * c3
-        # M_n^T[a][b] = sum_r g[r][a] phi[r][b] / L  (TN with A = g, B = phi): the B operand of y_n = theta_n M_n as it stands
-        attT = torch.empty(n, ci, ci, dtype=BF, device=dev)
-        gemm16("tn", g, ph, attT, M=ci, N=ci, K=L, lda=c3, ldb=c3, ldc=ci, batch=n, bsa=bq, bsb=bq, bsc=ci * ci, alpha=1.0 / L)
         y = torch.empty(rows, ci, dtype=BF, device=dev)
-        gemm16("nt", th, attT, y, M=L, N=ci, K=ci, lda=c3, ldb=ci, ldc=ci, batch=n, bsa=bq, bsb=ci * ci, bsc=L * ci)
+        if mode == "embedded":
+            # y_n = softmax(theta_n phi_n^T, dim=-1) g_n, fused (csrc/attn_s16.hip); attT holds the row log-sum-exp that backward
+            # recomputes the scores against
+            attT = torch.empty(rows, **f32)
+            check(lib.glf_s16_attn_softmax_fwd(_p(th), _p(ph), _p(g), _p(y), _p(attT), C.byref(_attn_params16(n, L, ci)), _stream()),
+                  "s16_attn_softmax_fwd")
+        else:
+            # M_n^T[a][b] = sum_r g[r][a] phi[r][b] / L  (TN with A = g, B = phi): the B operand of y_n = theta_n M_n as it stands
+            attT = torch.empty(n, ci, ci, dtype=BF, device=dev)
+            gemm16("tn", g, ph, attT, M=ci, N=ci, K=L, lda=c3, ldb=c3, ldc=ci, batch=n, bsa=bq, bsb=bq, bsc=ci * ci, alpha=1.0 / L)
+            gemm16("nt", th, attT, y, M=L, N=ci, K=ci, lda=c3, ldb=ci, ldc=ci, batch=n, bsa=bq, bsb=ci * ci, bsc=L * ci)
         wz = torch.empty(rows, c, dtype=BF, device=dev)
         sums = _o.stats_slot(c, dev) if training else None
         gemm16("nt", y, weight16(zW, wz_w, "w"), wz, M=rows, N=c, K=ci, lda=ci, ldb=ci, ldc=c, bias=wz_b, colstats=sums)
@@ -810,7 +827,7 @@ class Tpavi16Fn(Function):
         check(lib.glf_s16_bn_res_ln_fwd(_p(wz), _p(x), _p(mean), _p(invstd), _p(bn_g), _p(bn_b), _p(ln_g), _p(ln_b), ln_eps, _p(z), _p(rmu), _p(rrs),
                                         rows, c, _stream()), "s16_bn_res_ln_fwd")
         ctx.save_for_backward(x, qkv, attT, y, wz, mean, invstd, rmu, rrs, Wcat, zW, bn_g, bn_b, ln_g)
-        ctx.cfg = (n, L, c, ci, training, tuple(th_w.shape), tuple(wz_w.shape))
+        ctx.cfg = (n, L, c, ci, training, tuple(th_w.shape), tuple(wz_w.shape), mode)
         ctx.owners = (wz_w,)
         return z
 
@@ -818,7 +835,7 @@ class Tpavi16Fn(Function):
     @once_differentiable
     def backward(ctx, dz):
         (x, qkv, attT, y, wz, mean, invstd, rmu, rrs, Wcat, zW, bn_g, bn_b, ln_g) = ctx.saved_tensors
-        n, L, c, ci, training, pshape, zshape = ctx.cfg
+        n, L, c, ci, training, pshape, zshape, mode = ctx.cfg
         (wz_o,) = ctx.owners
         rows = n * L
         dev = dz.device
@@ -826,7 +843,7 @@ class Tpavi16Fn(Function):
         dz = _contig(dz)
         c3 = 3 * ci
         bq, bs = L * c3, L * ci
-        if BLOCK_CALLS and _o.PROFILER is None:
+        if BLOCK_CALLS and _o.PROFILER is None and mode == "dot":
             tp = TpaviParams(n, L, c, ci, int(training), 0.0, 0.0, 0.0)
             dx = torch.empty(rows, c, dtype=BF, device=dev)
             dWcat, dbcat = torch.empty(c3, c, **f32), torch.empty(c3, **f32)
@@ -863,14 +880,21 @@ class Tpavi16Fn(Function):
         del dwz
         dqkv = torch.empty(rows, c3, dtype=BF, device=dev)
         dth, dph, dg = dqkv[:, 0:ci], dqkv[:, ci:2 * ci], dqkv[:, 2 * ci:]
-        att = transpose16(attT, ci, ci, n)                     # M_n
-        gemm16("nt", dy, att, dth, M=L, N=ci, K=ci, lda=ci, ldb=ci, ldc=c3, batch=n, bsa=bs, bsb=ci * ci, bsc=bq)
-        dM = torch.empty(n, ci, ci, dtype=BF, device=dev)      # dM_n = theta_n^T dy_n
-        gemm16("tn", th, dy, dM, M=ci, N=ci, K=L, lda=c3, ldb=ci, ldc=ci, batch=n, bsa=bq, bsb=bs, bsc=ci * ci)
-        gemm16("nt", g, dM, dph, M=L, N=ci, K=ci, lda=c3, ldb=ci, ldc=c3, batch=n, bsa=bq, bsb=ci * ci, bsc=bq, alpha=1.0 / L)
-        dMT = transpose16(dM, ci, ci, n)
-        gemm16("nt", ph, dMT, dg, M=L, N=ci, K=ci, lda=c3, ldb=ci, ldc=c3, batch=n, bsa=bq, bsb=ci * ci, bsc=bq, alpha=1.0 / L)
-        del dy, att, dM, dMT
+        if mode == "embedded":
+            # attT is the row log-sum-exp here; one call writes all three column slices of dqkv
+            dsum = torch.empty(rows, **f32)
+            check(lib.glf_s16_attn_softmax_bwd(_p(th), _p(ph), _p(g), _p(y), _p(dy), _p(attT), _p(dth), _p(dph), _p(dg), _p(dsum),
+                                               C.byref(_attn_params16(n, L, ci)), _stream()), "s16_attn_softmax_bwd")
+            del dy, dsum
+        else:
+            att = transpose16(attT, ci, ci, n)                     # M_n
+            gemm16("nt", dy, att, dth, M=L, N=ci, K=ci, lda=ci, ldb=ci, ldc=c3, batch=n, bsa=bs, bsb=ci * ci, bsc=bq)
+            dM = torch.empty(n, ci, ci, dtype=BF, device=dev)      # dM_n = theta_n^T dy_n
+            gemm16("tn", th, dy, dM, M=ci, N=ci, K=L, lda=c3, ldb=ci, ldc=ci, batch=n, bsa=bq, bsb=bs, bsc=ci * ci)
+            gemm16("nt", g, dM, dph, M=L, N=ci, K=ci, lda=c3, ldb=ci, ldc=c3, batch=n, bsa=bq, bsb=ci * ci, bsc=bq, alpha=1.0 / L)
+            dMT = transpose16(dM, ci, ci, n)
+            gemm16("nt", ph, dMT, dg, M=L, N=ci, K=ci, lda=c3, ldb=ci, ldc=c3, batch=n, bsa=bq, bsb=ci * ci, bsc=bq, alpha=1.0 / L)
+            del dy, att, dM, dMT
         dWcat = torch.empty(c3, c, **f32)
         gemm16("tn", dqkv, x, dWcat, M=c3, N=c, K=rows, lda=c3, ldb=c, ldc=c, split=tn_split16(rows, c3, c, 1))
         dbcat = colsum16(dqkv, rows, c3)

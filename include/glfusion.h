@@ -262,6 +262,20 @@ int glf_attn_softmax_fwd(const float* theta, const float* phi, const float* g, f
  * dsum_ws: caller-owned scratch of frames*L floats. */
 int glf_attn_softmax_bwd(const float* theta, const float* phi, const float* g, const float* y, const float* dy, const float* lse,
                          float* dtheta, float* dphi, float* dg, float* dsum_ws, const glf_attn_params* p, glf_stream_t stream);
+/* The same attention under 16-bit storage: theta, phi, g, y, dy and the three gradients are bf16 (void* = bf16 data), lse and
+ * dsum_ws fp32 [frames*L].  S = theta phi^T on bf16 MFMA with fp32 accumulation; row max, row sum and rescaling in fp32; P is
+ * rounded to bf16 only as the A operand of P g; y is accumulated and normalised in fp32 and stored as bf16 once.  Backward:
+ * D = rowsum(dy o y) and dS = P (dP - D) in fp32, dS rounded to bf16 only as an MFMA operand; every output element is written
+ * exactly once (no atomics, no zero fill: bitwise reproducible).  Ci % 64 == 0, Ci <= 1024, any L >= 1; every row stride
+ * (ldq, ldk, ldv, ldy; backward also lddy, ldd) a multiple of 8 elements and >= Ci, theta / phi / g / y / dy 16-byte
+ * aligned; frame stride = L * row stride.  dsum_ws is caller-owned; the calls allocate nothing and never wait on the host.
+ * Arguments are checked before any HIP runtime call: GLF_ERR_NULL, GLF_ERR_BAD_SHAPE (frames or L < 1),
+ * GLF_ERR_UNSUPPORTED (Ci, strides, alignment). */
+int glf_s16_attn_softmax_fwd(const void* theta, const void* phi, const void* g, void* y, float* lse,
+                             const glf_attn_params* p, glf_stream_t stream);
+int glf_s16_attn_softmax_bwd(const void* theta, const void* phi, const void* g, const void* y, const void* dy,
+                             const float* lse, void* dtheta, void* dphi, void* dg, float* dsum_ws,
+                             const glf_attn_params* p, glf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Weight layout: torch OIHW [Cout][Cin][kh][kw] <-> tap-major [kh*kw][Cout][Cin].
