@@ -2,7 +2,7 @@
 activation gradients in HBM, fp32 master weights, fp32 accumulate; glfusion_amd.ops16, csrc/gemm_s16.hip, csrc/s16_ops.hip).
 
 Three layers of evidence, each with its own stated tolerance:
-  * kernels against torch on THE SAME bf16 inputs: what differs is one rounding of the result to bf16 (2^-9 relative) and the
+  * kernels against torch on THE SAME bf16 inputs: what differs is one rounding of the result to bf16 (unit roundoff 2^-8: 8-bit significand, round-to-nearest-even) and the
     order of fp32 sums -- relative L2 <= 4e-3 for bf16 results, <= 1e-5 for fp32 results (weight gradients, statistics);
   * blocks (Bottleneck, DeepLabHead, TPAVIModule) against the oracle evaluated in float64: a few layers of bf16 rounding --
     output, input gradient and the median parameter gradient within 5e-2 relative L2, no tensor beyond 0.2;
@@ -22,6 +22,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from oracle import glfusion_ref as orc   # the checker (tests only)
+from test_gpu_s16_gemm import gate_interval   # per-element interval against float64
 
 DEV = "cuda"
 BF = torch.bfloat16
@@ -84,6 +85,19 @@ def test_s16_conv2d_fwd_dgrad_wgrad(case):
     assert x.grad.dtype == BF and wt.grad.dtype == torch.float32
     assert l2(x.grad, xr.grad.permute(0, 2, 3, 1)) <= 4e-3
     assert l2(wt.grad, wr.grad) <= 1e-5
+    # element by element against float64 on the same bf16 operands: the derived interval of tests/test_gpu_s16_gemm.py (evidence (b))
+    x64 = x.detach().cpu().double().permute(0, 3, 1, 2).requires_grad_(True)
+    w64 = wq.cpu().double().requires_grad_(True)
+    dy64 = dy.cpu().double().permute(0, 3, 1, 2)
+    y64 = F.conv2d(x64, w64, None, stride, pad, dil)
+    y64.backward(dy64)
+    xa, wa = x64.detach().abs().requires_grad_(True), w64.detach().abs().requires_grad_(True)
+    ya = F.conv2d(xa, wa, None, stride, pad, dil)
+    ya.backward(dy64.abs())
+    nhwc = lambda t: t.detach().permute(0, 2, 3, 1)
+    gate_interval(y.detach().cpu(), nhwc(y64), nhwc(ya), cin * k * k, True, "y")
+    gate_interval(x.grad.cpu(), nhwc(x64.grad), nhwc(xa.grad), cout * k * k, True, "x.grad")
+    gate_interval(wt.grad.cpu(), w64.grad, wa.grad, int(y.numel()) // cout, False, "wt.grad")
 
 
 def test_s16_conv_bias_and_narrow_head():
