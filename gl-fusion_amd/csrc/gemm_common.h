@@ -26,7 +26,7 @@ struct GemmArgs {
     float* partial;                             // TN only: partial-sum slabs [batch*split][kept taps][M][N] (null = atomics into C)
     unsigned long long* stamps;                 // diagnostic builds (-DGLF_STAMPS) only
     int a_presplit, b_presplit;                 // f16x3 / f16 kernels: the operand pointer is the packed pre-split image (glf_split_f16_packed)
-    int flags;                                  // f16x3 rows kernel: bit 0 = waves 4-7 run at s_setprio 1 (the younger half of an 8-wave workgroup)
+    int flags;                                  // f16x3 rows kernel: bits 8-15 = tile-group size (row tiles walked together, 0 = plain row-major order)
 };
 constexpr int ZERO_PAGE_FLOATS = 1 << 18;
 

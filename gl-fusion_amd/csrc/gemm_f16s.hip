@@ -57,11 +57,6 @@ constexpr size_t SMEM_ROWS_H8 = 3 * BUF8 + 16 + 8192;
 constexpr size_t SMEM_ROWS_H8 = 3 * BUF8 + 16;
 #endif
 
-// M16: the products run on v_mfma_f32_16x16x32_f16 (16 x 16 output tiles, the whole 32-deep K-tile per instruction)
-// instead of v_mfma_f32_32x32x16_f16: the same MFMA cycles per FLOP, the same LDS fragment traffic, but under load the
-// chip holds a higher clock on the smaller shape (MI355X_MICROARCH.md, DVFS item 7).  LDS rows keep their 64-byte
-// layout; only the 16-byte chunk swizzle differs (chunk g(c) ^ (row >> 2 & 3), g = 0,3,1,2: conflict-free ds_read_b128 for
-// the lane -> (row = lane & 15, chunk = lane >> 4) fragment map).
 // PA / BP: the A / B operand arrives PRE-SPLIT in the packed image glf_split_f16_packed writes: every aligned group of four
 // consecutive elements (16 bytes of fp32) is replaced IN PLACE by {h0 h1 h2 h3 l0 l1 l2 l3} (fp16), x * s = h + 2^-11 l with the
 // scale of args.amax_a / amax_b.  Same byte size, same strides, same addressing as the fp32 operand -- the staging path keeps its
@@ -69,7 +64,7 @@ constexpr size_t SMEM_ROWS_H8 = 3 * BUF8 + 16;
 // operand is split ONCE (by glf_split_f16_packed, per tensor) instead of in every tile of every launch that reads it.
 // (The variants that were measured and dropped -- deeper register prefetch, ping-pong segments, sched_group_barrier interleave,
 // static wave priorities, other tile-group sizes -- are described with their numbers in DESIGN.md section 8; their code is gone.)
-template <bool GATHER, int NP, bool M16, bool BP, bool PA = false>
+template <bool GATHER, int NP, bool BP, bool PA = false>
 __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs args) {
     const int pM = args.M, pN = args.N, pK = args.K, p_lda = args.lda, p_ldb = args.ldb, p_ldc = args.ldc;
     const int p_taps = args.taps, p_gather = args.gather, p_accumulate = args.accumulate;
@@ -283,8 +278,7 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
         }
     };
     // swizzled staging offset of this thread inside a 64-byte row: 16-byte chunk (ac>>1) ^ ((row>>2)&3), half ac&1
-    const int st_chunk = M16 ? (int)((0x2130u >> (4 * (ac >> 1))) & 3u) : (ac >> 1);      // g = 0,3,1,2 for the 16x16x32 fragment map
-    const int st_off = ar * 64 + (((st_chunk ^ ((ar >> 2) & 3)) << 4) | ((ac & 1) << 3));
+    const int st_off = ar * 64 + ((((ac >> 1) ^ ((ar >> 2) & 3)) << 4) | ((ac & 1) << 3));
 #define GLF_H8_CONV_A(J, buf_)                                                                               \
     {                                                                                                        \
         unsigned char* d = smem_s + (buf_) * BUF8 + st_off + J * 64 * 64;                                    \
@@ -325,7 +319,7 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
         default: if (conv_) GLF_H8_CONV_B(1, buf_) GLF_H8_PIN(BP) if (load_) GLF_H8_LOAD_B(1) GLF_H8_PIN(BP) break;     \
     }
 
-    if (!M16 && ntiles > 0) {
+    if (ntiles > 0) {
         const int sw = (lane >> 2) & 3, hh = lane >> 5;
         const int fo0 = (lane & 31) * 64 + (((0 + hh) ^ sw) << 4);
         const int fo1 = (lane & 31) * 64 + (((2 + hh) ^ sw) << 4);
@@ -572,125 +566,6 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
 #endif
     }
 
-    // ---- 16x16x32 variant: accumulators t[i][j] (main) / u[i][j] (mixed), i = 16-row slab, j = 16-column slab of the
-    //      wave's 64 x 64 tile ----
-    f32x4 t00 = {0}, t01 = {0}, t02 = {0}, t03 = {0}, t10 = {0}, t11 = {0}, t12 = {0}, t13 = {0};
-    f32x4 t20 = {0}, t21 = {0}, t22 = {0}, t23 = {0}, t30 = {0}, t31 = {0}, t32 = {0}, t33 = {0};
-    f32x4 u00 = {0}, u01 = {0}, u02 = {0}, u03 = {0}, u10 = {0}, u11 = {0}, u12 = {0}, u13 = {0};
-    f32x4 u20 = {0}, u21 = {0}, u22 = {0}, u23 = {0}, u30 = {0}, u31 = {0}, u32 = {0}, u33 = {0};
-    if (M16 && ntiles > 0) {
-        const int lr = lane & 15;
-        const int fo = lr * 64 + (((int)((0x2130u >> (4 * (lane >> 4))) & 3u) ^ ((lr >> 2) & 3)) << 4);
-        advance();
-#pragma unroll
-        for (int pc = 0; pc < 6; ++pc) { GLF_H8_PIECE(pc, 0, false, true) }
-        {
-            const bool more = ntiles > 1;
-            if (more) advance();
-#pragma unroll
-            for (int pc = 0; pc < 6; ++pc) { GLF_H8_PIECE(pc, 0, true, more) }
-            if (more) {
-                const bool more2 = ntiles > 2;
-                if (more2) advance();
-#pragma unroll
-                for (int pc = 0; pc < 6; ++pc) { GLF_H8_PIECE(pc, 1, true, more2) }
-            }
-        }
-        __syncthreads();
-#define GLF_MFMA_16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
-        // one 16-row slab of A against one 16-column slab of B: main product into t, the two mixed ones into u
-#define GLF_M16_TILE(t, u, ah, al, bh, bl)                          \
-        t = GLF_MFMA_16(ah, bh, t);                                 \
-        if (NP == 3) { u = GLF_MFMA_16(al, bh, u); u = GLF_MFMA_16(ah, bl, u); }
-#define GLF_M16_A(buf_, s_, dh, dl)                                                                             \
-        {                                                                                                       \
-            const unsigned char* p_ = smem_s + (buf_) * BUF8 + (wm + 16 * (s_)) * 64 + fo;                      \
-            dh = *reinterpret_cast<const f16x8*>(p_);                                                           \
-            if (NP == 3) dl = *reinterpret_cast<const f16x8*>(p_ + PL_A8); else dl = dh;                        \
-        }
-#define GLF_M16_B(buf_, s_, dh, dl)                                                                             \
-        {                                                                                                       \
-            const unsigned char* p_ = smem_s + (buf_) * BUF8 + 2 * PL_A8 + (wn + 16 * (s_)) * 64 + fo;          \
-            dh = *reinterpret_cast<const f16x8*>(p_);                                                           \
-            if (NP == 3) dl = *reinterpret_cast<const f16x8*>(p_ + PL_B8); else dl = dh;                        \
-        }
-        f16x8 a0h, a0l, a1h, a1l, a2h, a2l, a3h, a3l, b0h, b0l, b1h, b1l, b2h, b2l, b3h, b3l;
-        GLF_M16_B(0, 0, b0h, b0l) GLF_M16_B(0, 1, b1h, b1l) GLF_M16_B(0, 2, b2h, b2l)
-        if (!(PA && BP)) GLF_M16_B(0, 3, b3h, b3l)
-        GLF_M16_A(0, 0, a0h, a0l) GLF_M16_A(0, 1, a1h, a1l)
-        int cur = 0, nxt = 1, wr = 2;
-        // Per iteration: slabs 0, 1 of A (loaded one iteration ahead) against all of B while slabs 2, 3 arrive; then slabs 2, 3
-        // column by column, each B slab being replaced by the next tile's as soon as its last product is issued, and slabs
-        // 0, 1 of the next tile are fetched at the half-way point: 64 fragment registers in all, nothing exposed behind the barrier.
-#define GLF_M16_BODY(CONV_, LOAD_, NEXT_)                                                                     \
-        {                                                                                                     \
-            if (LOAD_) advance();                                                                             \
-            GLF_M16_A(cur, 2, a2h, a2l) GLF_M16_A(cur, 3, a3h, a3l)                                           \
-            __builtin_amdgcn_sched_barrier(0);                                                                \
-            GLF_H8_PIECE(0, wr, CONV_, LOAD_)                                                                 \
-            GLF_M16_TILE(t00, u00, a0h, a0l, b0h, b0l) GLF_M16_TILE(t01, u01, a0h, a0l, b1h, b1l)             \
-            GLF_M16_TILE(t02, u02, a0h, a0l, b2h, b2l) GLF_M16_TILE(t03, u03, a0h, a0l, b3h, b3l)             \
-            GLF_H8_PIECE(1, wr, CONV_, LOAD_)                                                                 \
-            GLF_M16_TILE(t10, u10, a1h, a1l, b0h, b0l) GLF_M16_TILE(t11, u11, a1h, a1l, b1h, b1l)             \
-            GLF_M16_TILE(t12, u12, a1h, a1l, b2h, b2l) GLF_M16_TILE(t13, u13, a1h, a1l, b3h, b3l)             \
-            GLF_H8_PIECE(2, wr, CONV_, LOAD_)                                                                 \
-            __builtin_amdgcn_sched_barrier(0);                                                                \
-            if (NEXT_) { GLF_M16_A(nxt, 0, a0h, a0l) GLF_M16_A(nxt, 1, a1h, a1l) }                            \
-            __builtin_amdgcn_sched_barrier(0);                                                                \
-            GLF_M16_TILE(t20, u20, a2h, a2l, b0h, b0l) GLF_M16_TILE(t30, u30, a3h, a3l, b0h, b0l)             \
-            if (NEXT_) GLF_M16_B(nxt, 0, b0h, b0l)                                                            \
-            GLF_H8_PIECE(3, wr, CONV_, LOAD_)                                                                 \
-            GLF_M16_TILE(t21, u21, a2h, a2l, b1h, b1l) GLF_M16_TILE(t31, u31, a3h, a3l, b1h, b1l)             \
-            if (NEXT_) GLF_M16_B(nxt, 1, b1h, b1l)                                                            \
-            GLF_H8_PIECE(4, wr, CONV_, LOAD_)                                                                 \
-            GLF_M16_TILE(t22, u22, a2h, a2l, b2h, b2l) GLF_M16_TILE(t32, u32, a3h, a3l, b2h, b2l)             \
-            if (NEXT_) GLF_M16_B(nxt, 2, b2h, b2l)                                                            \
-            GLF_H8_PIECE(5, wr, CONV_, LOAD_)                                                                 \
-            GLF_M16_TILE(t23, u23, a2h, a2l, b3h, b3l) GLF_M16_TILE(t33, u33, a3h, a3l, b3h, b3l)             \
-            if (NEXT_) GLF_M16_B(nxt, 3, b3h, b3l)                                                            \
-            { const int t_ = cur; cur = nxt; nxt = wr; wr = t_; }                                             \
-            __syncthreads();                                                                                  \
-        }
-        // Pre-split operands: the same products with everything else placed tile by tile (a slot = what is issued behind the
-        // three MFMAs of one 16 x 16 tile; sched_barriers pin it).  B slab 3 of the NEXT tile is not fetched before the barrier
-        // (its registers are busy until the last product) but in the first slot of the next iteration, three tiles before its
-        // first use: no LDS operation is younger than two tiles when the barrier is reached.
-#define GLF_M16_T(t, u, ah, al, bh, bl, SLOT_) GLF_M16_TILE(t, u, ah, al, bh, bl) GLF_IL_PIN() SLOT_ GLF_IL_PIN()
-#define GLF_M16_BODY_IL(CONV_, LOAD_, NEXT_)                                                                  \
-        {                                                                                                     \
-            GLF_M16_T(t00, u00, a0h, a0l, b0h, b0l, { GLF_M16_B(cur, 3, b3h, b3l) GLF_M16_A(cur, 2, a2h, a2l) }) \
-            GLF_M16_T(t01, u01, a0h, a0l, b1h, b1l, { GLF_M16_A(cur, 3, a3h, a3l) })                          \
-            GLF_M16_T(t02, u02, a0h, a0l, b2h, b2l, { if (LOAD_) advance(); })                                \
-            GLF_M16_T(t03, u03, a0h, a0l, b3h, b3l, { if (NEXT_) GLF_M16_A(nxt, 0, a0h, a0l) })               \
-            GLF_M16_T(t10, u10, a1h, a1l, b0h, b0l, { GLF_H8_PIECE(0, wr, CONV_, LOAD_) })                    \
-            GLF_M16_T(t11, u11, a1h, a1l, b1h, b1l, { GLF_H8_PIECE(1, wr, CONV_, LOAD_) })                    \
-            GLF_M16_T(t12, u12, a1h, a1l, b2h, b2l, { GLF_H8_PIECE(2, wr, CONV_, LOAD_) })                    \
-            GLF_M16_T(t13, u13, a1h, a1l, b3h, b3l, { GLF_H8_PIECE(3, wr, CONV_, LOAD_) })                    \
-            GLF_M16_T(t20, u20, a2h, a2l, b0h, b0l, { if (NEXT_) GLF_M16_A(nxt, 1, a1h, a1l) })               \
-            GLF_M16_T(t30, u30, a3h, a3l, b0h, b0l, { if (NEXT_) GLF_M16_B(nxt, 0, b0h, b0l) GLF_H8_PIECE(4, wr, CONV_, LOAD_) }) \
-            GLF_M16_T(t21, u21, a2h, a2l, b1h, b1l, { GLF_H8_PIECE(5, wr, CONV_, LOAD_) })                    \
-            GLF_M16_T(t31, u31, a3h, a3l, b1h, b1l, { if (NEXT_) GLF_M16_B(nxt, 1, b1h, b1l) })               \
-            GLF_M16_T(t22, u22, a2h, a2l, b2h, b2l, {})                                                       \
-            GLF_M16_T(t32, u32, a3h, a3l, b2h, b2l, { if (NEXT_) GLF_M16_B(nxt, 2, b2h, b2l) })               \
-            GLF_M16_T(t23, u23, a2h, a2l, b3h, b3l, {})                                                       \
-            GLF_M16_T(t33, u33, a3h, a3l, b3h, b3l, {})                                                       \
-            { const int t_ = cur; cur = nxt; nxt = wr; wr = t_; }                                             \
-            __syncthreads();                                                                                  \
-        }
-        int it = 0;
-        if (PA && BP) {
-            for (; it + 3 < ntiles; ++it) GLF_M16_BODY_IL(true, true, true)
-            if (it + 2 < ntiles) { GLF_M16_BODY_IL(true, false, true) ++it; }
-            if (it + 1 < ntiles) { GLF_M16_BODY_IL(false, false, true) ++it; }
-            GLF_M16_BODY_IL(false, false, false)
-        } else {
-            for (; it + 3 < ntiles; ++it) GLF_M16_BODY(true, true, true)
-            if (it + 2 < ntiles) { GLF_M16_BODY(true, false, true) ++it; }
-            if (it + 1 < ntiles) { GLF_M16_BODY(false, false, true) ++it; }
-            GLF_M16_BODY(false, false, false)
-        }
-    }
-
     float cmax = 0.f;
     const bool p_colstats = args.colstats != nullptr;
     // one result element -> C (plain / accumulate / region store, or the atomic of per-tap rectangles); cs / cq: the calling
@@ -723,25 +598,13 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
                             (p_bsc % 4) == 0;
     if (wide_store) {
         float* tile = reinterpret_cast<float*>(smem_s) + wave * (64 * 64);
-        if (M16) {        // 16 x 16 tiles: element r of tile (i, j) is row 16 i + 4 (lane >> 4) + r, column 16 j + (lane & 15)
-            const int col_l = lane & 15, row_l = 4 * (lane >> 4);
-            auto park16 = [&](const f32x4& acc, int ti, int tj) __attribute__((always_inline)) {
+        const int col_l = lane & 31, row_l = 4 * (lane >> 5);
+        auto park = [&](const f32x16& acc, int ti, int tj) __attribute__((always_inline)) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) tile[(16 * ti + row_l + r) * 64 + 16 * tj + col_l] = acc[r];
-            };
-            park16(t00 + u00 * 0x1p-11f, 0, 0); park16(t01 + u01 * 0x1p-11f, 0, 1); park16(t02 + u02 * 0x1p-11f, 0, 2); park16(t03 + u03 * 0x1p-11f, 0, 3);
-            park16(t10 + u10 * 0x1p-11f, 1, 0); park16(t11 + u11 * 0x1p-11f, 1, 1); park16(t12 + u12 * 0x1p-11f, 1, 2); park16(t13 + u13 * 0x1p-11f, 1, 3);
-            park16(t20 + u20 * 0x1p-11f, 2, 0); park16(t21 + u21 * 0x1p-11f, 2, 1); park16(t22 + u22 * 0x1p-11f, 2, 2); park16(t23 + u23 * 0x1p-11f, 2, 3);
-            park16(t30 + u30 * 0x1p-11f, 3, 0); park16(t31 + u31 * 0x1p-11f, 3, 1); park16(t32 + u32 * 0x1p-11f, 3, 2); park16(t33 + u33 * 0x1p-11f, 3, 3);
-        } else {
-            const int col_l = lane & 31, row_l = 4 * (lane >> 5);
-            auto park = [&](const f32x16& acc, int ti, int tj) __attribute__((always_inline)) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) tile[(32 * ti + (r & 3) + 8 * (r >> 2) + row_l) * 64 + 32 * tj + col_l] = acc[r];
-            };
-            park(c00 + m00 * 0x1p-11f, 0, 0); park(c01 + m01 * 0x1p-11f, 0, 1);
-            park(c10 + m10 * 0x1p-11f, 1, 0); park(c11 + m11 * 0x1p-11f, 1, 1);
-        }
+            for (int r = 0; r < 16; ++r) tile[(32 * ti + (r & 3) + 8 * (r >> 2) + row_l) * 64 + 32 * tj + col_l] = acc[r];
+        };
+        park(c00 + m00 * 0x1p-11f, 0, 0); park(c01 + m01 * 0x1p-11f, 0, 1);
+        park(c10 + m10 * 0x1p-11f, 1, 0); park(c11 + m11 * 0x1p-11f, 1, 1);
         __syncthreads();
         const int c4 = 4 * (lane & 15), r0 = lane >> 4;
         const int col = tn * BN + wn + c4;
@@ -762,7 +625,7 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
                 ey = rem / r_w; ex = rem - ey * r_w;
             }
             if (p_accumulate && !p_rect && !p_colstats) {
-                // C += result (a dgrad landing on the shortcut's gradient): all 16 old values are requested before the first is
+                // C += result (the accumulate epilogue of glf_gemm): all 16 old values are requested before the first is
                 // needed -- fetched inside the store loop, each of its 4-deep batches waited out a full memory round trip
                 float4 prev[16];
                 const int rowb = tm * BM8 + wm + r0;
@@ -839,7 +702,7 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
                 }
             }
         }
-    } else if (!M16) {
+    } else {
         const int col_l = lane & 31, row_l = 4 * (lane >> 5);
         auto emit = [&](const f32x16& acc, int ti, int tj, double& cs, double& cq) {
             const int col = tn * BN + wn + 32 * tj + col_l;
@@ -861,31 +724,6 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
                 const int col0 = tn * BN + wn + col_l, col1 = col0 + 32;
                 if (col0 < pN) { atomicAdd(st + col0, cs0); atomicAdd(st + pN + col0, cq0); }
                 if (col1 < pN) { atomicAdd(st + col1, cs1); atomicAdd(st + pN + col1, cq1); }
-            }
-        }
-    } else {
-        // 16 x 16 tiles: element r of tile (i, j) is row 16 i + 4 (lane >> 4) + r, column 16 j + (lane & 15)
-        const int col_l = lane & 15, row_l = 4 * (lane >> 4);
-        double cs[4] = {0.0, 0.0, 0.0, 0.0}, cq[4] = {0.0, 0.0, 0.0, 0.0};
-        auto emit16 = [&](const f32x4& acc, int ti, int tj) {
-            const int col = tn * BN + wn + 16 * tj + col_l;
-            if (col >= pN) return;
-            const float bv = p_bias ? p_bias[col] : 0.f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) put(acc[r], tm * BM8 + wm + 16 * ti + row_l + r, col, bv, cs[tj], cq[tj]);
-        };
-        emit16(t00 + u00 * 0x1p-11f, 0, 0); emit16(t01 + u01 * 0x1p-11f, 0, 1); emit16(t02 + u02 * 0x1p-11f, 0, 2); emit16(t03 + u03 * 0x1p-11f, 0, 3);
-        emit16(t10 + u10 * 0x1p-11f, 1, 0); emit16(t11 + u11 * 0x1p-11f, 1, 1); emit16(t12 + u12 * 0x1p-11f, 1, 2); emit16(t13 + u13 * 0x1p-11f, 1, 3);
-        emit16(t20 + u20 * 0x1p-11f, 2, 0); emit16(t21 + u21 * 0x1p-11f, 2, 1); emit16(t22 + u22 * 0x1p-11f, 2, 2); emit16(t23 + u23 * 0x1p-11f, 2, 3);
-        emit16(t30 + u30 * 0x1p-11f, 3, 0); emit16(t31 + u31 * 0x1p-11f, 3, 1); emit16(t32 + u32 * 0x1p-11f, 3, 2); emit16(t33 + u33 * 0x1p-11f, 3, 3);
-        if (args.colstats && p_rect != 1) {
-            double* st = args.colstats;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {               // the four row groups of a column sit in lanes l, l + 16, l + 32, l + 48
-                cs[j] += __shfl_xor(cs[j], 16, 64); cq[j] += __shfl_xor(cq[j], 16, 64);
-                cs[j] += __shfl_xor(cs[j], 32, 64); cq[j] += __shfl_xor(cq[j], 32, 64);
-                const int col = tn * BN + wn + 16 * j + col_l;
-                if (lane < 16 && col < pN) { atomicAdd(st + col, cs[j]); atomicAdd(st + pN + col, cq[j]); }
             }
         }
     }
@@ -1529,10 +1367,10 @@ int init_gemm_f16s_attrs() {
 #define SET_ATTR(fn, bytes)                                                                              \
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)); \
     if (e != hipSuccess) return fail(GLF_ERR_LAUNCH, "hipFuncSetAttribute(" #fn "): %s", hipGetErrorString(e));
-#define SET_ROWS(G, NP_, PA_, PB_) SET_ATTR((gemm_rows_f16s8_kernel<G, NP_, false, PB_, PA_>), SMEM_ROWS_H8)
+#define SET_ROWS(G, NP_, PA_, PB_) SET_ATTR((gemm_rows_f16s8_kernel<G, NP_, PB_, PA_>), SMEM_ROWS_H8)
 #define SET_TN(G, NP_, PA_, PB_) SET_ATTR((gemm_tn_f16s_kernel<G, NP_, PA_, PB_>), SMEM_TN_H) SET_ATTR((gemm_tn_f16s_kernel<G, NP_, PA_, PB_, true>), SMEM_TN_H) \
                                  SET_ATTR((gemm_tn_f16s8_kernel<G, NP_, PA_, PB_>), SMEM_TN_H8)
-#define SET_ALL(G, NP_) SET_ATTR((gemm_rows_f16s8_kernel<G, 3, true, true, true>), SMEM_ROWS_H8) SET_ROWS(G, NP_, false, false) SET_ROWS(G, NP_, true, false) SET_ROWS(G, NP_, false, true) SET_ROWS(G, NP_, true, true) \
+#define SET_ALL(G, NP_) SET_ROWS(G, NP_, false, false) SET_ROWS(G, NP_, true, false) SET_ROWS(G, NP_, false, true) SET_ROWS(G, NP_, true, true) \
                         SET_TN(G, NP_, false, false) SET_TN(G, NP_, true, false) SET_TN(G, NP_, false, true) SET_TN(G, NP_, true, true)
     SET_ALL(false, 3) SET_ALL(true, 3) SET_ALL(false, 1) SET_ALL(true, 1)
 #undef SET_ALL
@@ -1594,18 +1432,10 @@ int launch_rows_f16s(const GemmArgs& a0, dim3 grid, bool gather, int nprod, hipS
 #ifdef GLF_STAMPS
     a.partial = reinterpret_cast<float*>(stamps_buffer());
 #endif
-#define GLF_LAUNCH_ROWS(G, NP_, PA_, PB_) hipLaunchKernelGGL((gemm_rows_f16s8_kernel<G, NP_, false, PB_, PA_>), g2, dim3(NT8), SMEM_ROWS_H8, s, a)
+#define GLF_LAUNCH_ROWS(G, NP_, PA_, PB_) hipLaunchKernelGGL((gemm_rows_f16s8_kernel<G, NP_, PB_, PA_>), g2, dim3(NT8), SMEM_ROWS_H8, s, a)
 #define GLF_ROWS_P(G, NP_)                                                                     \
     { if (pa && pb) GLF_LAUNCH_ROWS(G, NP_, true, true); else if (pa) GLF_LAUNCH_ROWS(G, NP_, true, false); \
       else if (pb) GLF_LAUNCH_ROWS(G, NP_, false, true); else GLF_LAUNCH_ROWS(G, NP_, false, false); }
-    // both operands pre-split, three products: the 16x16x32 MFMA form of the loop (same cycles per FLOP as 32x32x16; the chip
-    // holds a higher clock on it -- MI355X_MICROARCH.md, DVFS give-back item 7)
-    static const bool m16p = [] { const char* e = getenv("GLF_MFMA16_PRESPLIT"); return e ? e[0] != '0' : false; }();
-    if (nprod == 3 && pa && pb && m16p) {
-        if (gather) hipLaunchKernelGGL((gemm_rows_f16s8_kernel<true, 3, true, true, true>), g2, dim3(NT8), SMEM_ROWS_H8, s, a);
-        else hipLaunchKernelGGL((gemm_rows_f16s8_kernel<false, 3, true, true, true>), g2, dim3(NT8), SMEM_ROWS_H8, s, a);
-        return check_launch("gemm_nt(f16x3, 16x16x32, pre-split)");
-    }
     if (nprod == 3) { if (gather) GLF_ROWS_P(true, 3) else GLF_ROWS_P(false, 3) }
     else { if (gather) GLF_ROWS_P(true, 1) else GLF_ROWS_P(false, 1) }
 #undef GLF_ROWS_P
@@ -1621,8 +1451,7 @@ int launch_tn_f16s(const GemmArgs& a0, dim3 grid, bool gather, int nprod, hipStr
 #endif
     const bool pa = a.a_presplit != 0, pb = a.b_presplit != 0;
     // 64 x 64 tiles when one extent is <= 64 and the other small too (layer 1: 64 x 64, 256 x 64, 64 x 256): no zero-page columns
-    static const bool small_on = [] { const char* e = getenv("GLF_TN_SMALL"); return e ? e[0] != '0' : true; }();
-    const bool small = small_on && (a.M <= 64 || a.N <= 64) && a.M <= 256 && a.N <= 256;
+    const bool small = (a.M <= 64 || a.N <= 64) && a.M <= 256 && a.N <= 256;
     const bool wide = !small && a.M > BM;   // 256-wide tiles: re-derive the grid
     dim3 g2 = grid;
     if (wide) {

@@ -385,7 +385,7 @@ __global__ __launch_bounds__(NT4, 2) void gemm_rows_f16s4_kernel(const GemmArgs 
                 ey = rem / r_w; ex = rem - ey * r_w;
             }
             if (p_accumulate && !p_rect && !p_colstats) {
-                // C += result (a dgrad landing on the shortcut's gradient): all 16 old values are requested before the first is
+                // C += result (the accumulate epilogue of glf_gemm): all 16 old values are requested before the first is
                 // needed -- fetched inside the store loop, each of its 4-deep batches waited out a full memory round trip
                 float4 prev[16];
                 const int rowb = tm * BM4 + wm + r0;
@@ -518,9 +518,8 @@ bool use_f16s4(const GemmArgs& a) {
     static const int mode = [] { const char* e = getenv("GLF_F16S4"); return e ? atoi(e) : 1; }();
     if (mode == 0) return false;
     if (mode == 2) return true;
-    static const int kmax = [] { const char* e = getenv("GLF_F16S4_KMAX"); return e ? atoi(e) : 256; }();
     const long long kred = (long long)a.K * __builtin_popcount(a.tap_mask);
-    return kred <= kmax;
+    return kred <= 256;
 }
 
 int launch_rows_f16s4(const GemmArgs& a0, dim3 grid, bool gather, int nprod, hipStream_t s) {

@@ -74,8 +74,6 @@ class StepGraph:
             reducer.deferred = True
         prev_distinct, ops.SECTIONS_DISTINCT = ops.SECTIONS_DISTINCT, True
         self._prev_distinct = prev_distinct
-        # a conv's weight gradient on a side stream is a fork nested inside a section: not capturable on ROCm 7.2 (see above)
-        prev_wgrad, ops.WGRAD_STREAM = ops.WGRAD_STREAM, False
 
         self.wtable = None                         # frozen job table of THIS model's weight images (made after the warm-up)
 
@@ -109,13 +107,11 @@ class StepGraph:
                     self.out = body()
         except BaseException:
             # a failed warm-up / capture must not leave the process in capture configuration: the reducer back to
-            # immediate mode, the section / weight-gradient stream policies back to what they were
+            # immediate mode, the section stream policy back to what it was
             if reducer is not None:
                 reducer.deferred = False
             ops.SECTIONS_DISTINCT = prev_distinct
             raise
-        finally:
-            ops.WGRAD_STREAM = prev_wgrad
         torch.cuda.current_stream(dev).wait_stream(self.stream)
         self.grads = {p: p.grad for p in self.params if p.grad is not None}      # static tensors the replays write
 

@@ -25,7 +25,7 @@ from torch.autograd.function import once_differentiable
 
 from ._lib import AttnParams, check, lib
 from .ops import (_chk, _contig, _p, _stream, _tn_split, _ws, _wimage, _registry, WJ_COPY, stats_slot, amax_of, amax_slot, colsum, gemm, set_amax, split_mode,
-                  tn_needs_zero, transpose2d, weight_T, weight_packed, nt_presplit_ok, tn_presplit_ok, act_packed, packed_hit, pick, zeros, _ones4)
+                  transpose2d, weight_T, weight_packed, nt_presplit_ok, tn_presplit_ok, act_packed, packed_hit, pick, zeros, _ones4)
 
 
 FUSED_SOFTMAX = os.environ.get("GLF_FUSED_SOFTMAX", "1") != "0"
@@ -81,7 +81,6 @@ def _scores(th, ph, f0, g, L, lp, ci, c3, am_q, S):
 def _transposed(src, f0, g, L, lp, ci, c3, out):
     """out[0:g] = the [ci, lp] transposes of the [L, ci] column slices src (row stride c3) of frames f0 .. f0 + g, zero beyond L."""
     check(lib.glf_transpose2d_strided(_p(src[f0 * L:]), c3, L * c3, _p(out), lp, ci * lp, L, ci, lp, g, _stream()), "transpose2d_strided")
-PACKED_TPAVI = os.environ.get("GLF_PACKED_TPAVI", "1") != "0"      # W_z's output gradient handed over as a packed image (train mode)
 
 
 def fused_softmax_ok(ci: int) -> bool:
@@ -284,9 +283,9 @@ class TpaviFn(Function):
         am_dwz_slot = amax_slot(dev)
         dbn_g = torch.empty(c, **f32)
         dbn_b = torch.empty(c, **f32)
-        dwz_pk = bool(training and split and PACKED_TPAVI and am_dwz_slot is not None and nt_presplit_ok(c, c, c) and tn_presplit_ok(c, ci, c, ci))
-        from .ops import FUSED_BN_BWD, bnbwd_slot
-        fused = bnbwd_slot(c, dev) if (FUSED_BN_BWD and c <= 4096) else None
+        dwz_pk = bool(training and split and am_dwz_slot is not None and nt_presplit_ok(c, c, c) and tn_presplit_ok(c, ci, c, ci))
+        from .ops import bnbwd_slot
+        fused = bnbwd_slot(c, dev) if c <= 4096 else None
         check(lib.glf_bn_bwd(_p(du), c, _p(wz), c, None, c, _p(mean), _p(invstd), _p(bn_g), None, _p(dwz), c, None, c,
                              _p(dbn_g), _p(dbn_b), rows, c, 0, int(training), None if fused is not None else _p(_ws(rows, c, dev)), _p(am_dwz_slot),
                              int(dwz_pk), None, None, 0, _p(fused), _stream()), "bn_bwd")
@@ -295,7 +294,7 @@ class TpaviFn(Function):
         sp = _tn_split(rows, c, ci, 1)
         if not split_mode():
             sp = max(sp, min((rows + 511) // 512, 65535))          # (as for the projections' weight gradient below)
-        dzW = (zeros if tn_needs_zero(sp) else torch.empty)(c, ci, **f32)
+        dzW = torch.empty(c, ci, **f32)
         am_dwz, am_q = amax_of(dwz), amax_of(qkv)
         ok = tn_presplit_ok(c, ci, c, ci)
         dwz_a, pa = (dwz, True) if dwz_pk else pick(dwz, act_packed(dwz, am_dwz, True) if ok else None, ok)       # shared with the NT contraction below
@@ -400,7 +399,7 @@ class TpaviFn(Function):
             # ONE fp32 chain per slice -- slices of at most 512 rows (16 K-tiles; the second stage adds the slabs in double) keep the
             # strict-precision leg at least as accurate as the split-fp16 one (3e-3 -> 1.5e-3 on the smoke fixture)
             sp = max(sp, min((rows + 511) // 512, 65535))
-        dWcat = (zeros if tn_needs_zero(sp) else torch.empty)(c3, c, **f32)
+        dWcat = torch.empty(c3, c, **f32)
         am_dq = amax_of(dqkv)
         ok = tn_presplit_ok(c3, c, c3, c)
         dq_a, pa = pick(dqkv, act_packed(dqkv, am_dq, True) if ok else None, ok)

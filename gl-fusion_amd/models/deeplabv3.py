@@ -7,7 +7,6 @@ taps that fall into the zero padding for a whole tile are skipped inside the con
 broadcast."""
 from __future__ import annotations
 
-import os
 from typing import List
 
 import torch
@@ -16,8 +15,6 @@ from torch import nn
 from .. import ops
 from .layers import AdaptiveAvgPool2d, BatchNorm2d, Conv2d, Dropout, ReLU, conv_bn_act
 from ._utils import _SimpleSegmentationModel_iekd
-
-_CAT_BUFFER = os.environ.get("GLF_ASPP_CAT", "1") != "0"
 
 __all__ = ["DeepLabV3_iekd", "DeepLabHead", "ASPP", "ASPPConv", "ASPPPooling"]
 
@@ -85,21 +82,18 @@ class ASPP(nn.Module):
         slot = ops.amax_slot(x.device)
         branches, off = [], 0
         for conv, xi, ck in zip(self.convs, xs, widths):
-            if _CAT_BUFFER:
-                with ops.output_into(cat[..., off:off + ck], slot):
-                    branches.append(conv.forward_nhwc(xi))
-            else:
+            with ops.output_into(cat[..., off:off + ck], slot):
                 branches.append(conv.forward_nhwc(xi))
             off += ck
         pbn = self.project[1]
-        if ops.s16() and _CAT_BUFFER and (pbn.training or pbn.running_mean is None):
+        if ops.s16() and (pbn.training or pbn.running_mean is None):
             # 16-bit storage: the projection's BatchNorm statistics come out of its own epilogue
             sums = ops.stats_slot(self.project[0].out_channels, x.device)
             y = ops.conv1x1_cat(self.project[0].weight, branches, colstats=sums)
             return pbn.forward_nhwc(y, relu=True, sums=sums)
         y = ops.conv1x1_cat(self.project[0].weight, branches)
         # (the projection's gradient is consumed by ConvCatFn's dgrad / wgrad only -- and only its single-buffer form reads it packed)
-        pg = _CAT_BUFFER and torch.is_grad_enabled() and ops.takes_packed_grad(self.project[0].weight)
+        pg = torch.is_grad_enabled() and ops.takes_packed_grad(self.project[0].weight)
         return self.project[1].forward_nhwc(y, relu=True, packed_grad=pg)
 
     def forward_nhwc(self, x):

@@ -8,8 +8,6 @@ row-major [N*H*W, C] matrices.
 """
 from __future__ import annotations
 
-import os
-
 import torch
 from torch import nn
 
@@ -80,9 +78,6 @@ class AdaptiveAvgPool2d(nn.AdaptiveAvgPool2d):
         return ops.from_nhwc(ops.global_avgpool(ops.to_nhwc(x)))
 
 
-FUSE_BN_STATS = os.environ.get("GLF_FUSE_BN_STATS", "1") != "0"
-
-
 def conv_bn_act(x, conv: Conv2d, bn: BatchNorm2d, relu: bool, residual=None, consumer: Conv2d = None):
     """conv -> BatchNorm (train or eval) -> (+residual) -> (ReLU) on NHWC tensors.  In train() the batch statistics
     (sum x, sum x^2 per channel) are accumulated by the conv's own epilogue where the kernel supports it, which saves the
@@ -93,7 +88,7 @@ def conv_bn_act(x, conv: Conv2d, bn: BatchNorm2d, relu: bool, residual=None, con
     stem = conv.in_channels == 1 and conv.kernel_size == (7, 7)
     # the conv output's gradient has ONE consumer, this conv's backward: BatchNorm backward may hand it over as a packed image
     pg = (not stem) and conv.bias is None and torch.is_grad_enabled() and ops.takes_packed_grad(conv.weight)
-    if training and FUSE_BN_STATS and not stem:
+    if training and not stem:
         stride, pad, dil = conv._geom()
         if ops.conv_stats_fusable(conv.weight, stride, pad, dil, x.shape[1], x.shape[2], x.dtype):
             sums = ops.stats_slot(conv.out_channels, x.device)

@@ -19,11 +19,6 @@ from .segmentation import deeplabv3_resnet50_iekd
 
 # the two fusion blocks on side streams of their own (GLF_FUSION_STREAMS=0: one after the other on the current stream)
 _FUSION_STREAMS = os.environ.get("GLF_FUSION_STREAMS", "1") != "0"
-# classifier and centerness head of a view on streams of their own (inside the view's section)
-_HEAD_STREAMS = os.environ.get("GLF_HEAD_STREAMS", "0") != "0"
-_HEAD_ORDER = os.environ.get("GLF_HEAD_ORDER", "0") != "0"
-# the global fusion block beside the views' head sections instead of beside the local block
-_EARLY_GLOBAL = os.environ.get("GLF_EARLY_GLOBAL", "0") != "0"
 
 class TPAVIModule(nn.Module):
     """ours.py:770-917.  Built modes: 'dot' (shipped) and 'embedded' (softmax); dimension=3,
@@ -149,58 +144,23 @@ class Global_and_Local(_PerViewNetworks):
         def view_section(v):
             f = self._encode_view(v, x[v])
             fa, fb, fc, fg, *raw = ops.fan_out(f, 5 if self._third_output_is_f4 else 4)   # classifier / centerness / gate / global fusion
-            if _HEAD_STREAMS:            # the two heads of a view are independent chains of ~25 kernels each
-                (cls, again), ctr = ops.parallel_sections([lambda: self.classifier[v].forward_nhwc_shared(fa),
-                                                           lambda: self.centerness[v].forward_nhwc(fb)])
-            elif _HEAD_ORDER and views.index(v) % 2 == 1:
-                # the views' chains are copies of each other and run in lockstep -- contraction phases and streaming phases line
-                # up across the three streams; every other view evaluates its two (independent) heads in the opposite order
-                ctr = self.centerness[v].forward_nhwc(fb)
-                cls, again = self.classifier[v].forward_nhwc_shared(fa)
-            else:
-                cls, again = self.classifier[v].forward_nhwc_shared(fa)     # `again`: the mask_bb call below, same input
-                ctr = self.centerness[v].forward_nhwc(fb)
+            cls, again = self.classifier[v].forward_nhwc_shared(fa)     # `again`: the mask_bb call below, same input
+            ctr = self.centerness[v].forward_nhwc(fb)
             gated = ops.local_gate(cls, ctr, fc, self.center_aware_weight)
             if self._global_gets_background:                            # Foreground_and_Background (ours.py:2966)
                 g1, g2 = ops.fan_out(gated, 2)
                 fg, gated = ops.axpby(fg, g1, 1.0, -1.0), g2            # f4 * (1 - a) = f4 - f4 * a
             return again, fg, gated, (raw[0] if raw else None)
 
-        if _EARLY_GLOBAL and not self._global_gets_background:
-            # The global fusion block needs only the encoders' outputs: it runs NEXT TO the views' head + gate sections (four
-            # independent chains) instead of after them next to the local block.  The fusion blocks are the part of the step
-            # with the least to overlap with -- two chains of large contractions whose streaming kernels (stack / split /
-            # statistics / LayerNorm tail) ran with nothing but their twin beside them (profiles/r03_timeline_step.txt).
-            k = 5 if self._third_output_is_f4 else 4
-            enc = ops.parallel_sections([lambda v=v: ops.fan_out(self._encode_view(v, x[v]), k) for v in views])
-
-            def heads_gate(v, parts):
-                ops.use_here(*parts)
-                fa, fb, fc = parts[0], parts[1], parts[2]
-                cls, again = self.classifier[v].forward_nhwc_shared(fa)
-                ctr = self.centerness[v].forward_nhwc(fb)
-                return again, ops.local_gate(cls, ctr, fc, self.center_aware_weight)
-
-            def global_block():
-                fg = [e[3] for e in enc]
-                ops.use_here(*fg)
-                return self._attend(self.global_attn, ops.stack_views(fg))
-            res = ops.parallel_sections([lambda v=v, e=e: heads_gate(v, e) for v, e in zip(views, enc)] + [global_block])
-            g_out = res[-1]
-            cls_again = {v: r[0] for v, r in zip(views, res)}
-            f4_local = {v: r[1] for v, r in zip(views, res)}
-            secs = [(None, None, None, (e[4] if k == 5 else None)) for e in enc]
-            l_out = self._attend(self.local_attn, ops.stack_views([f4_local[v] for v in views]))
-        else:
-            secs = ops.parallel_sections([lambda v=v: view_section(v) for v in views])
-            cls_again = {v: s[0] for v, s in zip(views, secs)}
-            f4_glob = {v: s[1] for v, s in zip(views, secs)}
-            f4_local = {v: s[2] for v, s in zip(views, secs)}
-            # global / local cross-view fusion (ours.py:1819-1830): two independent blocks
-            fusion_jobs = [
-                lambda: self._attend(self.global_attn, ops.stack_views([f4_glob[v] for v in views])),    # [N,V,h,w,C]
-                lambda: self._attend(self.local_attn, ops.stack_views([f4_local[v] for v in views]))]
-            g_out, l_out = ops.parallel_sections(fusion_jobs) if _FUSION_STREAMS else [j() for j in fusion_jobs]
+        secs = ops.parallel_sections([lambda v=v: view_section(v) for v in views])
+        cls_again = {v: s[0] for v, s in zip(views, secs)}
+        f4_glob = {v: s[1] for v, s in zip(views, secs)}
+        f4_local = {v: s[2] for v, s in zip(views, secs)}
+        # global / local cross-view fusion (ours.py:1819-1830): two independent blocks
+        fusion_jobs = [
+            lambda: self._attend(self.global_attn, ops.stack_views([f4_glob[v] for v in views])),    # [N,V,h,w,C]
+            lambda: self._attend(self.local_attn, ops.stack_views([f4_local[v] for v in views]))]
+        g_out, l_out = ops.parallel_sections(fusion_jobs) if _FUSION_STREAMS else [j() for j in fusion_jobs]
         fused = self._fuse(g_out, l_out)                                                        # ours.py:1833-1834
 
         def head_section(i, v):       # same order per view as the reference: fused mask first, backbone mask second

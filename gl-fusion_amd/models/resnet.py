@@ -35,8 +35,6 @@ class Bottleneck(nn.Module):
         # x is the previous block's output and nobody else reads it (sole_reader, set by Stage), in no pass of their own at all:
         # that block's last BatchNorm backward adds them while reading
         x, xs = ops.fan_out(x, 2, lazy=sole_reader)
-        if self.downsample is None and x is not xs:
-            ops.join_gradients(x, xs)     # identity shortcut: conv1's dgrad accumulates onto the shortcut's gradient
         idn = xs if self.downsample is None else conv_bn_act(xs, self.downsample[0], self.downsample[1], relu=False)
         out = conv_bn_act(x, self.conv1, self.bn1, relu=True, consumer=self.conv2)      # inner activations: one reader each
         out = conv_bn_act(out, self.conv2, self.bn2, relu=True, consumer=self.conv3)

@@ -139,13 +139,6 @@ def act_dtype() -> torch.dtype:
 def _is16(t) -> bool:
     return isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16
 
-TWO_STAGE_SPLITK = os.environ.get("GLF_TWO_STAGE", "1") != "0"
-
-
-def tn_needs_zero(split: int) -> bool:
-    """True when a split-K TN call sums its slices with float atomics (C must then be zero-filled by the caller)."""
-    return split > 1 and not TWO_STAGE_SPLITK
-
 
 # bench.py sets this to a list to time every contraction launch with HIP events on the launch stream
 PROFILER = None
@@ -182,7 +175,7 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
     p.precision = _PREC[0] + 1
     p.a_presplit, p.b_presplit = int(a_packed), int(b_packed)
     ws = None
-    if mode == "tn" and split > 1 and TWO_STAGE_SPLITK:
+    if mode == "tn" and split > 1:
         # two-stage reduction: the slices store partial sums, a second kernel adds them in a fixed order -- no atomics, no
         # zero-filled C, bitwise reproducible gradients
         nbytes = int(lib.glf_gemm_tn_workspace_bytes(C.byref(p)))
@@ -485,9 +478,6 @@ def bnbwd_slot(c: int, dev) -> torch.Tensor:
     return stats_slot((3 * c + 1) // 2, dev).view(-1)
 
 
-FUSED_BN_BWD = os.environ.get("GLF_FUSED_BN_BWD", "1") != "0"      # BatchNorm backward in two launches (atomics) instead of three
-
-
 _colmax_pool: dict = {}
 
 
@@ -529,21 +519,17 @@ def set_amax(t: torch.Tensor, amax: Optional[torch.Tensor]) -> None:
         t._glf_amax = (t._version, t.data_ptr(), amax)
 
 
-_TN_TARGET = int(os.environ.get("GLF_TN_TARGET", "0"))      # 0: per precision (below)
-_TN_ROUND = os.environ.get("GLF_TN_ROUND", "1") != "0"
-
-
 def _tn_split(rows: int, m: int, n: int, ntaps: int, batch: int = 1) -> int:
     """Reduction slices for the TN (wgrad) kernel: fill ~4 waves of 512 resident workgroups,
     keep >= 16 K-tiles (512 rows) per slice."""
     tiles = ((m + 127) // 128) * ((n + 127) // 128) * max(ntaps, 1) * batch
     # workgroups to aim for: 2048 128x128 tiles on the fp32 / bf16x6 kernels (two per CU); the f16x3 kernel has 256-wide
     # tiles, one workgroup per CU, and shares the chip with other streams: 1024 measured best (293.5 vs 299.2 ms / step)
-    target = _TN_TARGET or (1024 if _PREC[0] >= 2 else 2048)
+    target = 1024 if _PREC[0] >= 2 else 2048
     want = max(1, (target + tiles - 1) // tiles)
     cap = max(1, rows // 512)
     hi = 65535 // max(batch, 1)
-    if _TN_ROUND and _PREC[0] >= 2:
+    if _PREC[0] >= 2:
         # among the slice counts around the target, the one whose workgroups (256-wide tiles, one per CU) fill whole
         # rounds of the 256 CUs best
         wg = ((m + 255) // 256) * ((n + 127) // 128) * max(ntaps, 1) * batch
@@ -631,10 +617,7 @@ def colsum(dy2d: torch.Tensor, rows: int, c: int) -> torch.Tensor:
         # tiny channel counts (the 5- and 1-channel heads): reduce with the TN contraction against a
         # broadcast 1.0 (row stride 0)
         one = _ones4(dy2d.device)
-        sp = _tn_split(rows, c, 1, 1)
-        if tn_needs_zero(sp):
-            zero_(db)
-        gemm("tn", dy2d, one, db, M=c, N=1, K=rows, lda=c, ldb=0, ldc=1, split=sp)
+        gemm("tn", dy2d, one, db, M=c, N=1, K=rows, lda=c, ldb=0, ldc=1, split=_tn_split(rows, c, 1, 1))
     return db
 
 
@@ -658,8 +641,6 @@ PRESPLIT = os.environ.get("GLF_PRESPLIT", "1") != "0"
 # weight-gradient kernel ~15 % of a time proportional to rows x K x (output columns x taps).  Break-even measured near
 # columns x taps = 1000.  (Weights are always pre-split: once per update, cached.)
 PRESPLIT_MIN_COLS = int(os.environ.get("GLF_PRESPLIT_MIN_COLS", "1024"))
-WGRAD_STREAM = os.environ.get("GLF_WGRAD_STREAM", "0") != "0"      # a conv's weight gradient on a side stream of its dgrad
-_wgrad_streams = {}
 
 
 def presplit_ok(t: torch.Tensor, amax: Optional[torch.Tensor]) -> bool:
@@ -879,7 +860,7 @@ def region_mode(taps: int, kh: int, stride: int, pad: int, dil: int, h: int, w: 
     outputs, 392 workgroups) is faster as per-tap rectangles -- the regions' blocks are fewer and of uneven length
     (4 / 6 / 9 taps) -- and for dilations 1-4 the 5-18 % of padding work saved is less than the extra partial tiles
     and the per-element pixel arithmetic of the epilogue cost."""
-    return (os.environ.get("GLF_REGION", "1") != "0" and _PREC[0] >= 2 and taps == 9 and kh == 3 and stride == 1 and pad == dil and h == ho and w == wo
+    return (_PREC[0] >= 2 and taps == 9 and kh == 3 and stride == 1 and pad == dil and h == ho and w == wo
             and k % 32 == 0 and frac < RECT_THRESHOLD["region"])
 
 
@@ -942,7 +923,6 @@ class Conv2dFn(Function):
                  amax_a=am_x, amax_b=am_w, colstats=colstats, colmax=getattr(colstats, "_glf_colmax", None), a_packed=pa, b_packed=pb)
         ctx.save_for_backward(x, wt)
         ctx.x_packed = (xa, am_x) if (pa and (x_pk or packed_hit(x, am_x) is not None)) else None      # retained: the weight gradient reads the same image
-        ctx.join = getattr(x, "_glf_join", None) if plain else None
         ctx.weight_ref = weight            # for the cached [tap][Cin][Cout] layout of the split-bf16 dgrad
         ctx.cfg = (n, h, w, cin, cout, kh, kw, ho, wo, stride, pad, dil, plain, bias is not None, tuple(weight.shape))
         return y
@@ -961,48 +941,30 @@ class Conv2dFn(Function):
         if dy_pk and (has_bias or am_dy is None or not (split_mode() and cout % 32 == 0)):
             raise RuntimeError("glfusion_amd: a packed-only gradient reached a convolution that cannot consume it")
         def dgrad():
-            dx = None
-            if True:
-                mask = 1 if plain else tap_mask(2, h, w, ho, wo, kh, kw, stride, pad, dil)
-                if mask == 0:
-                    dx = zeros(x.shape, device=x.device)
-                else:
-                    frac = 1.0 if plain or stride != 1 else rect_fraction(2, h, w, ho, wo, kh, kw, pad, dil, mask)
-                    if not plain and bin(mask).count("1") > 1 and region_mode(taps, kh, stride, pad, dil, ho, wo, h, w, cout, frac):
-                        rect = 2
-                    else:
-                        rect = int(not plain and taps > 1 and stride == 1 and bin(mask).count("1") > 1 and frac < _rect_thr("dgrad"))
-                    parked = None
-                    if ctx.join is not None:              # the shortcut's gradient is waiting: add this dgrad onto it in the epilogue
-                        parked, ctx.join.parked = ctx.join.parked, None
-                        if parked is None:
-                            raise RuntimeError("glfusion_amd: gradient join reached before the shortcut's gradient was produced")
-                    acc = parked is not None
-                    if acc:
-                        dx = parked
-                    else:
-                        dx = zeros(x.shape, device=x.device) if rect == 1 else torch.empty_like(x)
-                    if split_mode() and cout % 32 == 0:
-                        # dgrad as NT on the split-bf16 kernels: B_tap[n = ci][k = co]
-                        am_dx = amax_slot(dx.device) if acc else None
-                        wT = tap_major_T(ctx.weight_ref)
-                        ok = nt_presplit_ok(cout, cout, cout)
-                        ok_dy = ok and cin * bin(mask).count("1") >= PRESPLIT_MIN_COLS
-                        da, pa = (dy, True) if dy_pk else pick(dy, act_packed(dy, am_dy, True) if ok_dy else None, ok_dy)
-                        wb, pb = pick(wT, weight_packed(wT, ctx.weight_ref, "wT", am_w) if ok else None, ok)
-                        gemm("nt", da, wb, dx, M=n * h * w, N=cin, K=cout, lda=cout, ldb=cout, ldc=cin,
-                             taps=taps, mask=mask, tap_stride_b=cout * cin, gather=0 if plain else 2,
-                             geo=None if plain else (n, ho, wo, h, w, kh, kw, stride, pad, dil), rect=rect,
-                             amax_a=am_dy, amax_b=am_w, accumulate=acc, amax_c=am_dx, a_packed=pa, b_packed=pb)
-                        if acc:
-                            dx._glf_amax = None
-                            set_amax(dx, am_dx)            # the maximum of the SUM, from the accumulating epilogue
-                    else:
-                        gemm("nn", dy, wt, dx, M=n * h * w, N=cin, K=cout, lda=cout, ldb=cin, ldc=cin, taps=taps, mask=mask,
-                             tap_stride_b=cout * cin, gather=0 if plain else 2,
-                             geo=None if plain else (n, ho, wo, h, w, kh, kw, stride, pad, dil), rect=rect, accumulate=acc)
-                        if acc:
-                            dx._glf_amax = None
+            mask = 1 if plain else tap_mask(2, h, w, ho, wo, kh, kw, stride, pad, dil)
+            if mask == 0:
+                return zeros(x.shape, device=x.device)
+            frac = 1.0 if plain or stride != 1 else rect_fraction(2, h, w, ho, wo, kh, kw, pad, dil, mask)
+            if not plain and bin(mask).count("1") > 1 and region_mode(taps, kh, stride, pad, dil, ho, wo, h, w, cout, frac):
+                rect = 2
+            else:
+                rect = int(not plain and taps > 1 and stride == 1 and bin(mask).count("1") > 1 and frac < _rect_thr("dgrad"))
+            dx = zeros(x.shape, device=x.device) if rect == 1 else torch.empty_like(x)
+            if split_mode() and cout % 32 == 0:
+                # dgrad as NT on the split-bf16 kernels: B_tap[n = ci][k = co]
+                wT = tap_major_T(ctx.weight_ref)
+                ok = nt_presplit_ok(cout, cout, cout)
+                ok_dy = ok and cin * bin(mask).count("1") >= PRESPLIT_MIN_COLS
+                da, pa = (dy, True) if dy_pk else pick(dy, act_packed(dy, am_dy, True) if ok_dy else None, ok_dy)
+                wb, pb = pick(wT, weight_packed(wT, ctx.weight_ref, "wT", am_w) if ok else None, ok)
+                gemm("nt", da, wb, dx, M=n * h * w, N=cin, K=cout, lda=cout, ldb=cout, ldc=cin,
+                     taps=taps, mask=mask, tap_stride_b=cout * cin, gather=0 if plain else 2,
+                     geo=None if plain else (n, ho, wo, h, w, kh, kw, stride, pad, dil), rect=rect,
+                     amax_a=am_dy, amax_b=am_w, a_packed=pa, b_packed=pb)
+            else:
+                gemm("nn", dy, wt, dx, M=n * h * w, N=cin, K=cout, lda=cout, ldb=cin, ldc=cin, taps=taps, mask=mask,
+                     tap_stride_b=cout * cin, gather=0 if plain else 2,
+                     geo=None if plain else (n, ho, wo, h, w, kh, kw, stride, pad, dil), rect=rect)
             return dx
 
         def wgrad():
@@ -1015,10 +977,10 @@ class Conv2dFn(Function):
                 frac = rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) if rect else 1.0
                 split = wgrad_split(rows_o, frac, cout, cin, ntap, rect)
                 full = mask == (1 << taps) - 1
-                if taps == 1 and full and not tn_needs_zero(split):
+                if taps == 1 and full:
                     dwt = grad_out(ctx.weight_ref, (1, cout, cin), x.device)       # a 1x1 weight's gradient is the contraction's output
                 else:
-                    dwt = (zeros if (tn_needs_zero(split) or not full) else torch.empty)(taps, cout, cin, dtype=torch.float32, device=x.device)
+                    dwt = (torch.empty if full else zeros)(taps, cout, cin, dtype=torch.float32, device=x.device)
                 ok = tn_presplit_ok(cout, cin, cout, cin)
                 am_x = ctx.x_packed[1] if ctx.x_packed is not None else amax_of(x)
                 # dy: the image dgrad made (or one worth making for this kernel alone); x: the image the forward made, if any
@@ -1036,27 +998,10 @@ class Conv2dFn(Function):
                     check(lib.glf_tap_major_to_oihw(_p(dwt), _p(dw), cout, cin, taps, _stream()), "tap_major_to_oihw")
             return dw
 
-        if WGRAD_STREAM and STREAMS and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
-            # dgrad and wgrad of one conv are independent and read the same dy: the weight gradient goes to a side stream of
-            # the stream this node runs on (its workgroups fill the partial last round of the dgrad kernel and vice versa)
-            if not dy_pk and presplit_ok(dy, am_dy) and (cin * taps >= PRESPLIT_MIN_COLS):
-                act_packed(dy, am_dy, True)                  # the shared image is made before the fork, on this stream
-            cur = torch.cuda.current_stream()
-            side = _wgrad_streams.get(cur.cuda_stream)
-            if side is None:
-                side = _wgrad_streams[cur.cuda_stream] = torch.cuda.Stream(device=dy.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                dw = wgrad()
+        if ctx.needs_input_grad[0]:
             dx = dgrad()
-            cur.wait_stream(side)
-            if dw is not None:
-                dw.record_stream(cur)
-        else:
-            if ctx.needs_input_grad[0]:
-                dx = dgrad()
-            if ctx.needs_input_grad[1]:
-                dw = wgrad()
+        if ctx.needs_input_grad[1]:
+            dw = wgrad()
         if has_bias and ctx.needs_input_grad[2]:
             db = colsum(dy, rows_o, cout)
         return dx, dw, db, None, None, None, None
@@ -1147,7 +1092,7 @@ class ConvCatFn(Function):
         split = _tn_split(rows, cout, xs[0].shape[-1], 1)
         dw = None
         if ctx.needs_input_grad[0]:
-            dw = (zeros if tn_needs_zero(split) else torch.empty)(cout, ctot, dtype=torch.float32, device=dy.device)
+            dw = torch.empty(cout, ctot, dtype=torch.float32, device=dy.device)
         db = colsum(dy, rows, cout) if (ctx.has_bias and ctx.needs_input_grad[1]) else None
         grads = []
         off = 0
@@ -1179,8 +1124,6 @@ class ConvCatFn(Function):
                 grads = [None] * len(xs)
             if dw is not None:
                 split = _tn_split(rows, cout, ctot, 1)
-                if tn_needs_zero(split):
-                    zero_(dw)
                 ok = tn_presplit_ok(cout, ctot, cout, ctot)
                 da, pa = (dy, True) if dy_pk else pick(dy, act_packed(dy, am_dy, True) if ok else None, ok)
                 gemm("tn", da, t0, dw, M=cout, N=ctot, K=rows, lda=cout, ldb=ctot, ldc=ctot, split=split,
@@ -1325,8 +1268,6 @@ def _rows_view(t: torch.Tensor):
 # BatchNorm (+ residual, + ReLU)
 # ----------------------------------------------------------------------------------------
 _last_bn = [None]          # (mean, invstd, rows) of the most recent BatchNormActFn.forward (read by BN_TAP)
-FUSE_BN_FINALIZE = os.environ.get("GLF_FUSE_BN_FINALIZE", "1") != "0"     # statistics finished inside the apply kernel
-RELU_MASK_BYTES = os.environ.get("GLF_RELU_MASK_BYTES", "1") != "0"       # BN(+residual)+ReLU keeps sign bytes, not y, for backward
 
 
 class BatchNormActFn(Function):
@@ -1340,7 +1281,7 @@ class BatchNormActFn(Function):
         dev = x.device
         mean = torch.empty(c, dtype=torch.float32, device=dev)
         invstd = torch.empty(c, dtype=torch.float32, device=dev)
-        fused_stats = training and sums is not None and c <= 4096 and FUSE_BN_FINALIZE
+        fused_stats = training and sums is not None and c <= 4096
         if fused_stats:
             pass                                 # finished inside the apply kernel below (one launch)
         elif training and sums is not None:      # (sum x, sum x^2) came out of the producing contraction's epilogue
@@ -1366,7 +1307,7 @@ class BatchNormActFn(Function):
         # relu + residual: the backward needs the sign of the forward output -- kept as one byte per four channels instead of y
         # (grad mode is always OFF inside Function.forward: before round 4 this read torch.is_grad_enabled() and the sign bytes were
         # never produced -- the backward fell back to re-reading y; what says that a backward may follow is needs_input_grad)
-        need_mask = relu and residual is not None and any(ctx.needs_input_grad[:4]) and RELU_MASK_BYTES
+        need_mask = relu and residual is not None and any(ctx.needs_input_grad[:4])
         mask = torch.empty(rows * (c // 4), dtype=torch.uint8, device=dev) if need_mask else None
         if fused_stats:
             check(lib.glf_bn_apply_from_sums(_p(x), c, _p(residual), c, _p(y), ldy, _p(sums), rows, c, eps, momentum, _p(gamma), _p(beta),
@@ -1384,7 +1325,6 @@ class BatchNormActFn(Function):
         ctx.cfg = (rows, c, relu, training, residual is not None, ldy)
         ctx.packed_grad = bool(packed_grad) and _PREC[0] >= 2
         ctx.param_refs = (gamma, beta)
-        ctx.join = getattr(residual, "_glf_join", None) if residual is not None else None
         _last_bn[0] = (mean, invstd, rows)
         return y
 
@@ -1411,15 +1351,13 @@ class BatchNormActFn(Function):
         # followed by a split pass
         packed = ctx.packed_grad and _PREC[0] >= 2 and am is not None and PACKED_GRADS
         mask = y if ctx.has_mask else None
-        fused = bnbwd_slot(c, dev) if (FUSED_BN_BWD and c <= 4096) else None
+        fused = bnbwd_slot(c, dev) if c <= 4096 else None      # two launches (atomics) instead of three
         check(lib.glf_bn_bwd(_p(dy), lddy, _p(x), c, None if ctx.has_mask else _p(y), ldy, _p(mean), _p(invstd), _p(gamma), _p(beta),
                              _p(dx), c, _p(dres), c, _p(dgamma), _p(dbeta), rows, c, int(relu), int(training),
                              None if fused is not None else _p(_ws(rows, c, dev)), _p(am), int(packed), _p(mask), _p(dy2), lddy2, _p(fused), _stream()), "bn_bwd")
         set_amax(dx, am)
         if packed:
             dx._glf_packed_only = True
-        if ctx.join is not None and dres is not None:
-            ctx.join.parked, dres = dres, None       # handed to the block's first conv, whose dgrad accumulates onto it
         return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None, None, None
 
 
@@ -1712,32 +1650,6 @@ def fan_out(x: torch.Tensor, k: int, lazy: bool = False):
     return FanOutFn.apply(x, k, lazy)
 
 
-class GradJoin:
-    """Meeting point of the two gradients of a residual block's input (identity shortcut + first conv).  The shortcut's
-    gradient -- produced by the BatchNorm(+residual) backward, early in the block's backward -- is parked here instead of
-    being returned; the first conv's dgrad, the last kernel of the block's backward, ACCUMULATES into it in its epilogue
-    (C += result) and returns the total.  The separate two-input add (two reads + one write of the block input per block)
-    is gone.  Attached to the two aliases by `join_gradients`."""
-    __slots__ = ("parked",)
-
-    def __init__(self):
-        self.parked = None
-
-
-# Measured (C2 step, A/B in one run): 298.9 ms with the join against 291.3 ms without -- the accumulating epilogue sits on
-# the backward's critical chain (the block's last dgrad) while the add it replaces overlaps with other streams.  Off.
-GRAD_JOIN = os.environ.get("GLF_GRAD_JOIN", "0") != "0"
-
-
-def join_gradients(conv_input: torch.Tensor, shortcut: torch.Tensor) -> None:
-    """Mark two fan_out aliases of one tensor: `shortcut` will be used as the residual of a BatchNorm, `conv_input` as the
-    input of a 1x1 stride-1 convolution whose dgrad then absorbs the shortcut's gradient (see GradJoin)."""
-    if GRAD_JOIN and torch.is_grad_enabled() and conv_input.requires_grad:
-        j = GradJoin()
-        conv_input._glf_join = j
-        shortcut._glf_join = j
-
-
 # ----------------------------------------------------------------------------------------
 # independent sections on side streams
 # ----------------------------------------------------------------------------------------
@@ -1766,9 +1678,9 @@ def _walk_tensors(obj):
             yield from _walk_tensors(v)
 
 
-# GLF_SECTIONS_DISTINCT=1: the stream counter restarts only at begin_step() (the models call it at the top of forward), so
-# successive top-level parallel_sections calls of one forward get DIFFERENT side streams instead of re-using 0, 1, 2 ...
-SECTIONS_DISTINCT = os.environ.get("GLF_SECTIONS_DISTINCT", "0") != "0"
+# True (engine.StepGraph sets it): the stream counter restarts only at begin_step() (the models call it at the top of forward),
+# so successive top-level parallel_sections calls of one forward get DIFFERENT side streams instead of re-using 0, 1, 2 ...
+SECTIONS_DISTINCT = False
 
 
 _step_counters = {}
@@ -1805,17 +1717,6 @@ def reset_capture_pools() -> None:
     _amax_pool.clear()
     _stats_pool.clear()
     _colmax_pool.clear()
-
-
-def use_here(*tensors) -> None:
-    """Tell the caching allocator that these tensors (allocated on another stream) are read on the CURRENT stream: their
-    memory must not be handed out again before this stream's work on them is done."""
-    if not STREAMS:
-        return
-    cur = torch.cuda.current_stream()
-    for t in tensors:
-        if isinstance(t, torch.Tensor) and t.is_cuda:
-            t.record_stream(cur)
 
 
 def parallel_sections(fns):

@@ -26,10 +26,6 @@ _p, _stream, _contig = _o._p, _o._stream, _o._contig
 DT_F32, DT_BF16 = 0, 1
 # block sequences through their single-call C entry points (glf_s16_tpavi_fwd / _bwd); 0 = composed from Python, the same launches
 BLOCK_CALLS = os.environ.get("GLF_BLOCK_CALLS", "1") != "0"
-# gathered weight gradients whose taps fall mostly into the padding reduce over per-tap rectangles (glf_s16_gemm_tn rect = 1); 0 = banded K-tile skipping only
-RECT_WGRAD = os.environ.get("GLF_S16_RECT_WGRAD", "1") != "0"
-# a conv's weight gradient on a side stream of its dgrad (experiment switch; joined before the node returns)
-WGRAD_STREAM16 = os.environ.get("GLF_S16_WGRAD_STREAM", "0") != "0"
 
 
 def _chk16(t: torch.Tensor, name: str = "tensor") -> torch.Tensor:
@@ -241,7 +237,7 @@ class Conv2d16Fn(Function):
             # pixels only.  A slice is the same number of rows for every tap (a short rectangle uses fewer slices), so the slice
             # count is the one of the in-range rows scaled back up to the whole map.
             rect = 0
-            if RECT_WGRAD and not plain and stride == 1 and ntap > 1 and rows_o >= 2048:
+            if not plain and stride == 1 and ntap > 1 and rows_o >= 2048:
                 frac = _o.rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask)
                 if frac < 0.8:
                     s_in = tn_split16(max(512, int(rows_o * frac)), cout, cin, ntap)
@@ -260,25 +256,10 @@ class Conv2d16Fn(Function):
             check(lib.glf_tap_major_to_oihw(_p(dwt), _p(dw), cout, cin, taps, _stream()), "tap_major_to_oihw")
             return dw
 
-        if WGRAD_STREAM16 and _o.STREAMS and _o.PROFILER is None and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] \
-                and not torch.cuda.is_current_stream_capturing():
-            # dgrad and wgrad of one conv are independent and read the same dy: the weight gradient goes to a side stream of the
-            # stream this node runs on and is joined before the node returns (ops.Conv2dFn.backward's form)
-            cur = torch.cuda.current_stream()
-            side = _o._wgrad_streams.get(cur.cuda_stream)
-            if side is None:
-                side = _o._wgrad_streams[cur.cuda_stream] = torch.cuda.Stream(device=dy.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                dw = wgrad()
+        if ctx.needs_input_grad[0]:
             dx = dgrad()
-            cur.wait_stream(side)
-            dw.record_stream(cur)
-        else:
-            if ctx.needs_input_grad[0]:
-                dx = dgrad()
-            if ctx.needs_input_grad[1]:
-                dw = wgrad()
+        if ctx.needs_input_grad[1]:
+            dw = wgrad()
         if has_bias and ctx.needs_input_grad[2]:
             db = colsum16(dy, rows_o, cout)
         return dx, dw, db, None, None, None, None
