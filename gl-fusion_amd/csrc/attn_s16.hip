@@ -29,8 +29,11 @@
 //     ds_read_b64_tr_b16 from Z (the reduction index is Z's row).
 // LDS: 3 x 33,280 B ring + two fp32 64 x 68 tiles + the 8 KiB T tile + row statistics = 142,080 B, one workgroup per CU.
 #include "gemm_common.h"
+#include "stream_common.h"
 
 namespace {
+
+using glf::pack2;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4_ __attribute__((ext_vector_type(4)));
@@ -70,12 +73,6 @@ __device__ __forceinline__ void glds16(const u16* src, unsigned char* lds_base) 
 }
 __device__ __forceinline__ void glds4(const float* src, unsigned char* lds_base) {
     __builtin_amdgcn_global_load_lds((glb_ptr_t)src, (lds_ptr_t)lds_base, 4, 0, 0);
-}
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-    const f32x2_ v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_));
 }
 // wait until at most n of this wave's vector-memory operations are outstanding (n wave-uniform, 0..5) and its LDS writes are done
 // (they are read by other waves behind the barrier that follows)

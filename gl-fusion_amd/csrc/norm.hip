@@ -6,8 +6,10 @@
 //   * BatchNorm apply (+residual, +ReLU) and the backward apply are single streaming passes.
 //   * the TPAVI tail z = LayerNorm_C(BN(W_z y) + x) runs one wavefront per row with shuffle
 //     reductions only (no LDS, no barrier).
-#include "glf_common.h"
+#include "stream_common.h"
 #include "split_f16.h"
+
+using namespace glf;
 
 namespace {
 
@@ -652,12 +654,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
 // ---- TPAVI tail: one wavefront per row ---------------------------------------------------
 constexpr int LN_NV = 8;      // float4 per lane => C <= 64*4*8 = 2048
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <bool BWD>
 __global__ __launch_bounds__(256) void bn_res_ln_kernel(const float* __restrict__ w, const float* __restrict__ x, Coef bn,
                                                         const float* __restrict__ ln_g, const float* __restrict__ ln_b, float eps,
@@ -751,14 +747,6 @@ __global__ __launch_bounds__(256) void bn_res_ln_kernel(const float* __restrict_
     }
 }
 
-inline int stream_grid(long long total, int block) {
-    long long g = (total + block - 1) / block;
-    const long long cap = (long long)glf::num_cus() * 8;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 template <class Op>
 int launch_colreduce(Op op, int rows, int c, double* ws, hipStream_t s) {
     const int slices = n_slices_c(rows, c);
@@ -775,7 +763,6 @@ extern "C" size_t glf_bn_workspace(int rows, int c) {
 }
 
 #define REQ_C4(c) GLF_REQUIRE((c) > 0 && ((c) % 4) == 0, GLF_ERR_BAD_SHAPE, "channel count must be a positive multiple of 4 (got %d)", (c))
-#define REQ_AL(p, name) GLF_REQUIRE(al16(p), GLF_ERR_BAD_SHAPE, name " must be 16-byte aligned")
 #define REQ_LD(ld, name) GLF_REQUIRE(((ld) % 4) == 0, GLF_ERR_BAD_SHAPE, name " must be a multiple of 4")
 
 extern "C" int glf_bn_stats(const float* x, int ldx, int rows, int c, float eps, float momentum,

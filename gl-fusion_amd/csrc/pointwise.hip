@@ -2,29 +2,22 @@
 // view stacking, bilinear up-sampling, loss and metric reductions, weight re-layout.
 // All channels-last; 16-byte accesses wherever the channel count allows; 64-wide wavefront
 // reductions via __shfl_xor.
-#include "glf_common.h"
+//
+// The streaming ops between the contractions (ReLU, dropout, axpby, max-pool, gate, frame adds, n-ary sum, row broadcast) exist for
+// fp32 and for bf16 storage (glf_* / glf_s16_*): ONE kernel body each, templated on <storage type T, elements per access W> through
+// Stream<T, W> (stream_common.h), instantiated as <float, 1> / <float, 4> / <u16, 8>.
+#include "stream_common.h"
 #include "split_f16.h"
+
+using namespace glf;
 
 namespace {
 
-inline int stream_grid(long long total, int block) {
-    long long g = (total + block - 1) / block;
-    const long long cap = (long long)glf::num_cus() * 8;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ---------------------------------------------------------------------------------------
 // weight re-layout
@@ -68,6 +61,22 @@ __global__ __launch_bounds__(256) void transpose2d_kernel(const float* __restric
         if (c < cols && r < rows) dst[boff + (long long)c * rows + r] = tile[tx][i];
     }
 }
+// the same for 16-bit elements: a 64 x 64 tile (a wavefront reads / writes 128 contiguous bytes either way)
+__global__ __launch_bounds__(256) void s16_transpose2d_kernel(const u16* __restrict__ src, u16* __restrict__ dst, int rows, int cols) {
+    __shared__ u16 tile[64][66];
+    const long long boff = (long long)blockIdx.z * rows * cols;
+    const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (int i = ty; i < 64; i += 4) {
+        const int r = r0 + i, c = c0 + tx;
+        tile[i][tx] = (r < rows && c < cols) ? src[boff + (long long)r * cols + c] : (u16)0;
+    }
+    __syncthreads();
+    for (int i = ty; i < 64; i += 4) {
+        const int c = c0 + i, r = r0 + tx;
+        if (c < cols && r < rows) dst[boff + (long long)c * rows + r] = tile[tx][i];
+    }
+}
 
 // the same with strides: src[b][r][c] at src + b * bs_src + r * ld_src + c; dst[b][c][r] at dst + b * bs_dst + c * ld_dst + r for
 // r < rows_pad, ZERO for rows <= r < rows_pad (a reduction dimension padded to the contraction kernels' K granule)
@@ -96,12 +105,6 @@ __global__ __launch_bounds__(256) void transpose2d_strided_kernel(const float* _
 // ---------------------------------------------------------------------------------------
 constexpr int ST = 16, SP = ST + 6;
 // 16-bit storage (glf_s16_stem7x7_*): the conv output / its gradient are bf16; arithmetic stays fp32
-__device__ __forceinline__ unsigned stem_pack2(float a, float b) {
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-    const f32x2_ v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_));
-}
 template <int COUT, bool OUT16>
 __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                        void* __restrict__ yv, int h, int wd, int ho, int wo, int pad) {
@@ -145,8 +148,8 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__
             a3.x = fmaf(v, w3.x, a3.x); a3.y = fmaf(v, w3.y, a3.y); a3.z = fmaf(v, w3.z, a3.z); a3.w = fmaf(v, w3.w, a3.w);
         }
         if (OUT16) {
-            *reinterpret_cast<uint4*>(dst16 + c0) = make_uint4(stem_pack2(a0.x, a0.y), stem_pack2(a0.z, a0.w), stem_pack2(a1.x, a1.y), stem_pack2(a1.z, a1.w));
-            *reinterpret_cast<uint4*>(dst16 + c0 + 8) = make_uint4(stem_pack2(a2.x, a2.y), stem_pack2(a2.z, a2.w), stem_pack2(a3.x, a3.y), stem_pack2(a3.z, a3.w));
+            *reinterpret_cast<uint4*>(dst16 + c0) = make_uint4(pack2(a0.x, a0.y), pack2(a0.z, a0.w), pack2(a1.x, a1.y), pack2(a1.z, a1.w));
+            *reinterpret_cast<uint4*>(dst16 + c0 + 8) = make_uint4(pack2(a2.x, a2.y), pack2(a2.z, a2.w), pack2(a3.x, a3.y), pack2(a3.z, a3.w));
         } else {
             *reinterpret_cast<float4*>(dst + c0) = a0; *reinterpret_cast<float4*>(dst + c0 + 4) = a1;
             *reinterpret_cast<float4*>(dst + c0 + 8) = a2; *reinterpret_cast<float4*>(dst + c0 + 12) = a3;
@@ -212,15 +215,21 @@ __global__ __launch_bounds__(1024) void stem_wgrad_finalize(const float* __restr
 // ---------------------------------------------------------------------------------------
 // maxpool 3x3 stride 2 pad 1
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ idx,
-                                                          int n, int h, int w, int c4, int ho, int wo) {
-    const long long total = (long long)n * ho * wo * c4;
+// W window indices (one byte each), stored and loaded in one W-byte access
+template <int W> struct alignas(W) IdxPack { unsigned w[W / 4]; };
+
+template <class T, int W>
+__global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, uint8_t* __restrict__ idx,
+                                                          int n, int h, int w, int cw, int ho, int wo) {
+    const long long total = (long long)n * ho * wo * cw;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int cc = (int)(i % c4); long long p = i / c4;
+        const int cc = (int)(i % cw); long long p = i / cw;
         const int ox = (int)(p % wo); p /= wo;
         const int oy = (int)(p % ho); const int nn = (int)(p / ho);
-        float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-        int b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+        FV<W> best;
+        unsigned bi[W];
+#pragma unroll
+        for (int j = 0; j < W; ++j) { best.v[j] = -INFINITY; bi[j] = 0; }
         bool first = true;
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky)
@@ -228,27 +237,32 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restric
             for (int kx = 0; kx < 3; ++kx) {
                 const int iy = oy * 2 - 1 + ky, ix = ox * 2 - 1 + kx;
                 if (iy < 0 || iy >= h || ix < 0 || ix >= w) continue;
-                const float4 v = *reinterpret_cast<const float4*>(x + (((long long)nn * h + iy) * w + ix) * (c4 * 4) + cc * 4);
-                const int t = ky * 3 + kx;
+                const FV<W> v = Stream<T, W>::ld(x + (((long long)nn * h + iy) * w + ix) * (cw * W) + cc * W);
+                const unsigned t = ky * 3 + kx;
                 // ATen: take the first in-range element, then strictly-greater (or NaN) replaces
-                if (first || v.x > best.x || v.x != v.x) { best.x = v.x; b0 = t; }
-                if (first || v.y > best.y || v.y != v.y) { best.y = v.y; b1 = t; }
-                if (first || v.z > best.z || v.z != v.z) { best.z = v.z; b2 = t; }
-                if (first || v.w > best.w || v.w != v.w) { best.w = v.w; b3 = t; }
+#pragma unroll
+                for (int j = 0; j < W; ++j)
+                    if (first || v.v[j] > best.v[j] || v.v[j] != v.v[j]) { best.v[j] = v.v[j]; bi[j] = t; }
                 first = false;
             }
-        *reinterpret_cast<float4*>(y + i * 4) = best;
-        *reinterpret_cast<uchar4*>(idx + i * 4) = make_uchar4((unsigned char)b0, (unsigned char)b1, (unsigned char)b2, (unsigned char)b3);
+        Stream<T, W>::st(y + i * W, best);
+        IdxPack<W> pk;
+#pragma unroll
+        for (int q = 0; q < W / 4; ++q) pk.w[q] = bi[4 * q] | (bi[4 * q + 1] << 8) | (bi[4 * q + 2] << 16) | (bi[4 * q + 3] << 24);
+        *reinterpret_cast<IdxPack<W>*>(idx + i * W) = pk;
     }
 }
-__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restrict__ dy, const uint8_t* __restrict__ idx, float* __restrict__ dx,
-                                                          int n, int h, int w, int c4, int ho, int wo) {
-    const long long total = (long long)n * h * w * c4;
+template <class T, int W>
+__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ dy, const uint8_t* __restrict__ idx, T* __restrict__ dx,
+                                                          int n, int h, int w, int cw, int ho, int wo) {
+    const long long total = (long long)n * h * w * cw;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int cc = (int)(i % c4); long long p = i / c4;
+        const int cc = (int)(i % cw); long long p = i / cw;
         const int ix = (int)(p % w); p /= w;
         const int iy = (int)(p % h); const int nn = (int)(p / h);
-        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+        FV<W> g;
+#pragma unroll
+        for (int j = 0; j < W; ++j) g.v[j] = 0.f;
         // windows (oy,ox) that contain (iy,ix): iy = 2*oy - 1 + ky
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
@@ -262,17 +276,16 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restric
                 if (nx < 0 || (nx & 1)) continue;
                 const int ox = nx >> 1;
                 if (ox >= wo) continue;
-                const long long o = ((((long long)nn * ho + oy) * wo + ox) * c4 + cc) * 4;
-                const uchar4 t = *reinterpret_cast<const uchar4*>(idx + o);
-                const float4 d = *reinterpret_cast<const float4*>(dy + o);
-                const int me = ky * 3 + kx;
-                if (t.x == me) g.x += d.x;
-                if (t.y == me) g.y += d.y;
-                if (t.z == me) g.z += d.z;
-                if (t.w == me) g.w += d.w;
+                const long long o = ((((long long)nn * ho + oy) * wo + ox) * cw + cc) * W;
+                const IdxPack<W> t = *reinterpret_cast<const IdxPack<W>*>(idx + o);
+                const FV<W> d = Stream<T, W>::ld(dy + o);
+                const unsigned me = ky * 3 + kx;
+#pragma unroll
+                for (int j = 0; j < W; ++j)
+                    if (((t.w[j >> 2] >> (8 * (j & 3))) & 0xffu) == me) g.v[j] += d.v[j];
             }
         }
-        *reinterpret_cast<float4*>(dx + i * 4) = g;
+        Stream<T, W>::st(dx + i * W, g);
     }
 }
 
@@ -330,55 +343,89 @@ __global__ __launch_bounds__(256) void sum_rows4_kernel(const float* __restrict_
         *reinterpret_cast<float4*>(y + (long long)n * 4 * c4 + 4 * cq) = make_float4((float)(sc * s0), (float)(sc * s1), (float)(sc * s2), (float)(sc * s3));
     }
 }
-__global__ __launch_bounds__(256) void bcast_rows4_kernel(const float* __restrict__ x, float* __restrict__ y, int ld, float scale, int p, int c4, long long total4) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total4; i += (long long)gridDim.x * blockDim.x) {
-        const int cc = (int)(i % c4); const long long row = i / c4;
-        const long long n = row / p;
-        const float4 v = *reinterpret_cast<const float4*>(x + (n * c4 + cc) * 4);
-        *reinterpret_cast<float4*>(y + row * ld + 4 * cc) = make_float4(scale * v.x, scale * v.y, scale * v.z, scale * v.w);
-    }
-}
-__global__ __launch_bounds__(256) void bcast_rows_kernel(const float* __restrict__ x, float* __restrict__ y, int ld, float scale, int p, int c, long long total) {
+// y[n][p][c] = scale * x[n][c]   (y row stride ld, storage T; x storage TX: the ASPP pooled branch stays fp32 up to this broadcast)
+template <class T, class TX, int W>
+__global__ __launch_bounds__(256) void bcast_rows_kernel(const TX* __restrict__ x, T* __restrict__ y, int ld, float scale, int p, int cw, long long total) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int cc = (int)(i % c); const long long row = i / c;
+        const int cc = (int)(i % cw); const long long row = i / cw;
         const long long n = row / p;
-        y[row * ld + cc] = scale * x[n * c + cc];
+        FV<W> v = Stream<TX, W>::ld(x + (n * cw + cc) * W);
+#pragma unroll
+        for (int j = 0; j < W; ++j) v.v[j] *= scale;
+        Stream<T, W>::st(y + row * ld + cc * W, v);
     }
 }
 
 // ---------------------------------------------------------------------------------------
 // dropout (counter-based; same mask recomputed in backward from the seed)
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned mix64(unsigned long long z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (unsigned)(z >> 40);                           // 24 bits
-}
-__global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long long n, float p, float scale,
+template <class T, int W>
+__global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, T* __restrict__ y, long long n, float p, float scale,
                                                       unsigned long long seed, const unsigned long long* __restrict__ step) {
     // `step`: a device counter the caller advances once per training step.  A launch recorded in a hipGraph replays with the
     // SAME `seed` argument every time; the counter is what gives every replay its own mask (forward and backward of one step
-    // read the same value).
+    // read the same value).  n counts accesses of W elements; the hash is taken per ELEMENT index.
     if (step) seed += *step * 0xD1B54A32D192ED03ull;
     const unsigned thr = (unsigned)(p * 16777216.0f);
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        y[i] = (mix64(seed * 0x100000001B3ull + (unsigned long long)i) >= thr) ? x[i] * scale : 0.f;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        FV<W> v = Stream<T, W>::ld(x + i * W);
+#pragma unroll
+        for (int j = 0; j < W; ++j) v.v[j] = (mix64(seed * 0x100000001B3ull + (unsigned long long)(i * W + j)) >= thr) ? v.v[j] * scale : 0.f;
+        Stream<T, W>::st(y + i * W, v);
+    }
 }
 
-__global__ __launch_bounds__(256) void relu_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long long n) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) y[i] = fmaxf(x[i], 0.f);
+template <class T, int W>
+__global__ __launch_bounds__(256) void relu_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, long long n) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        FV<W> v = Stream<T, W>::ld(x + i * W);
+#pragma unroll
+        for (int j = 0; j < W; ++j) v.v[j] = fmaxf(v.v[j], 0.f);
+        Stream<T, W>::st(y + i * W, v);
+    }
 }
-__global__ __launch_bounds__(256) void relu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, float* __restrict__ dx, long long n) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) dx[i] = y[i] > 0.f ? dy[i] : 0.f;
+template <class T, int W>
+__global__ __launch_bounds__(256) void relu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ y, T* __restrict__ dx, long long n) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        FV<W> g = Stream<T, W>::ld(dy + i * W);
+        const FV<W> v = Stream<T, W>::ld(y + i * W);
+#pragma unroll
+        for (int j = 0; j < W; ++j) g.v[j] = v.v[j] > 0.f ? g.v[j] : 0.f;
+        Stream<T, W>::st(dx + i * W, g);
+    }
+}
+// out = a * x + b * y: nw accesses of W elements, then the n - W * nw elements left over one by one
+template <class T, int W>
+__global__ __launch_bounds__(256) void axpby_kernel(const T* __restrict__ x, const T* __restrict__ y, T* __restrict__ out, float a, float b,
+                                                    long long nw, long long n) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nw; i += (long long)gridDim.x * blockDim.x) {
+        FV<W> u = Stream<T, W>::ld(x + i * W);
+        const FV<W> v = Stream<T, W>::ld(y + i * W);
+#pragma unroll
+        for (int j = 0; j < W; ++j) u.v[j] = a * u.v[j] + b * v.v[j];
+        Stream<T, W>::st(out + i * W, u);
+    }
+    for (long long i = W * nw + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        Stream<T, 1>::st(out + i, {{a * Stream<T, 1>::ld(x + i).v[0] + b * Stream<T, 1>::ld(y + i).v[0]}});
 }
 
 // ---------------------------------------------------------------------------------------
 // local gate
 // ---------------------------------------------------------------------------------------
+// lane 0 of a gate-backward row: da = sum_c dy * f  ->  the gradients of the class and centre logits
+__device__ __forceinline__ void gate_bwd_logits(float da, int lane, int row, float a, const float* __restrict__ cls, int ncls, const float* __restrict__ ctr,
+                                                const int* __restrict__ amax, float weight, float* __restrict__ dcls, float* __restrict__ dctr) {
+    if (lane != 0) return;
+    const int bi = amax[row];
+    const float m = sigmoidf_(cls[(long long)row * ncls + bi]);
+    const float cc = sigmoidf_(ctr[row]);
+    const float dt = da * a * (1.f - a) * weight;            // d/d(m*cc)
+    for (int k = 0; k < ncls; ++k) dcls[(long long)row * ncls + k] = (k == bi) ? dt * cc * m * (1.f - m) : 0.f;
+    dctr[row] = dt * m * cc * (1.f - cc);
+}
+template <class T, int W>
 __global__ __launch_bounds__(256) void gate_fwd_kernel(const float* __restrict__ cls, int ncls, const float* __restrict__ ctr,
-                                                       const float* __restrict__ f, float* __restrict__ y, float* __restrict__ a_out,
+                                                       const T* __restrict__ f, T* __restrict__ y, float* __restrict__ a_out,
                                                        int* __restrict__ amax, float weight, int rows, int c) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -390,10 +437,15 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const float* __restrict__
     const float cc = sigmoidf_(ctr[row]);
     const float a = sigmoidf_(weight * best * cc);
     if (lane == 0) { a_out[row] = a; amax[row] = bi; }
-    const float4* src = reinterpret_cast<const float4*>(f + (long long)row * c);
-    float4* dst = reinterpret_cast<float4*>(y + (long long)row * c);
-    for (int i = lane; i < (c >> 2); i += 64) { float4 v = src[i]; v.x *= a; v.y *= a; v.z *= a; v.w *= a; dst[i] = v; }
+    for (int i = lane; i < c / W; i += 64) {
+        FV<W> v = Stream<T, W>::ld(f + (long long)row * c + i * W);
+#pragma unroll
+        for (int j = 0; j < W; ++j) v.v[j] *= a;
+        Stream<T, W>::st(y + (long long)row * c + i * W, v);
+    }
 }
+// The two storage forms of gate backward stay two kernels: the row dot product sum(dy * f) is summed pairwise-of-four per access in
+// fp32 and sequentially in bf16, and both orders are kept bit for bit (one body would need a per-type branch in the arithmetic).
 __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ f, const float* __restrict__ cls, int ncls,
                                                        const float* __restrict__ ctr, const float* __restrict__ a_in, const int* __restrict__ amax,
                                                        float weight, float* __restrict__ df, float* __restrict__ dcls, float* __restrict__ dctr,
@@ -411,19 +463,29 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__
         s += (g.x * v.x + g.y * v.y) + (g.z * v.z + g.w * v.w);
         d4[i] = make_float4(g.x * a, g.y * a, g.z * a, g.w * a);
     }
-    const float da = wave_sum(s);
-    if (lane == 0) {
-        const int bi = amax[row];
-        const float m = sigmoidf_(cls[(long long)row * ncls + bi]);
-        const float cc = sigmoidf_(ctr[row]);
-        const float dt = da * a * (1.f - a) * weight;            // d/d(m*cc)
-        for (int k = 0; k < ncls; ++k) dcls[(long long)row * ncls + k] = (k == bi) ? dt * cc * m * (1.f - m) : 0.f;
-        dctr[row] = dt * m * cc * (1.f - cc);
+    gate_bwd_logits(wave_sum(s), lane, row, a, cls, ncls, ctr, amax, weight, dcls, dctr);
+}
+__global__ __launch_bounds__(256) void s16_gate_bwd_kernel(const u16* __restrict__ dy, const u16* __restrict__ f, const float* __restrict__ cls, int ncls,
+                                                           const float* __restrict__ ctr, const float* __restrict__ a_in, const int* __restrict__ amax,
+                                                           float weight, u16* __restrict__ df, float* __restrict__ dcls, float* __restrict__ dctr,
+                                                           int rows, int c) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float a = a_in[row];
+    float s = 0.f;
+    for (int i = lane; i < (c >> 3); i += 64) {
+        F8 g = ld8(dy + (long long)row * c + i * 8);
+        const F8 v = ld8(f + (long long)row * c + i * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { s += g.v[j] * v.v[j]; g.v[j] *= a; }
+        st8(df + (long long)row * c + i * 8, g);
     }
+    gate_bwd_logits(wave_sum(s), lane, row, a, cls, ncls, ctr, amax, weight, dcls, dctr);
 }
 
 // ---------------------------------------------------------------------------------------
-// frame-strided copies / adds
+// frame-strided copies / adds (frame strides and `inner` in elements)
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void copy_frames_kernel(const float4* __restrict__ src, long long sfs, float4* __restrict__ dst, long long dfs,
                                                           long long inner4, long long total4) {
@@ -448,22 +510,31 @@ __global__ __launch_bounds__(256) void copy_frames_split_kernel(const float4* __
         dst_pk[n * dfs + r] = make_float4(h.x, h.y, l.x, l.y);
     }
 }
-__global__ __launch_bounds__(256) void add_frames_kernel(const float4* __restrict__ a, long long afs, const float4* __restrict__ b, long long bfs,
-                                                         float4* __restrict__ dst, long long dfs, long long inner4, long long total4) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total4; i += (long long)gridDim.x * blockDim.x) {
-        const long long n = i / inner4, r = i - n * inner4;
-        const float4 u = a[n * afs + r], v = b[n * bfs + r];
-        dst[n * dfs + r] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
+template <class T, int W>
+__global__ __launch_bounds__(256) void add_frames_kernel(const T* __restrict__ a, long long afs, const T* __restrict__ b, long long bfs,
+                                                         T* __restrict__ dst, long long dfs, long long innerw, long long total) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long n = i / innerw, r = i - n * innerw;
+        FV<W> u = Stream<T, W>::ld(a + n * afs + r * W);
+        const FV<W> v = Stream<T, W>::ld(b + n * bfs + r * W);
+#pragma unroll
+        for (int j = 0; j < W; ++j) u.v[j] += v.v[j];
+        Stream<T, W>::st(dst + n * dfs + r * W, u);
     }
 }
 
 // n-ary sum (gradient fan-in of a tensor consumed by several branches): one pass, k reads + 1 write
-struct AddNPtrs { const float4* p[8]; };
-__global__ __launch_bounds__(256) void add_n_kernel(AddNPtrs in, int k, float4* __restrict__ out, long long n4) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        float4 a = in.p[0][i];
-        for (int j = 1; j < k; ++j) { const float4 b = in.p[j][i]; a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
-        out[i] = a;
+template <class T> struct AddNPtrs { const T* p[8]; };
+template <class T, int W>
+__global__ __launch_bounds__(256) void add_n_kernel(AddNPtrs<T> in, int k, T* __restrict__ out, long long n) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        FV<W> a = Stream<T, W>::ld(in.p[0] + i * W);
+        for (int j = 1; j < k; ++j) {
+            const FV<W> b = Stream<T, W>::ld(in.p[j] + i * W);
+#pragma unroll
+            for (int e = 0; e < W; ++e) a.v[e] += b.v[e];
+        }
+        Stream<T, W>::st(out + i * W, a);
     }
 }
 
@@ -600,6 +671,67 @@ __global__ __launch_bounds__(256) void overlap_kernel(const float* __restrict__ 
     if ((threadIdx.x & 63) == 0) { atomicAdd(counts + 0, tp); atomicAdd(counts + 1, fp); atomicAdd(counts + 2, fn); atomicAdd(counts + 3, tn); }
 }
 
+// ---------------------------------------------------------------------------------------
+// one launcher per streaming op; the extern "C" entry points of both families check their arguments and call these
+// ---------------------------------------------------------------------------------------
+template <class T, int W>
+int launch_maxpool_fwd(const void* x, void* y, uint8_t* idx, int n, int h, int w, int c, hipStream_t s, const char* what) {
+    const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
+    const long long total = (long long)n * ho * wo * (c / W);
+    hipLaunchKernelGGL((maxpool_fwd_kernel<T, W>), dim3(stream_grid(total, 256)), dim3(256), 0, s, static_cast<const T*>(x), static_cast<T*>(y), idx,
+                       n, h, w, c / W, ho, wo);
+    return glf::check_launch(what);
+}
+template <class T, int W>
+int launch_maxpool_bwd(const void* dy, const uint8_t* idx, void* dx, int n, int h, int w, int c, hipStream_t s, const char* what) {
+    const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
+    const long long total = (long long)n * h * w * (c / W);
+    hipLaunchKernelGGL((maxpool_bwd_kernel<T, W>), dim3(stream_grid(total, 256)), dim3(256), 0, s, static_cast<const T*>(dy), idx, static_cast<T*>(dx),
+                       n, h, w, c / W, ho, wo);
+    return glf::check_launch(what);
+}
+template <class T, class TX, int W>
+int launch_bcast_rows(const void* x, void* y, int ldy, float scale, int n, int p, int c, hipStream_t s, const char* what) {
+    const long long total = (long long)n * p * (c / W);
+    hipLaunchKernelGGL((bcast_rows_kernel<T, TX, W>), dim3(stream_grid(total, 256)), dim3(256), 0, s, static_cast<const TX*>(x), static_cast<T*>(y), ldy,
+                       scale, p, c / W, total);
+    return glf::check_launch(what);
+}
+template <class T, int W>
+int launch_dropout(const void* x, void* y, int64_t numel, float p, uint64_t seed, const uint64_t* step_counter, hipStream_t s, const char* what) {
+    hipLaunchKernelGGL((dropout_kernel<T, W>), dim3(stream_grid(numel / W, 256)), dim3(256), 0, s, static_cast<const T*>(x), static_cast<T*>(y),
+                       (long long)(numel / W), p, 1.0f / (1.0f - p), (unsigned long long)seed, reinterpret_cast<const unsigned long long*>(step_counter));
+    return glf::check_launch(what);
+}
+template <class T, int W>
+int launch_relu(const void* dy, const void* y, void* out, int64_t numel, hipStream_t s, const char* what) {       // dy == NULL: forward of y
+    const dim3 grid(stream_grid(numel / W, 256));
+    if (dy) hipLaunchKernelGGL((relu_bwd_kernel<T, W>), grid, dim3(256), 0, s, static_cast<const T*>(dy), static_cast<const T*>(y), static_cast<T*>(out), (long long)(numel / W));
+    else hipLaunchKernelGGL((relu_fwd_kernel<T, W>), grid, dim3(256), 0, s, static_cast<const T*>(y), static_cast<T*>(out), (long long)(numel / W));
+    return glf::check_launch(what);
+}
+template <class T, int W>
+int launch_gate_fwd(const float* cls, int ncls, const float* ctr, const void* f, void* y, float* a, int32_t* argmax, float weight, int rows, int c,
+                    hipStream_t s, const char* what) {
+    hipLaunchKernelGGL((gate_fwd_kernel<T, W>), dim3((rows + 3) / 4), dim3(256), 0, s, cls, ncls, ctr, static_cast<const T*>(f), static_cast<T*>(y), a, argmax,
+                       weight, rows, c);
+    return glf::check_launch(what);
+}
+template <class T, int W>
+int launch_add_frames(const void* a, int64_t a_fs, const void* b, int64_t b_fs, void* dst, int64_t dst_fs, int n, int64_t inner, hipStream_t s, const char* what) {
+    const long long total = (long long)n * (inner / W);
+    hipLaunchKernelGGL((add_frames_kernel<T, W>), dim3(stream_grid(total, 256)), dim3(256), 0, s, static_cast<const T*>(a), (long long)a_fs,
+                       static_cast<const T*>(b), (long long)b_fs, static_cast<T*>(dst), (long long)dst_fs, (long long)(inner / W), total);
+    return glf::check_launch(what);
+}
+template <class T, int W>
+int launch_add_n(const void* const* inputs, int k, void* out, int64_t numel, hipStream_t s, const char* what) {
+    AddNPtrs<T> in;
+    for (int j = 0; j < 8; ++j) in.p[j] = static_cast<const T*>(inputs[j < k ? j : 0]);
+    hipLaunchKernelGGL((add_n_kernel<T, W>), dim3(stream_grid(numel / W, 256)), dim3(256), 0, s, in, k, static_cast<T*>(out), (long long)(numel / W));
+    return glf::check_launch(what);
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -635,6 +767,14 @@ extern "C" int glf_transpose2d(const float* src, float* dst, int rows, int cols,
     GLF_REQUIRE(rows > 0 && cols > 0 && batch > 0 && batch <= 65535 && (rows + 31) / 32 <= 65535, GLF_ERR_BAD_SHAPE, "transpose2d: bad shape");
     hipLaunchKernelGGL(transpose2d_kernel, dim3((cols + 31) / 32, (rows + 31) / 32, batch), dim3(256), 0, glf::S(s), src, dst, rows, cols);
     return glf::check_launch("transpose2d");
+}
+extern "C" int glf_s16_transpose2d(const void* src, void* dst, int rows, int cols, int batch, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(src && dst, GLF_ERR_NULL, "s16_transpose2d: null argument");
+    GLF_REQUIRE(rows > 0 && cols > 0 && batch > 0 && batch <= 65535, GLF_ERR_BAD_SHAPE, "s16_transpose2d: bad extents");
+    hipLaunchKernelGGL(s16_transpose2d_kernel, dim3((cols + 63) / 64, (rows + 63) / 64, batch), dim3(256), 0, glf::S(s), static_cast<const u16*>(src),
+                       static_cast<u16*>(dst), rows, cols);
+    return glf::check_launch("s16_transpose2d");
 }
 
 extern "C" int glf_transpose2d_strided(const float* src, int64_t ld_src, int64_t batch_stride_src, float* dst, int64_t ld_dst,
@@ -815,20 +955,28 @@ extern "C" int glf_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* idx, int 
     GLF_REQUIRE(x && y && idx, GLF_ERR_NULL, "maxpool_fwd: null argument");
     GLF_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0 && (c % 4) == 0, GLF_ERR_BAD_SHAPE, "maxpool_fwd: bad shape (C %% 4 == 0 required)");
     GLF_REQUIRE(al16(x) && al16(y) && ((reinterpret_cast<uintptr_t>(idx) & 3u) == 0), GLF_ERR_BAD_SHAPE, "maxpool_fwd: alignment");
-    const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
-    const long long total = (long long)n * ho * wo * (c / 4);
-    hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(stream_grid(total, 256)), dim3(256), 0, glf::S(s), x, y, idx, n, h, w, c / 4, ho, wo);
-    return glf::check_launch("maxpool_fwd");
+    return launch_maxpool_fwd<float, 4>(x, y, idx, n, h, w, c, glf::S(s), "maxpool_fwd");
 }
 extern "C" int glf_maxpool3x3s2_bwd(const float* dy, const uint8_t* idx, float* dx, int n, int h, int w, int c, glf_stream_t s) {
     if (int rc = glf::ensure_init()) return rc;
     GLF_REQUIRE(dy && idx && dx, GLF_ERR_NULL, "maxpool_bwd: null argument");
     GLF_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0 && (c % 4) == 0, GLF_ERR_BAD_SHAPE, "maxpool_bwd: bad shape (C %% 4 == 0 required)");
     GLF_REQUIRE(al16(dy) && al16(dx), GLF_ERR_BAD_SHAPE, "maxpool_bwd: alignment");
-    const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
-    const long long total = (long long)n * h * w * (c / 4);
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(stream_grid(total, 256)), dim3(256), 0, glf::S(s), dy, idx, dx, n, h, w, c / 4, ho, wo);
-    return glf::check_launch("maxpool_bwd");
+    return launch_maxpool_bwd<float, 4>(dy, idx, dx, n, h, w, c, glf::S(s), "maxpool_bwd");
+}
+extern "C" int glf_s16_maxpool3x3s2_fwd(const void* x, void* y, uint8_t* idx, int n, int h, int w, int c, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(x && y && idx, GLF_ERR_NULL, "s16_maxpool_fwd: null argument");
+    GLF_REQUIRE(n > 0 && h > 0 && w > 0, GLF_ERR_BAD_SHAPE, "s16_maxpool_fwd: bad extents");
+    REQ_C8(c); REQ_AL(x, "x"); REQ_AL(y, "y");
+    return launch_maxpool_fwd<u16, 8>(x, y, idx, n, h, w, c, glf::S(s), "s16_maxpool_fwd");
+}
+extern "C" int glf_s16_maxpool3x3s2_bwd(const void* dy, const uint8_t* idx, void* dx, int n, int h, int w, int c, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(dy && dx && idx, GLF_ERR_NULL, "s16_maxpool_bwd: null argument");
+    GLF_REQUIRE(n > 0 && h > 0 && w > 0, GLF_ERR_BAD_SHAPE, "s16_maxpool_bwd: bad extents");
+    REQ_C8(c); REQ_AL(dy, "dy"); REQ_AL(dx, "dx");
+    return launch_maxpool_bwd<u16, 8>(dy, idx, dx, n, h, w, c, glf::S(s), "s16_maxpool_bwd");
 }
 
 extern "C" int glf_sum_rows_fwd(const float* dy, int lddy, float* dx, float scale, int n, int p, int c, glf_stream_t s) {
@@ -848,12 +996,17 @@ extern "C" int glf_bcast_rows_scaled(const float* x, float* y, int ldy, float sc
     if (int rc = glf::ensure_init()) return rc;
     GLF_REQUIRE(x && y, GLF_ERR_NULL, "bcast_rows: null argument");
     GLF_REQUIRE(n > 0 && p > 0 && c > 0 && ldy >= c, GLF_ERR_BAD_SHAPE, "bcast_rows: bad shape");
-    const long long total = (long long)n * p * c;
-    if (c % 4 == 0 && ldy % 4 == 0 && al16(x) && al16(y))
-        hipLaunchKernelGGL(bcast_rows4_kernel, dim3(stream_grid(total / 4, 256)), dim3(256), 0, glf::S(s), x, y, ldy, scale, p, c / 4, total / 4);
-    else
-        hipLaunchKernelGGL(bcast_rows_kernel, dim3(stream_grid(total, 256)), dim3(256), 0, glf::S(s), x, y, ldy, scale, p, c, total);
-    return glf::check_launch("bcast_rows");
+    if (c % 4 == 0 && ldy % 4 == 0 && al16(x) && al16(y)) return launch_bcast_rows<float, float, 4>(x, y, ldy, scale, n, p, c, glf::S(s), "bcast_rows");
+    return launch_bcast_rows<float, float, 1>(x, y, ldy, scale, n, p, c, glf::S(s), "bcast_rows");
+}
+extern "C" int glf_s16_bcast_rows(const void* x, int x_dtype, void* y, int ldy, float scale, int n, int p, int c, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(x && y, GLF_ERR_NULL, "s16_bcast_rows: null argument");
+    GLF_REQUIRE(n > 0 && p > 0, GLF_ERR_BAD_SHAPE, "s16_bcast_rows: bad extents");
+    REQ_C8(c); REQ_AL(x, "x"); REQ_AL(y, "y"); REQ_LD8(ldy, "ldy");
+    GLF_REQUIRE(x_dtype == GLF_DT_F32 || x_dtype == GLF_DT_BF16, GLF_ERR_UNSUPPORTED, "s16_bcast_rows: x_dtype must be GLF_DT_F32 or GLF_DT_BF16");
+    if (x_dtype == GLF_DT_F32) return launch_bcast_rows<u16, float, 8>(x, y, ldy, scale, n, p, c, glf::S(s), "s16_bcast_rows");
+    return launch_bcast_rows<u16, u16, 8>(x, y, ldy, scale, n, p, c, glf::S(s), "s16_bcast_rows");
 }
 extern "C" int glf_bcast_rows_fwd(const float* x, float* y, int ldy, int n, int p, int c, glf_stream_t s) {
     return glf_bcast_rows_scaled(x, y, ldy, 1.0f, n, p, c, s);
@@ -863,9 +1016,14 @@ extern "C" int glf_dropout(const float* x, float* y, int64_t numel, float p, uin
     if (int rc = glf::ensure_init()) return rc;
     GLF_REQUIRE(x && y, GLF_ERR_NULL, "dropout: null argument");
     GLF_REQUIRE(numel > 0 && p >= 0.f && p < 1.f, GLF_ERR_BAD_SHAPE, "dropout: numel > 0 and 0 <= p < 1 required");
-    hipLaunchKernelGGL(dropout_kernel, dim3(stream_grid(numel, 256)), dim3(256), 0, glf::S(s), x, y, (long long)numel, p, 1.0f / (1.0f - p),
-                       (unsigned long long)seed, reinterpret_cast<const unsigned long long*>(step_counter));
-    return glf::check_launch("dropout");
+    return launch_dropout<float, 1>(x, y, numel, p, seed, step_counter, glf::S(s), "dropout");
+}
+extern "C" int glf_s16_dropout(const void* x, void* y, int64_t numel, float p, uint64_t seed, const uint64_t* step_counter, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(x && y, GLF_ERR_NULL, "s16_dropout: null argument");
+    GLF_REQUIRE(numel > 0 && numel % 8 == 0 && p >= 0.f && p < 1.f, GLF_ERR_BAD_SHAPE, "s16_dropout: numel must be a positive multiple of 8, 0 <= p < 1");
+    REQ_AL(x, "x"); REQ_AL(y, "y");
+    return launch_dropout<u16, 8>(x, y, numel, p, seed, step_counter, glf::S(s), "s16_dropout");
 }
 __global__ void amax_combine_kernel(const float* a, const float* b, float scale, int sum, float* out) {
     const float va = fabsf(*a), vb = b ? fabsf(*b) : 0.f;
@@ -891,15 +1049,48 @@ extern "C" int glf_relu_fwd(const float* x, float* y, int64_t numel, glf_stream_
     if (int rc = glf::ensure_init()) return rc;
     GLF_REQUIRE(x && y, GLF_ERR_NULL, "relu_fwd: null argument");
     GLF_REQUIRE(numel > 0, GLF_ERR_BAD_SHAPE, "relu_fwd: numel must be > 0");
-    hipLaunchKernelGGL(relu_fwd_kernel, dim3(stream_grid(numel, 256)), dim3(256), 0, glf::S(s), x, y, (long long)numel);
-    return glf::check_launch("relu_fwd");
+    return launch_relu<float, 1>(nullptr, x, y, numel, glf::S(s), "relu_fwd");
 }
 extern "C" int glf_relu_bwd(const float* dy, const float* y, float* dx, int64_t numel, glf_stream_t s) {
     if (int rc = glf::ensure_init()) return rc;
     GLF_REQUIRE(dy && y && dx, GLF_ERR_NULL, "relu_bwd: null argument");
     GLF_REQUIRE(numel > 0, GLF_ERR_BAD_SHAPE, "relu_bwd: numel must be > 0");
-    hipLaunchKernelGGL(relu_bwd_kernel, dim3(stream_grid(numel, 256)), dim3(256), 0, glf::S(s), dy, y, dx, (long long)numel);
-    return glf::check_launch("relu_bwd");
+    return launch_relu<float, 1>(dy, y, dx, numel, glf::S(s), "relu_bwd");
+}
+extern "C" int glf_s16_relu_fwd(const void* x, void* y, int64_t numel, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(x && y, GLF_ERR_NULL, "s16_relu_fwd: null argument");
+    GLF_REQUIRE(numel > 0 && numel % 8 == 0, GLF_ERR_BAD_SHAPE, "s16_relu_fwd: numel must be a positive multiple of 8");
+    REQ_AL(x, "x"); REQ_AL(y, "y");
+    return launch_relu<u16, 8>(nullptr, x, y, numel, glf::S(s), "s16_relu_fwd");
+}
+extern "C" int glf_s16_relu_bwd(const void* dy, const void* y, void* dx, int64_t numel, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(dy && y && dx, GLF_ERR_NULL, "s16_relu_bwd: null argument");
+    GLF_REQUIRE(numel > 0 && numel % 8 == 0, GLF_ERR_BAD_SHAPE, "s16_relu_bwd: numel must be a positive multiple of 8");
+    REQ_AL(dy, "dy"); REQ_AL(y, "y"); REQ_AL(dx, "dx");
+    return launch_relu<u16, 8>(dy, y, dx, numel, glf::S(s), "s16_relu_bwd");
+}
+
+// fp32: a float4 body when all three pointers are 16-byte aligned, single elements for the rest (or for everything)
+extern "C" int glf_axpby(const float* x, const float* y, float* out, float a, float b, int64_t numel, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(x && y && out, GLF_ERR_NULL, "axpby: null argument");
+    GLF_REQUIRE(numel > 0, GLF_ERR_BAD_SHAPE, "axpby: numel must be > 0");
+    const long long n4 = (al16(x) && al16(y) && al16(out)) ? numel / 4 : 0;
+    long long blocks = (numel / 4 + 255) / 256;
+    blocks = blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks);
+    hipLaunchKernelGGL((axpby_kernel<float, 4>), dim3((unsigned)blocks), dim3(256), 0, glf::S(s), x, y, out, a, b, n4, (long long)numel);
+    return glf::check_launch("axpby");
+}
+extern "C" int glf_s16_axpby(const void* x, const void* y, void* out, float a, float b, int64_t numel, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(x && y && out, GLF_ERR_NULL, "s16_axpby: null argument");
+    GLF_REQUIRE(numel > 0 && numel % 8 == 0, GLF_ERR_BAD_SHAPE, "s16_axpby: numel must be a positive multiple of 8");
+    REQ_AL(x, "x"); REQ_AL(y, "y"); REQ_AL(out, "out");
+    hipLaunchKernelGGL((axpby_kernel<u16, 8>), dim3(stream_grid(numel / 8, 256)), dim3(256), 0, glf::S(s), static_cast<const u16*>(x), static_cast<const u16*>(y),
+                       static_cast<u16*>(out), a, b, (long long)(numel / 8), (long long)numel);
+    return glf::check_launch("s16_axpby");
 }
 
 extern "C" int glf_gate_fwd(const float* cls, int ncls, const float* ctr, const float* f, float* y, float* a,
@@ -908,8 +1099,15 @@ extern "C" int glf_gate_fwd(const float* cls, int ncls, const float* ctr, const 
     GLF_REQUIRE(cls && ctr && f && y && a && argmax, GLF_ERR_NULL, "gate_fwd: null argument");
     GLF_REQUIRE(rows > 0 && ncls > 0 && c > 0 && (c % 4) == 0, GLF_ERR_BAD_SHAPE, "gate_fwd: bad shape (C %% 4 == 0 required)");
     GLF_REQUIRE(al16(f) && al16(y), GLF_ERR_BAD_SHAPE, "gate_fwd: alignment");
-    hipLaunchKernelGGL(gate_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, glf::S(s), cls, ncls, ctr, f, y, a, argmax, weight, rows, c);
-    return glf::check_launch("gate_fwd");
+    return launch_gate_fwd<float, 4>(cls, ncls, ctr, f, y, a, argmax, weight, rows, c, glf::S(s), "gate_fwd");
+}
+extern "C" int glf_s16_gate_fwd(const float* cls, int ncls, const float* ctr, const void* f, void* y, float* a, int32_t* argmax, float weight,
+                                int rows, int c, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(cls && ctr && f && y && a && argmax, GLF_ERR_NULL, "s16_gate_fwd: null argument");
+    GLF_REQUIRE(rows > 0 && ncls > 0, GLF_ERR_BAD_SHAPE, "s16_gate_fwd: bad extents");
+    REQ_C8(c); REQ_AL(f, "f"); REQ_AL(y, "y");
+    return launch_gate_fwd<u16, 8>(cls, ncls, ctr, f, y, a, argmax, weight, rows, c, glf::S(s), "s16_gate_fwd");
 }
 extern "C" int glf_gate_bwd(const float* dy, const float* f, const float* cls, int ncls, const float* ctr,
                             const float* a, const int32_t* argmax, float weight,
@@ -920,6 +1118,16 @@ extern "C" int glf_gate_bwd(const float* dy, const float* f, const float* cls, i
     GLF_REQUIRE(al16(dy) && al16(f) && al16(df), GLF_ERR_BAD_SHAPE, "gate_bwd: alignment");
     hipLaunchKernelGGL(gate_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, glf::S(s), dy, f, cls, ncls, ctr, a, argmax, weight, df, dcls, dctr, rows, c);
     return glf::check_launch("gate_bwd");
+}
+extern "C" int glf_s16_gate_bwd(const void* dy, const void* f, const float* cls, int ncls, const float* ctr, const float* a, const int32_t* argmax,
+                                float weight, void* df, float* dcls, float* dctr, int rows, int c, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(dy && f && cls && ctr && a && argmax && df && dcls && dctr, GLF_ERR_NULL, "s16_gate_bwd: null argument");
+    GLF_REQUIRE(rows > 0 && ncls > 0, GLF_ERR_BAD_SHAPE, "s16_gate_bwd: bad extents");
+    REQ_C8(c); REQ_AL(dy, "dy"); REQ_AL(f, "f"); REQ_AL(df, "df");
+    hipLaunchKernelGGL(s16_gate_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, glf::S(s), static_cast<const u16*>(dy), static_cast<const u16*>(f), cls, ncls,
+                       ctr, a, argmax, weight, static_cast<u16*>(df), dcls, dctr, rows, c);
+    return glf::check_launch("s16_gate_bwd");
 }
 
 extern "C" int glf_copy_frames(const float* src, int64_t src_fs, float* dst, int64_t dst_fs, int n, int64_t inner, glf_stream_t s) {
@@ -953,25 +1161,33 @@ extern "C" int glf_add_frames(const float* a, int64_t a_fs, const float* b, int6
     GLF_REQUIRE(n > 0 && inner > 0 && (inner % 4) == 0 && (a_fs % 4) == 0 && (b_fs % 4) == 0 && (dst_fs % 4) == 0, GLF_ERR_BAD_SHAPE,
                 "add_frames: sizes and strides must be positive multiples of 4");
     GLF_REQUIRE(al16(a) && al16(b) && al16(dst), GLF_ERR_BAD_SHAPE, "add_frames: alignment");
-    const long long total4 = (long long)n * (inner / 4);
-    hipLaunchKernelGGL(add_frames_kernel, dim3(stream_grid(total4, 256)), dim3(256), 0, glf::S(s), reinterpret_cast<const float4*>(a),
-                       (long long)(a_fs / 4), reinterpret_cast<const float4*>(b), (long long)(b_fs / 4), reinterpret_cast<float4*>(dst),
-                       (long long)(dst_fs / 4), (long long)(inner / 4), total4);
-    return glf::check_launch("add_frames");
+    return launch_add_frames<float, 4>(a, a_fs, b, b_fs, dst, dst_fs, n, inner, glf::S(s), "add_frames");
+}
+extern "C" int glf_s16_add_frames(const void* a, int64_t a_fs, const void* b, int64_t b_fs, void* dst, int64_t dst_fs, int n, int64_t inner,
+                                  glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(a && b && dst, GLF_ERR_NULL, "s16_add_frames: null argument");
+    GLF_REQUIRE(n > 0 && inner > 0 && inner % 8 == 0 && a_fs % 8 == 0 && b_fs % 8 == 0 && dst_fs % 8 == 0, GLF_ERR_BAD_SHAPE,
+                "s16_add_frames: inner and the frame strides must be multiples of 8");
+    REQ_AL(a, "a"); REQ_AL(b, "b"); REQ_AL(dst, "dst");
+    return launch_add_frames<u16, 8>(a, a_fs, b, b_fs, dst, dst_fs, n, inner, glf::S(s), "s16_add_frames");
 }
 
 extern "C" int glf_add_n(const float* const* inputs, int k, float* out, int64_t numel, glf_stream_t s) {
     if (int rc = glf::ensure_init()) return rc;
     GLF_REQUIRE(inputs && out, GLF_ERR_NULL, "add_n: null argument");
     GLF_REQUIRE(k >= 1 && k <= 8 && numel > 0 && (numel % 4) == 0, GLF_ERR_BAD_SHAPE, "add_n: 1 <= k <= 8 and numel %% 4 == 0 required");
-    AddNPtrs ptrs;
-    for (int j = 0; j < 8; ++j) {
-        ptrs.p[j] = reinterpret_cast<const float4*>(inputs[j < k ? j : 0]);
-        GLF_REQUIRE(ptrs.p[j] != nullptr && al16(ptrs.p[j]), GLF_ERR_BAD_SHAPE, "add_n: inputs must be non-null and 16-byte aligned");
-    }
+    for (int j = 0; j < k; ++j) GLF_REQUIRE(inputs[j] != nullptr && al16(inputs[j]), GLF_ERR_BAD_SHAPE, "add_n: inputs must be non-null and 16-byte aligned");
     GLF_REQUIRE(al16(out), GLF_ERR_BAD_SHAPE, "add_n: out must be 16-byte aligned");
-    hipLaunchKernelGGL(add_n_kernel, dim3(stream_grid(numel / 4, 256)), dim3(256), 0, glf::S(s), ptrs, k, reinterpret_cast<float4*>(out), (long long)(numel / 4));
-    return glf::check_launch("add_n");
+    return launch_add_n<float, 4>(reinterpret_cast<const void* const*>(inputs), k, out, numel, glf::S(s), "add_n");
+}
+extern "C" int glf_s16_add_n(const void* const* inputs, int k, void* out, int64_t numel, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(inputs && out, GLF_ERR_NULL, "s16_add_n: null argument");
+    GLF_REQUIRE(k >= 1 && k <= 8 && numel > 0 && numel % 8 == 0, GLF_ERR_BAD_SHAPE, "s16_add_n: 1 <= k <= 8, numel a positive multiple of 8");
+    for (int i = 0; i < k; ++i) { GLF_REQUIRE(inputs[i], GLF_ERR_NULL, "s16_add_n: null input"); REQ_AL(inputs[i], "input"); }
+    REQ_AL(out, "out");
+    return launch_add_n<u16, 8>(inputs, k, out, numel, glf::S(s), "s16_add_n");
 }
 
 extern "C" int glf_softmax_rows(float* x, int64_t rows, int cols, glf_stream_t s) {

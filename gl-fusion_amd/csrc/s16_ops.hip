@@ -5,54 +5,12 @@
 // column and workgroup in a zero-filled [2][C] buffer -- the same contract as glf_gemm_params.colstats, so a BatchNorm takes
 // its sums from the producing contraction's epilogue or from s16_colstats_kernel alike, and every apply kernel finishes the
 // statistics itself (no finalize launches).
-#include "glf_common.h"
+#include "stream_common.h"
+
+using namespace glf;
 
 namespace {
 
-typedef unsigned short u16;
-
-struct F8 { float v[8]; };
-
-__device__ __forceinline__ F8 ld8(const u16* p) {
-    const uint4 q = *reinterpret_cast<const uint4*>(p);
-    F8 o;
-    o.v[0] = __uint_as_float(q.x << 16); o.v[1] = __uint_as_float(q.x & 0xffff0000u);
-    o.v[2] = __uint_as_float(q.y << 16); o.v[3] = __uint_as_float(q.y & 0xffff0000u);
-    o.v[4] = __uint_as_float(q.z << 16); o.v[5] = __uint_as_float(q.z & 0xffff0000u);
-    o.v[6] = __uint_as_float(q.w << 16); o.v[7] = __uint_as_float(q.w & 0xffff0000u);
-    return o;
-}
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-    const f32x2_ v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_));
-}
-__device__ __forceinline__ void st8(u16* p, const F8& o) {
-    *reinterpret_cast<uint4*>(p) = make_uint4(pack2(o.v[0], o.v[1]), pack2(o.v[2], o.v[3]), pack2(o.v[4], o.v[5]), pack2(o.v[6], o.v[7]));
-}
-__device__ __forceinline__ F8 ldf8(const float* p) {
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    F8 o;
-    o.v[0] = a.x; o.v[1] = a.y; o.v[2] = a.z; o.v[3] = a.w; o.v[4] = b.x; o.v[5] = b.y; o.v[6] = b.z; o.v[7] = b.w;
-    return o;
-}
-__device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ u16 f2bf(float f) { return (u16)(pack2(f, 0.f) & 0xffffu); }
-
-inline int stream_grid(long long total, int block) {
-    long long g = (total + block - 1) / block;
-    const long long cap = (long long)glf::num_cus() * 8;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 // the forward value of one BatchNorm element: ONE definition, so the ReLU mask recomputed in backward is the forward's
 __device__ __forceinline__ float bn_val(float x, float mu, float is, float ga, float be) { return (x - mu) * is * ga + be; }
 
@@ -177,15 +135,6 @@ struct OpBnBwd16 {          // (dy', dy' * xhat), dy' = (dy + dy2) * relu-mask
         }
     }
 };
-
-__device__ __forceinline__ F8 unpack8(const uint4 q) {
-    F8 o;
-    o.v[0] = __uint_as_float(q.x << 16); o.v[1] = __uint_as_float(q.x & 0xffff0000u);
-    o.v[2] = __uint_as_float(q.y << 16); o.v[3] = __uint_as_float(q.y & 0xffff0000u);
-    o.v[4] = __uint_as_float(q.z << 16); o.v[5] = __uint_as_float(q.z & 0xffff0000u);
-    o.v[6] = __uint_as_float(q.w << 16); o.v[7] = __uint_as_float(q.w & 0xffff0000u);
-    return o;
-}
 
 // BatchNorm backward column reduce, the form that runs: the generic kernel above with OpBnBwd16 compiled into a chain of dependent
 // loads (dy -> wait -> dy2 -> wait -> x -> wait -> mask -> the four coefficient vectors again for every row: the ISA had five
@@ -585,76 +534,8 @@ __global__ __launch_bounds__(256) void s16_ln_param_finalize(const float* __rest
 }
 
 // ----------------------------------------------------------------------------------------------------------------------
-// pooling / broadcast / dropout / gate / adds / casts
+// per-frame row sums, casts (the other streaming ops share their kernel bodies with fp32 storage: pointwise.hip)
 // ----------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void s16_maxpool_fwd_kernel(const u16* __restrict__ x, u16* __restrict__ y, uint8_t* __restrict__ idx,
-                                                              int n, int h, int w, int c8, int ho, int wo) {
-    const long long total = (long long)n * ho * wo * c8;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int cc = (int)(i % c8); long long p = i / c8;
-        const int ox = (int)(p % wo); p /= wo;
-        const int oy = (int)(p % ho); const int nn = (int)(p / ho);
-        F8 best;
-        unsigned char bi[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { best.v[j] = -INFINITY; bi[j] = 0; }
-        bool first = true;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int iy = oy * 2 - 1 + ky, ix = ox * 2 - 1 + kx;
-                if (iy < 0 || iy >= h || ix < 0 || ix >= w) continue;
-                const F8 v = ld8(x + (((long long)nn * h + iy) * w + ix) * (c8 * 8) + cc * 8);
-                const int t = ky * 3 + kx;
-                // ATen: the first in-range element, then strictly greater (or NaN) replaces
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (first || v.v[j] > best.v[j] || v.v[j] != v.v[j]) { best.v[j] = v.v[j]; bi[j] = (unsigned char)t; }
-                first = false;
-            }
-        st8(y + i * 8, best);
-        *reinterpret_cast<uint2*>(idx + i * 8) = make_uint2(bi[0] | (bi[1] << 8) | (bi[2] << 16) | ((unsigned)bi[3] << 24),
-                                                            bi[4] | (bi[5] << 8) | (bi[6] << 16) | ((unsigned)bi[7] << 24));
-    }
-}
-__global__ __launch_bounds__(256) void s16_maxpool_bwd_kernel(const u16* __restrict__ dy, const uint8_t* __restrict__ idx, u16* __restrict__ dx,
-                                                              int n, int h, int w, int c8, int ho, int wo) {
-    const long long total = (long long)n * h * w * c8;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int cc = (int)(i % c8); long long p = i / c8;
-        const int ix = (int)(p % w); p /= w;
-        const int iy = (int)(p % h); const int nn = (int)(p / h);
-        F8 g;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) g.v[j] = 0.f;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const int ny = iy + 1 - ky;
-            if (ny < 0 || (ny & 1)) continue;
-            const int oy = ny >> 1;
-            if (oy >= ho) continue;
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int nx = ix + 1 - kx;
-                if (nx < 0 || (nx & 1)) continue;
-                const int ox = nx >> 1;
-                if (ox >= wo) continue;
-                const long long o = ((((long long)nn * ho + oy) * wo + ox) * c8 + cc) * 8;
-                const uint2 t = *reinterpret_cast<const uint2*>(idx + o);
-                const F8 d = ld8(dy + o);
-                const unsigned me = ky * 3 + kx;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const unsigned tj = ((j < 4 ? t.x : t.y) >> (8 * (j & 3))) & 0xffu;
-                    if (tj == me) g.v[j] += d.v[j];
-                }
-            }
-        }
-        st8(dx + i * 8, g);
-    }
-}
-
 // y[n][c] = scale * sum_p x[n][p][c]   (x row stride ld); y bf16 or fp32 (the ASPP pooled branch keeps its N per-frame vectors
 // in fp32: its BatchNorm normalises over the N frames, whose averages differ by less than a few bf16 steps)
 __global__ __launch_bounds__(256) void s16_sum_rows_kernel(const u16* __restrict__ x, int ld, void* __restrict__ yv, int y_f32, float scale, int p, int c) {
@@ -696,135 +577,6 @@ __global__ __launch_bounds__(256) void s16_sum_rows_kernel(const u16* __restrict
         }
     }
 }
-__global__ __launch_bounds__(256) void s16_bcast_rows_kernel(const void* __restrict__ xv, int x_f32, u16* __restrict__ y, int ld, float scale, int p, int c8, long long total8) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8; i += (long long)gridDim.x * blockDim.x) {
-        const int cc = (int)(i % c8); const long long row = i / c8;
-        const long long n = row / p;
-        F8 v = x_f32 ? ldf8(static_cast<const float*>(xv) + (n * c8 + cc) * 8) : ld8(static_cast<const u16*>(xv) + (n * c8 + cc) * 8);
-        if (scale != 1.f) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v.v[j] *= scale;
-        }
-        st8(y + row * ld + cc * 8, v);
-    }
-}
-
-__device__ __forceinline__ unsigned mix64(unsigned long long z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (unsigned)(z >> 40);                           // 24 bits
-}
-__global__ __launch_bounds__(256) void s16_dropout_kernel(const u16* __restrict__ x, u16* __restrict__ y, long long n8, float p, float scale,
-                                                          unsigned long long seed, const unsigned long long* __restrict__ step) {
-    if (step) seed += *step * 0xD1B54A32D192ED03ull;
-    const unsigned thr = (unsigned)(p * 16777216.0f);
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) {
-        F8 v = ld8(x + i * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v.v[j] = (mix64(seed * 0x100000001B3ull + (unsigned long long)(i * 8 + j)) >= thr) ? v.v[j] * scale : 0.f;
-        st8(y + i * 8, v);
-    }
-}
-
-__global__ __launch_bounds__(256) void s16_relu_fwd_kernel(const u16* __restrict__ x, u16* __restrict__ y, long long n8) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) {
-        F8 v = ld8(x + i * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v.v[j] = fmaxf(v.v[j], 0.f);
-        st8(y + i * 8, v);
-    }
-}
-__global__ __launch_bounds__(256) void s16_relu_bwd_kernel(const u16* __restrict__ dy, const u16* __restrict__ y, u16* __restrict__ dx, long long n8) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) {
-        F8 g = ld8(dy + i * 8);
-        const F8 v = ld8(y + i * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) g.v[j] = v.v[j] > 0.f ? g.v[j] : 0.f;
-        st8(dx + i * 8, g);
-    }
-}
-// out = a * x + b * y
-__global__ __launch_bounds__(256) void s16_axpby_kernel(const u16* __restrict__ x, const u16* __restrict__ y, u16* __restrict__ out, float a, float b, long long n8) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) {
-        F8 u = ld8(x + i * 8);
-        const F8 v = ld8(y + i * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) u.v[j] = a * u.v[j] + b * v.v[j];
-        st8(out + i * 8, u);
-    }
-}
-
-__global__ __launch_bounds__(256) void s16_gate_fwd_kernel(const float* __restrict__ cls, int ncls, const float* __restrict__ ctr,
-                                                           const u16* __restrict__ f, u16* __restrict__ y, float* __restrict__ a_out,
-                                                           int* __restrict__ amax, float weight, int rows, int c) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    float best = sigmoidf_(cls[(long long)row * ncls]);
-    int bi = 0;
-    for (int k = 1; k < ncls; ++k) { const float s = sigmoidf_(cls[(long long)row * ncls + k]); if (s > best) { best = s; bi = k; } }
-    const float cc = sigmoidf_(ctr[row]);
-    const float a = sigmoidf_(weight * best * cc);
-    if (lane == 0) { a_out[row] = a; amax[row] = bi; }
-    for (int i = lane; i < (c >> 3); i += 64) {
-        F8 v = ld8(f + (long long)row * c + i * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v.v[j] *= a;
-        st8(y + (long long)row * c + i * 8, v);
-    }
-}
-__global__ __launch_bounds__(256) void s16_gate_bwd_kernel(const u16* __restrict__ dy, const u16* __restrict__ f, const float* __restrict__ cls, int ncls,
-                                                           const float* __restrict__ ctr, const float* __restrict__ a_in, const int* __restrict__ amax,
-                                                           float weight, u16* __restrict__ df, float* __restrict__ dcls, float* __restrict__ dctr,
-                                                           int rows, int c) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float a = a_in[row];
-    float s = 0.f;
-    for (int i = lane; i < (c >> 3); i += 64) {
-        F8 g = ld8(dy + (long long)row * c + i * 8);
-        const F8 v = ld8(f + (long long)row * c + i * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { s += g.v[j] * v.v[j]; g.v[j] *= a; }
-        st8(df + (long long)row * c + i * 8, g);
-    }
-    const float da = wave_sum(s);
-    if (lane == 0) {
-        const int bi = amax[row];
-        const float m = sigmoidf_(cls[(long long)row * ncls + bi]);
-        const float cc = sigmoidf_(ctr[row]);
-        const float dt = da * a * (1.f - a) * weight;
-        for (int k = 0; k < ncls; ++k) dcls[(long long)row * ncls + k] = (k == bi) ? dt * cc * m * (1.f - m) : 0.f;
-        dctr[row] = dt * m * cc * (1.f - cc);
-    }
-}
-
-__global__ __launch_bounds__(256) void s16_add_frames_kernel(const u16* __restrict__ a, long long afs, const u16* __restrict__ b, long long bfs,
-                                                             u16* __restrict__ dst, long long dfs, long long inner8, long long total8) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8; i += (long long)gridDim.x * blockDim.x) {
-        const long long n = i / inner8, r = i - n * inner8;
-        F8 u = ld8(a + n * afs + r * 8);
-        const F8 v = ld8(b + n * bfs + r * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) u.v[j] += v.v[j];
-        st8(dst + n * dfs + r * 8, u);
-    }
-}
-struct AddN16 { const u16* p[8]; };
-__global__ __launch_bounds__(256) void s16_add_n_kernel(AddN16 in, int k, u16* __restrict__ out, long long n8) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) {
-        F8 a = ld8(in.p[0] + i * 8);
-        for (int j = 1; j < k; ++j) {
-            const F8 b = ld8(in.p[j] + i * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) a.v[e] += b.v[e];
-        }
-        st8(out + i * 8, a);
-    }
-}
 __global__ __launch_bounds__(256) void s16_to_f32_kernel(const u16* __restrict__ x, float* __restrict__ y, long long n8) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) {
         const F8 v = ld8(x + i * 8);
@@ -835,34 +587,14 @@ __global__ __launch_bounds__(256) void s16_to_f32_kernel(const u16* __restrict__
 __global__ __launch_bounds__(256) void s16_from_f32_kernel(const float* __restrict__ x, u16* __restrict__ y, long long n8) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) st8(y + i * 8, ldf8(x + i * 8));
 }
-// batched 2-D transpose of 16-bit elements through a padded LDS tile: dst[b][c][r] = src[b][r][c]
-__global__ __launch_bounds__(256) void s16_transpose2d_kernel(const u16* __restrict__ src, u16* __restrict__ dst, int rows, int cols) {
-    __shared__ u16 tile[64][66];
-    const long long boff = (long long)blockIdx.z * rows * cols;
-    const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    for (int i = ty; i < 64; i += 4) {
-        const int r = r0 + i, c = c0 + tx;
-        tile[i][tx] = (r < rows && c < cols) ? src[boff + (long long)r * cols + c] : (u16)0;
-    }
-    __syncthreads();
-    for (int i = ty; i < 64; i += 4) {
-        const int c = c0 + i, r = r0 + tx;
-        if (c < cols && r < rows) dst[boff + (long long)c * rows + r] = tile[tx][i];
-    }
-}
 
 }  // namespace
-
-#define REQ_C8(c) GLF_REQUIRE((c) > 0 && ((c) % 8) == 0, GLF_ERR_BAD_SHAPE, "channel count must be a positive multiple of 8 (got %d)", (c))
-#define REQ_AL(p, name) GLF_REQUIRE(al16(p), GLF_ERR_BAD_SHAPE, name " must be 16-byte aligned")
-#define REQ_LD(ld, name) GLF_REQUIRE(((ld) % 8) == 0, GLF_ERR_BAD_SHAPE, name " must be a multiple of 8")
 
 extern "C" int glf_s16_colstats(const void* x, int ldx, int rows, int c, double* sums, glf_stream_t s) {
     if (int rc = glf::ensure_init()) return rc;
     GLF_REQUIRE(x && sums, GLF_ERR_NULL, "s16_colstats: null argument");
     GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "s16_colstats: rows must be > 0");
-    REQ_C8(c); REQ_AL(x, "x"); REQ_LD(ldx, "ldx");
+    REQ_C8(c); REQ_AL(x, "x"); REQ_LD8(ldx, "ldx");
     return launch_colreduce16(OpStats16{static_cast<const u16*>(x), ldx}, rows, c, sums, glf::S(s));
 }
 
@@ -873,10 +605,10 @@ extern "C" int glf_s16_bn_apply(const void* x, int ldx, const void* residual, in
     if (int rc = glf::ensure_init()) return rc;
     GLF_REQUIRE(x && y && mean && invstd && gamma && beta, GLF_ERR_NULL, "s16_bn_apply: null argument");
     GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "s16_bn_apply: rows must be > 0");
-    REQ_C8(c); REQ_AL(x, "x"); REQ_AL(y, "y"); REQ_LD(ldx, "ldx"); REQ_LD(ldy, "ldy");
+    REQ_C8(c); REQ_AL(x, "x"); REQ_AL(y, "y"); REQ_LD8(ldx, "ldx"); REQ_LD8(ldy, "ldy");
     GLF_REQUIRE(c <= APPLY_MAX_C, GLF_ERR_UNSUPPORTED, "s16_bn_apply: C must be <= %d", APPLY_MAX_C);
     GLF_REQUIRE((running_mean == nullptr) == (running_var == nullptr), GLF_ERR_NULL, "s16_bn_apply: running_mean/var must both be set or both NULL");
-    if (residual) { REQ_AL(residual, "residual"); REQ_LD(ldr, "ldr"); }
+    if (residual) { REQ_AL(residual, "residual"); REQ_LD8(ldr, "ldr"); }
     const long long total8 = (long long)rows * (c / 8);
     hipLaunchKernelGGL(s16_bn_apply_kernel, dim3(stream_grid(total8, 256)), dim3(256), (size_t)2 * c * sizeof(float), glf::S(s),
                        static_cast<const u16*>(x), ldx, static_cast<const u16*>(residual), ldr, static_cast<u16*>(y), ldy, sums, rows, c, eps, momentum,
@@ -893,10 +625,10 @@ extern "C" int glf_s16_bn_bwd(const void* dy, int lddy, const void* dy2, int ldd
     GLF_REQUIRE(dy && x && mean && invstd && gamma && dx && sums, GLF_ERR_NULL, "s16_bn_bwd: null argument");
     GLF_REQUIRE(!relu || beta || relu_mask, GLF_ERR_NULL, "s16_bn_bwd: relu != 0 needs relu_mask or beta (to recompute the sign from x)");
     GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "s16_bn_bwd: rows must be > 0");
-    REQ_C8(c); REQ_AL(dy, "dy"); REQ_AL(x, "x"); REQ_AL(dx, "dx"); REQ_LD(lddy, "lddy"); REQ_LD(ldx, "ldx"); REQ_LD(lddx, "lddx");
+    REQ_C8(c); REQ_AL(dy, "dy"); REQ_AL(x, "x"); REQ_AL(dx, "dx"); REQ_LD8(lddy, "lddy"); REQ_LD8(ldx, "ldx"); REQ_LD8(lddx, "lddx");
     GLF_REQUIRE(c <= APPLY_MAX_C, GLF_ERR_UNSUPPORTED, "s16_bn_bwd: C must be <= %d", APPLY_MAX_C);
-    if (dres) { REQ_AL(dres, "dres"); REQ_LD(lddres, "lddres"); }
-    if (dy2) { REQ_AL(dy2, "dy2"); REQ_LD(lddy2, "lddy2"); }
+    if (dres) { REQ_AL(dres, "dres"); REQ_LD8(lddres, "lddres"); }
+    if (dy2) { REQ_AL(dy2, "dy2"); REQ_LD8(lddy2, "lddy2"); }
     const OpBnBwd16 op{static_cast<const u16*>(dy), lddy, static_cast<const u16*>(dy2), lddy2, static_cast<const u16*>(x), ldx, mean, invstd, gamma, beta,
                        relu, relu_mask, c / 8};
     if (int rc = launch_bnbwd_reduce16(op, rows, c, sums, glf::S(s))) return rc;
@@ -912,7 +644,7 @@ extern "C" int glf_s16_colsum(const void* dy, int lddy, float* db, int rows, int
     if (int rc = glf::ensure_init()) return rc;
     GLF_REQUIRE(dy && db && workspace, GLF_ERR_NULL, "s16_colsum: null argument");
     GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "s16_colsum: rows must be > 0");
-    REQ_C8(c); REQ_AL(dy, "dy"); REQ_LD(lddy, "lddy");
+    REQ_C8(c); REQ_AL(dy, "dy"); REQ_LD8(lddy, "lddy");
     hipError_t e = hipMemsetAsync(workspace, 0, (size_t)2 * c * sizeof(double), glf::S(s));
     if (e != hipSuccess) return glf::fail(GLF_ERR_LAUNCH, "s16_colsum: hipMemsetAsync: %s", hipGetErrorString(e));
     if (int rc = launch_colreduce16(OpColsum16{static_cast<const u16*>(dy), lddy}, rows, c, workspace, glf::S(s))) return rc;
@@ -957,132 +689,15 @@ extern "C" int glf_s16_bn_res_ln_bwd(const void* dz, const void* w, const void* 
     return glf::check_launch("s16_ln_param_finalize");
 }
 
-extern "C" int glf_s16_maxpool3x3s2_fwd(const void* x, void* y, uint8_t* idx, int n, int h, int w, int c, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(x && y && idx, GLF_ERR_NULL, "s16_maxpool_fwd: null argument");
-    GLF_REQUIRE(n > 0 && h > 0 && w > 0, GLF_ERR_BAD_SHAPE, "s16_maxpool_fwd: bad extents");
-    REQ_C8(c); REQ_AL(x, "x"); REQ_AL(y, "y");
-    const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
-    const long long total = (long long)n * ho * wo * (c / 8);
-    hipLaunchKernelGGL(s16_maxpool_fwd_kernel, dim3(stream_grid(total, 256)), dim3(256), 0, glf::S(s), static_cast<const u16*>(x), static_cast<u16*>(y), idx,
-                       n, h, w, c / 8, ho, wo);
-    return glf::check_launch("s16_maxpool_fwd");
-}
-extern "C" int glf_s16_maxpool3x3s2_bwd(const void* dy, const uint8_t* idx, void* dx, int n, int h, int w, int c, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(dy && dx && idx, GLF_ERR_NULL, "s16_maxpool_bwd: null argument");
-    GLF_REQUIRE(n > 0 && h > 0 && w > 0, GLF_ERR_BAD_SHAPE, "s16_maxpool_bwd: bad extents");
-    REQ_C8(c); REQ_AL(dy, "dy"); REQ_AL(dx, "dx");
-    const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
-    const long long total = (long long)n * h * w * (c / 8);
-    hipLaunchKernelGGL(s16_maxpool_bwd_kernel, dim3(stream_grid(total, 256)), dim3(256), 0, glf::S(s), static_cast<const u16*>(dy), idx, static_cast<u16*>(dx),
-                       n, h, w, c / 8, ho, wo);
-    return glf::check_launch("s16_maxpool_bwd");
-}
-
 extern "C" int glf_s16_sum_rows(const void* x, int ldx, void* y, int y_dtype, float scale, int n, int p, int c, glf_stream_t s) {
     if (int rc = glf::ensure_init()) return rc;
     GLF_REQUIRE(x && y, GLF_ERR_NULL, "s16_sum_rows: null argument");
     GLF_REQUIRE(n > 0 && p > 0, GLF_ERR_BAD_SHAPE, "s16_sum_rows: bad extents");
-    REQ_C8(c); REQ_AL(x, "x"); REQ_LD(ldx, "ldx");
+    REQ_C8(c); REQ_AL(x, "x"); REQ_LD8(ldx, "ldx");
     GLF_REQUIRE(y_dtype == GLF_DT_F32 || y_dtype == GLF_DT_BF16, GLF_ERR_UNSUPPORTED, "s16_sum_rows: y_dtype must be GLF_DT_F32 or GLF_DT_BF16");
     hipLaunchKernelGGL(s16_sum_rows_kernel, dim3((c + 255) / 256, n), dim3(256), 0, glf::S(s), static_cast<const u16*>(x), ldx, y, y_dtype == GLF_DT_F32, scale, p, c);
     return glf::check_launch("s16_sum_rows");
 }
-extern "C" int glf_s16_bcast_rows(const void* x, int x_dtype, void* y, int ldy, float scale, int n, int p, int c, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(x && y, GLF_ERR_NULL, "s16_bcast_rows: null argument");
-    GLF_REQUIRE(n > 0 && p > 0, GLF_ERR_BAD_SHAPE, "s16_bcast_rows: bad extents");
-    REQ_C8(c); REQ_AL(x, "x"); REQ_AL(y, "y"); REQ_LD(ldy, "ldy");
-    const long long total8 = (long long)n * p * (c / 8);
-    GLF_REQUIRE(x_dtype == GLF_DT_F32 || x_dtype == GLF_DT_BF16, GLF_ERR_UNSUPPORTED, "s16_bcast_rows: x_dtype must be GLF_DT_F32 or GLF_DT_BF16");
-    hipLaunchKernelGGL(s16_bcast_rows_kernel, dim3(stream_grid(total8, 256)), dim3(256), 0, glf::S(s), x, x_dtype == GLF_DT_F32, static_cast<u16*>(y), ldy,
-                       scale, p, c / 8, total8);
-    return glf::check_launch("s16_bcast_rows");
-}
-
-extern "C" int glf_s16_dropout(const void* x, void* y, int64_t numel, float p, uint64_t seed, const uint64_t* step_counter, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(x && y, GLF_ERR_NULL, "s16_dropout: null argument");
-    GLF_REQUIRE(numel > 0 && numel % 8 == 0 && p >= 0.f && p < 1.f, GLF_ERR_BAD_SHAPE, "s16_dropout: numel must be a positive multiple of 8, 0 <= p < 1");
-    REQ_AL(x, "x"); REQ_AL(y, "y");
-    hipLaunchKernelGGL(s16_dropout_kernel, dim3(stream_grid(numel / 8, 256)), dim3(256), 0, glf::S(s), static_cast<const u16*>(x), static_cast<u16*>(y),
-                       (long long)(numel / 8), p, 1.0f / (1.0f - p), (unsigned long long)seed, reinterpret_cast<const unsigned long long*>(step_counter));
-    return glf::check_launch("s16_dropout");
-}
-
-extern "C" int glf_s16_relu_fwd(const void* x, void* y, int64_t numel, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(x && y, GLF_ERR_NULL, "s16_relu_fwd: null argument");
-    GLF_REQUIRE(numel > 0 && numel % 8 == 0, GLF_ERR_BAD_SHAPE, "s16_relu_fwd: numel must be a positive multiple of 8");
-    REQ_AL(x, "x"); REQ_AL(y, "y");
-    hipLaunchKernelGGL(s16_relu_fwd_kernel, dim3(stream_grid(numel / 8, 256)), dim3(256), 0, glf::S(s), static_cast<const u16*>(x), static_cast<u16*>(y), (long long)(numel / 8));
-    return glf::check_launch("s16_relu_fwd");
-}
-extern "C" int glf_s16_relu_bwd(const void* dy, const void* y, void* dx, int64_t numel, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(dy && y && dx, GLF_ERR_NULL, "s16_relu_bwd: null argument");
-    GLF_REQUIRE(numel > 0 && numel % 8 == 0, GLF_ERR_BAD_SHAPE, "s16_relu_bwd: numel must be a positive multiple of 8");
-    REQ_AL(dy, "dy"); REQ_AL(y, "y"); REQ_AL(dx, "dx");
-    hipLaunchKernelGGL(s16_relu_bwd_kernel, dim3(stream_grid(numel / 8, 256)), dim3(256), 0, glf::S(s), static_cast<const u16*>(dy), static_cast<const u16*>(y),
-                       static_cast<u16*>(dx), (long long)(numel / 8));
-    return glf::check_launch("s16_relu_bwd");
-}
-extern "C" int glf_s16_axpby(const void* x, const void* y, void* out, float a, float b, int64_t numel, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(x && y && out, GLF_ERR_NULL, "s16_axpby: null argument");
-    GLF_REQUIRE(numel > 0 && numel % 8 == 0, GLF_ERR_BAD_SHAPE, "s16_axpby: numel must be a positive multiple of 8");
-    REQ_AL(x, "x"); REQ_AL(y, "y"); REQ_AL(out, "out");
-    hipLaunchKernelGGL(s16_axpby_kernel, dim3(stream_grid(numel / 8, 256)), dim3(256), 0, glf::S(s), static_cast<const u16*>(x), static_cast<const u16*>(y),
-                       static_cast<u16*>(out), a, b, (long long)(numel / 8));
-    return glf::check_launch("s16_axpby");
-}
-
-extern "C" int glf_s16_gate_fwd(const float* cls, int ncls, const float* ctr, const void* f, void* y, float* a, int32_t* argmax, float weight,
-                                int rows, int c, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(cls && ctr && f && y && a && argmax, GLF_ERR_NULL, "s16_gate_fwd: null argument");
-    GLF_REQUIRE(rows > 0 && ncls > 0, GLF_ERR_BAD_SHAPE, "s16_gate_fwd: bad extents");
-    REQ_C8(c); REQ_AL(f, "f"); REQ_AL(y, "y");
-    hipLaunchKernelGGL(s16_gate_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, glf::S(s), cls, ncls, ctr, static_cast<const u16*>(f), static_cast<u16*>(y), a,
-                       argmax, weight, rows, c);
-    return glf::check_launch("s16_gate_fwd");
-}
-extern "C" int glf_s16_gate_bwd(const void* dy, const void* f, const float* cls, int ncls, const float* ctr, const float* a, const int32_t* argmax,
-                                float weight, void* df, float* dcls, float* dctr, int rows, int c, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(dy && f && cls && ctr && a && argmax && df && dcls && dctr, GLF_ERR_NULL, "s16_gate_bwd: null argument");
-    GLF_REQUIRE(rows > 0 && ncls > 0, GLF_ERR_BAD_SHAPE, "s16_gate_bwd: bad extents");
-    REQ_C8(c); REQ_AL(dy, "dy"); REQ_AL(f, "f"); REQ_AL(df, "df");
-    hipLaunchKernelGGL(s16_gate_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, glf::S(s), static_cast<const u16*>(dy), static_cast<const u16*>(f), cls, ncls,
-                       ctr, a, argmax, weight, static_cast<u16*>(df), dcls, dctr, rows, c);
-    return glf::check_launch("s16_gate_bwd");
-}
-
-extern "C" int glf_s16_add_frames(const void* a, int64_t a_fs, const void* b, int64_t b_fs, void* dst, int64_t dst_fs, int n, int64_t inner,
-                                  glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(a && b && dst, GLF_ERR_NULL, "s16_add_frames: null argument");
-    GLF_REQUIRE(n > 0 && inner > 0 && inner % 8 == 0 && a_fs % 8 == 0 && b_fs % 8 == 0 && dst_fs % 8 == 0, GLF_ERR_BAD_SHAPE,
-                "s16_add_frames: inner and the frame strides must be multiples of 8");
-    REQ_AL(a, "a"); REQ_AL(b, "b"); REQ_AL(dst, "dst");
-    const long long total8 = (long long)n * (inner / 8);
-    hipLaunchKernelGGL(s16_add_frames_kernel, dim3(stream_grid(total8, 256)), dim3(256), 0, glf::S(s), static_cast<const u16*>(a), (long long)a_fs,
-                       static_cast<const u16*>(b), (long long)b_fs, static_cast<u16*>(dst), (long long)dst_fs, (long long)(inner / 8), total8);
-    return glf::check_launch("s16_add_frames");
-}
-extern "C" int glf_s16_add_n(const void* const* inputs, int k, void* out, int64_t numel, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(inputs && out, GLF_ERR_NULL, "s16_add_n: null argument");
-    GLF_REQUIRE(k >= 1 && k <= 8 && numel > 0 && numel % 8 == 0, GLF_ERR_BAD_SHAPE, "s16_add_n: 1 <= k <= 8, numel a positive multiple of 8");
-    AddN16 in;
-    for (int i = 0; i < 8; ++i) in.p[i] = static_cast<const u16*>(inputs[i < k ? i : 0]);
-    for (int i = 0; i < k; ++i) { GLF_REQUIRE(inputs[i], GLF_ERR_NULL, "s16_add_n: null input"); REQ_AL(inputs[i], "input"); }
-    REQ_AL(out, "out");
-    hipLaunchKernelGGL(s16_add_n_kernel, dim3(stream_grid(numel / 8, 256)), dim3(256), 0, glf::S(s), in, k, static_cast<u16*>(out), (long long)(numel / 8));
-    return glf::check_launch("s16_add_n");
-}
-
 extern "C" int glf_s16_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t numel, glf_stream_t s) {
     if (int rc = glf::ensure_init()) return rc;
     GLF_REQUIRE(src && dst, GLF_ERR_NULL, "s16_cast: null argument");
@@ -1097,13 +712,4 @@ extern "C" int glf_s16_cast(const void* src, int src_dtype, void* dst, int dst_d
     else
         return glf::fail(GLF_ERR_UNSUPPORTED, "s16_cast: built for bf16 -> f32 and f32 -> bf16");
     return glf::check_launch("s16_cast");
-}
-
-extern "C" int glf_s16_transpose2d(const void* src, void* dst, int rows, int cols, int batch, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(src && dst, GLF_ERR_NULL, "s16_transpose2d: null argument");
-    GLF_REQUIRE(rows > 0 && cols > 0 && batch > 0 && batch <= 65535, GLF_ERR_BAD_SHAPE, "s16_transpose2d: bad extents");
-    hipLaunchKernelGGL(s16_transpose2d_kernel, dim3((cols + 63) / 64, (rows + 63) / 64, batch), dim3(256), 0, glf::S(s), static_cast<const u16*>(src),
-                       static_cast<u16*>(dst), rows, cols);
-    return glf::check_launch("s16_transpose2d");
 }

@@ -25,6 +25,14 @@ from ._lib import GemmParams, WeightJob, WJ_AMAX, WJ_COPY, WJ_PACK, WJ_PASSES, W
 # ----------------------------------------------------------------------------------------
 # small helpers
 # ----------------------------------------------------------------------------------------
+BF = torch.bfloat16
+DT_F32, DT_BF16 = 0, 1                  # GLF_DT_* of include/glfusion.h
+
+
+def _is16(t) -> bool:
+    return isinstance(t, torch.Tensor) and t.dtype == BF
+
+
 def _p(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -33,11 +41,14 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _chk(t: torch.Tensor, name: str = "tensor") -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-        raise RuntimeError(
-            f"glfusion_amd: {name} must be a CUDA(HIP) float32 tensor (got "
-            f"{getattr(t, 'device', None)}, {getattr(t, 'dtype', None)}). The engine has no CPU fallback.")
+def _chk(t: torch.Tensor, name: str = "tensor", dtype: Optional[torch.dtype] = torch.float32) -> torch.Tensor:
+    """t must be a CUDA tensor of `dtype`; dtype=None: of either storage dtype (the streaming nodes serve fp32 and bf16 alike)."""
+    if dtype is None:
+        dtype = BF if _is16(t) else torch.float32
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+        kind = "bfloat16 tensor in 16-bit storage mode" if dtype == BF else "float32 tensor"
+        raise RuntimeError(f"glfusion_amd: {name} must be a CUDA(HIP) {kind} (got "
+                           f"{getattr(t, 'device', None)}, {getattr(t, 'dtype', None)}). The engine has no CPU fallback.")
     return t
 
 
@@ -64,6 +75,30 @@ def zero_(t: torch.Tensor) -> torch.Tensor:
     if t.numel():
         check(lib.glf_zero(_p(t), t.numel() * t.element_size(), _stream()), "zero")
     return t
+
+
+def _dt(t: torch.Tensor) -> int:
+    return DT_BF16 if t.dtype == BF else DT_F32
+
+
+# The streaming ops between the contractions have one entry point per storage dtype: glf_<name> for fp32, glf_s16_<name> for bf16,
+# with the same argument list -- except these, given here as (bf16 name, arguments) in terms of the fp32 call's arguments:
+# the 16-bit row sums / broadcasts take the dtype of their fp32-or-bf16 side, and glf_copy_frames moves 16-byte pieces counted in
+# floats (a bf16 extent is half as long).
+_S16_FORM = {
+    "avgpool_fwd": lambda x, y, n, p, c: ("s16_sum_rows", (x, c, y, _dt(y), 1.0 / p, n, p, c)),
+    "sum_rows_fwd": lambda x, ld, y, scale, n, p, c: ("s16_sum_rows", (x, ld, y, _dt(y), scale, n, p, c)),
+    "bcast_rows_scaled": lambda x, y, ld, scale, n, p, c: ("s16_bcast_rows", (x, _dt(x), y, ld, scale, n, p, c)),
+    "copy_frames": lambda src, sfs, dst, dfs, n, inner: ("copy_frames", (src, sfs // 2, dst, dfs // 2, n, inner // 2)),
+}
+
+
+def _launch(name: str, ref: torch.Tensor, *args) -> None:
+    """Launch streaming op `name` (named after its fp32 entry point glf_<name>) for the storage dtype of `ref` on the current
+    stream.  Tensors are passed as tensors.  The ONE place where a node's dtype picks its kernel."""
+    if _is16(ref):
+        name, args = _S16_FORM[name](*args) if name in _S16_FORM else ("s16_" + name, args)
+    check(getattr(lib, "glf_" + name)(*[_p(a) if isinstance(a, torch.Tensor) else a for a in args], _stream()), name)
 
 
 def to_nhwc(x: torch.Tensor) -> torch.Tensor:
@@ -134,10 +169,6 @@ def s16() -> bool:
 def act_dtype() -> torch.dtype:
     """dtype of the activations the engine keeps in HBM under the current precision."""
     return torch.bfloat16 if _S16[0] else torch.float32
-
-
-def _is16(t) -> bool:
-    return isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16
 
 
 # bench.py sets this to a list to time every contraction launch with HIP events on the launch stream
@@ -495,8 +526,8 @@ def colmax_slot(c: int, dev) -> torch.Tensor:
 def amax_bound(t: torch.Tensor, srcs: Sequence[Optional[torch.Tensor]], scale: float = 1.0, sum_: bool = False) -> None:
     """Attach to t an upper bound of its maximum derived from the maxima of the tensors it was made from (glf_amax_combine: one
     tiny launch per pair, no pass over the data): scale * max(srcs) or scale * sum(srcs).  Does nothing unless every source's
-    maximum is known (t is then measured on first use, as before)."""
-    if _PREC[0] < 2:
+    maximum is known (t is then measured on first use, as before).  fp32 storage only: bf16 tensors carry no maxima."""
+    if _PREC[0] < 2 or _is16(t):
         return
     ams = [getattr(x, "_glf_amax", None) for x in srcs]
     ams = [h[2] if (h is not None and h[0] == x._version and h[1] == x.data_ptr()) else None for h, x in zip(ams, srcs)]
@@ -1241,24 +1272,25 @@ class output_into:
         return False
 
 
-def _take_out(shape, device):
-    """(output tensor, row stride, shared amax slot or None) for a [..., C] result of `shape`."""
+def _take_out(shape, device, dtype=torch.float32):
+    """(output tensor, row stride, shared amax slot or None) for a [..., C] result of `shape`: the pending output_into view when
+    it matches, a fresh tensor otherwise.  Only fp32 storage carries maxima."""
     item = _OUT_VIEW[0]
-    if item is not None and tuple(item[0].shape) == tuple(shape) and item[0].stride(-1) == 1:
+    if item is not None and tuple(item[0].shape) == tuple(shape) and item[0].stride(-1) == 1 and item[0].dtype == dtype:
         _OUT_VIEW[0] = None
-        return item[0], int(item[0].stride(-2)), item[1]
-    return torch.empty(tuple(shape), dtype=torch.float32, device=device), int(shape[-1]), None
+        return item[0], int(item[0].stride(-2)), item[1] if dtype == torch.float32 else None
+    return torch.empty(tuple(shape), dtype=dtype, device=device), int(shape[-1]), None
 
 
 def _rows_view(t: torch.Tensor):
     """(tensor, row stride) for reading a [..., C] tensor as rows: contiguous, or a column slice of a wider
-    channels-last buffer (uniform row stride); anything else is copied."""
+    channels-last buffer (uniform row stride; bf16: one the 16-byte accesses can walk); anything else is copied."""
     if t.is_contiguous():
         return t, int(t.shape[-1])
     if t.dim() >= 2 and t.stride(-1) == 1:
         ld = int(t.stride(-2))
         ok = all(t.stride(d) == t.stride(d + 1) * t.shape[d + 1] for d in range(t.dim() - 2))
-        if ok and ld >= t.shape[-1]:
+        if ok and ld >= t.shape[-1] and (not _is16(t) or (ld % 8 == 0 and t.data_ptr() % 16 == 0)):
             return t, ld
     t = t.contiguous()
     return t, int(t.shape[-1])
@@ -1444,9 +1476,9 @@ def batch_norm_act(x, bn: torch.nn.modules.batchnorm._BatchNorm, relu: bool, res
 class ReluFn(Function):
     @staticmethod
     def forward(ctx, x):
-        x = _contig(_chk(x, "relu input"))
+        x = _contig(_chk(x, "relu input", None))
         y = torch.empty_like(x)
-        check(lib.glf_relu_fwd(_p(x), _p(y), x.numel(), _stream()), "relu_fwd")
+        _launch("relu_fwd", x, x, y, x.numel())
         ctx.save_for_backward(y)
         return y
 
@@ -1456,23 +1488,20 @@ class ReluFn(Function):
         (y,) = ctx.saved_tensors
         dy = _contig(dy)
         dx = torch.empty_like(dy)
-        check(lib.glf_relu_bwd(_p(dy), _p(y), _p(dx), dy.numel(), _stream()), "relu_bwd")
+        _launch("relu_bwd", dy, dy, y, dx, dy.numel())
         return dx
 
 
 def relu(x):
-    if _is16(x):
-        from . import ops16
-        return ops16.Relu16Fn.apply(x)
     return ReluFn.apply(x)
 
 
 class DropoutFn(Function):
     @staticmethod
     def forward(ctx, x, p: float, seed: int):
-        x = _contig(_chk(x, "dropout input"))
+        x = _contig(_chk(x, "dropout input", None))
         y = torch.empty_like(x)
-        check(lib.glf_dropout(_p(x), _p(y), x.numel(), p, seed, _p(step_counter(x.device)), _stream()), "dropout")
+        _launch("dropout", x, x, y, x.numel(), p, seed, step_counter(x.device))
         amax_bound(y, [x], scale=1.0 / (1.0 - p))          # kept elements are scaled by 1 / (1 - p)
         ctx.cfg = (p, seed)
         return y
@@ -1483,7 +1512,7 @@ class DropoutFn(Function):
         p, seed = ctx.cfg
         dy = _contig(dy)
         dx = torch.empty_like(dy)
-        check(lib.glf_dropout(_p(dy), _p(dx), dy.numel(), p, seed, _p(step_counter(dy.device)), _stream()), "dropout_bwd")
+        _launch("dropout", dy, dy, dx, dy.numel(), p, seed, step_counter(dy.device))
         return dx, None, None
 
 
@@ -1493,21 +1522,18 @@ def dropout(x, p: float, training: bool):
     if p >= 1.0:
         raise RuntimeError("dropout p must be < 1")
     seed = int(torch.empty((), dtype=torch.int64).random_(0, 2 ** 62).item())   # host RNG: no device sync
-    if _is16(x):
-        from . import ops16
-        return ops16.Dropout16Fn.apply(x, float(p), seed)
     return DropoutFn.apply(x, float(p), seed)
 
 
 class MaxPool3x3s2Fn(Function):
     @staticmethod
     def forward(ctx, x):
-        x = _contig(_chk(x, "maxpool input"))
+        x = _contig(_chk(x, "maxpool input", None))
         n, h, w, c = x.shape
         ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-        y = torch.empty(n, ho, wo, c, dtype=torch.float32, device=x.device)
+        y = torch.empty(n, ho, wo, c, dtype=x.dtype, device=x.device)
         idx = torch.empty(n, ho, wo, c, dtype=torch.uint8, device=x.device)
-        check(lib.glf_maxpool3x3s2_fwd(_p(x), _p(y), _p(idx), n, h, w, c, _stream()), "maxpool_fwd")
+        _launch("maxpool3x3s2_fwd", x, x, y, idx, n, h, w, c)
         amax_bound(y, [x])                                  # a window maximum never exceeds the input's largest magnitude
         ctx.save_for_backward(idx)
         ctx.cfg = (n, h, w, c)
@@ -1519,78 +1545,71 @@ class MaxPool3x3s2Fn(Function):
         (idx,) = ctx.saved_tensors
         n, h, w, c = ctx.cfg
         dy = _contig(dy)
-        dx = torch.empty(n, h, w, c, dtype=torch.float32, device=dy.device)
-        check(lib.glf_maxpool3x3s2_bwd(_p(dy), _p(idx), _p(dx), n, h, w, c, _stream()), "maxpool_bwd")
+        dx = torch.empty(n, h, w, c, dtype=dy.dtype, device=dy.device)
+        _launch("maxpool3x3s2_bwd", dy, dy, idx, dx, n, h, w, c)
         return dx
 
 
 def maxpool3x3s2(x):
-    if _is16(x):
-        from . import ops16
-        return ops16.MaxPool16Fn.apply(x)
     return MaxPool3x3s2Fn.apply(x)
 
 
 class AvgPoolFn(Function):
-    """AdaptiveAvgPool2d(1): [N,H,W,C] -> [N,1,1,C]."""
+    """AdaptiveAvgPool2d(1): [N,H,W,C] -> fp32 [N,1,1,C].  From a bf16 map too: the ASPP pooled branch (deeplabv3.py:123-135) stays
+    fp32 up to its broadcast -- its BatchNorm normalises over the N per-frame averages, which differ by less than a few bf16 steps."""
 
     @staticmethod
     def forward(ctx, x):
-        x = _contig(_chk(x, "avgpool input"))
+        x = _contig(_chk(x, "avgpool input", None))
         n, h, w, c = x.shape
         y = torch.empty(n, 1, 1, c, dtype=torch.float32, device=x.device)
-        check(lib.glf_avgpool_fwd(_p(x), _p(y), n, h * w, c, _stream()), "avgpool_fwd")
-        ctx.cfg = (n, h, w, c)
+        _launch("avgpool_fwd", x, x, y, n, h * w, c)
+        ctx.cfg = (n, h, w, c, x.dtype)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        n, h, w, c = ctx.cfg
+        n, h, w, c, xdt = ctx.cfg
         dy = _contig(dy)
-        dx = torch.empty(n, h, w, c, dtype=torch.float32, device=dy.device)
-        check(lib.glf_bcast_rows_scaled(_p(dy), _p(dx), c, 1.0 / (h * w), n, h * w, c, _stream()), "avgpool_bwd")
+        dx = torch.empty(n, h, w, c, dtype=xdt, device=dy.device)
+        _launch("bcast_rows_scaled", dx, dy, dx, c, 1.0 / (h * w), n, h * w, c)
         return dx
 
 
 def global_avgpool(x):
-    if _is16(x):
-        from . import ops16
-        return ops16.AvgPool16Fn.apply(x)
     return AvgPoolFn.apply(x)
 
 
 class BroadcastFn(Function):
-    """bilinear up-sampling from a 1x1 map == broadcast: [N,1,1,C] -> [N,H,W,C]."""
+    """bilinear up-sampling from a 1x1 map == broadcast: [N,1,1,C] -> [N,H,W,C] (into the pending output view).  Under 16-bit storage
+    the input is fp32 (the pooled branch) or bf16 and the output bf16."""
 
     @staticmethod
     def forward(ctx, x, h: int, w: int):
-        x = _contig(_chk(x, "broadcast input"))
+        x = _contig(_chk(x, "broadcast input", None))
         n, c = x.shape[0], x.shape[-1]
-        y, ldy, shared = _take_out((n, h, w, c), x.device)
-        check(lib.glf_bcast_rows_fwd(_p(x), _p(y), ldy, n, h * w, c, _stream()), "bcast_rows")
+        y, ldy, shared = _take_out((n, h, w, c), x.device, BF if _S16[0] else x.dtype)
+        _launch("bcast_rows_scaled", y, x, y, ldy, 1.0, n, h * w, c)
         if shared is not None:                   # the broadcast repeats x: its maximum is the source's
             src = amax_of(x)
             if src is not None:
                 torch.maximum(shared, src, out=shared)
             set_amax(y, shared)
-        ctx.cfg = (n, h, w, c)
+        ctx.cfg = (n, h, w, c, x.dtype)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        n, h, w, c = ctx.cfg
+        n, h, w, c, xdt = ctx.cfg
         dy, lddy = _rows_view(dy)
-        dx = torch.empty(n, 1, 1, c, dtype=torch.float32, device=dy.device)
-        check(lib.glf_sum_rows_fwd(_p(dy), lddy, _p(dx), 1.0, n, h * w, c, _stream()), "bcast_rows_bwd")
+        dx = torch.empty(n, 1, 1, c, dtype=xdt, device=dy.device)
+        _launch("sum_rows_fwd", dy, dy, lddy, dx, 1.0, n, h * w, c)
         return dx, None, None
 
 
 def broadcast_hw(x, h: int, w: int):
-    if _is16(x) or _S16[0]:             # 16-bit storage: the pooled branch arrives in fp32 and is broadcast into the bf16 buffer
-        from . import ops16
-        return ops16.Broadcast16Fn.apply(x, h, w)
     return BroadcastFn.apply(x, h, w)
 
 
@@ -1625,15 +1644,13 @@ class FanOutFn(Function):
             a = live[0]
             a._glf_addend = live[1]
             return a, None, None
-        if _is16(live[0]):
-            from . import ops16
-            return ops16.add_n16(live), None, None
         out = torch.empty_like(live[0])
         n = out.numel()
-        if n % 4 != 0 or any(d.shape != out.shape for d in live) or len(live) > 8:
-            raise RuntimeError("fan_out: gradients must share one shape with numel % 4 == 0 (<= 8 branches)")
+        w = 8 if _is16(out) else 4                # elements per 16-byte access
+        if n % w != 0 or any(d.shape != out.shape for d in live) or len(live) > 8:
+            raise RuntimeError(f"fan_out: gradients must share one shape with numel % {w} == 0 (<= 8 branches)")
         arr = (C.c_void_p * len(live))(*[d.data_ptr() for d in live])
-        check(lib.glf_add_n(arr, len(live), _p(out), n, _stream()), "add_n")
+        _launch("add_n", out, arr, len(live), out, n)
         return out, None, None
 
 
@@ -1764,14 +1781,14 @@ def parallel_sections(fns):
 # local gate (ours.py:1802-1816)
 # ----------------------------------------------------------------------------------------
 def _gate_forward(ctx, cls, ctr, f, weight: float):
-    cls, ctr, f = _contig(_chk(cls, "cls")), _contig(_chk(ctr, "ctr")), _contig(_chk(f, "f4"))
+    cls, ctr, f = _contig(_chk(cls, "cls")), _contig(_chk(ctr, "ctr")), _contig(_chk(f, "f4", None))
     c = f.shape[-1]
     rows = f.numel() // c
     ncls = cls.shape[-1]
     y = torch.empty_like(f)
     a = torch.empty(rows, dtype=torch.float32, device=f.device)
     am = torch.empty(rows, dtype=torch.int32, device=f.device)
-    check(lib.glf_gate_fwd(_p(cls), ncls, _p(ctr), _p(f), _p(y), _p(a), _p(am), weight, rows, c, _stream()), "gate_fwd")
+    _launch("gate_fwd", f, cls, ncls, ctr, f, y, a, am, weight, rows, c)
     amax_bound(y, [f])                                      # y = f * a with a in (0, 1)
     ctx.save_for_backward(cls, ctr, f, a, am)
     ctx.cfg = (rows, c, ncls, weight)
@@ -1792,15 +1809,11 @@ class GateFn(Function):
         df = torch.empty_like(f)
         dcls = torch.empty_like(cls)
         dctr = torch.empty_like(ctr)
-        check(lib.glf_gate_bwd(_p(dy), _p(f), _p(cls), ncls, _p(ctr), _p(a), _p(am), weight, _p(df), _p(dcls), _p(dctr),
-                               rows, c, _stream()), "gate_bwd")
+        _launch("gate_bwd", f, dy, f, cls, ncls, ctr, a, am, weight, df, dcls, dctr, rows, c)
         return dcls, dctr, df, None
 
 
 def local_gate(cls_logits, ctr_logits, f4, weight: float):
-    if _is16(f4):
-        from . import ops16
-        return ops16.Gate16Fn.apply(cls_logits, ctr_logits, f4, float(weight))[0]
     return GateFn.apply(cls_logits, ctr_logits, f4, float(weight))
 
 
@@ -1809,11 +1822,12 @@ class AxpbyFn(Function):
 
     @staticmethod
     def forward(ctx, x, y, a: float, b: float):
-        x, y = _contig(_chk(x, "x")), _contig(_chk(y, "y"))
+        x = _contig(_chk(x, "x", None))
+        y = _contig(_chk(y, "y", x.dtype))
         if x.shape != y.shape:
             raise RuntimeError("axpby: shapes differ")
         out = torch.empty_like(x)
-        check(lib.glf_axpby(_p(x), _p(y), _p(out), a, b, x.numel(), _stream()), "axpby")
+        _launch("axpby", x, x, y, out, a, b, x.numel())
         ctx.ab = (a, b)
         return out
 
@@ -1822,21 +1836,17 @@ class AxpbyFn(Function):
     def backward(ctx, d):
         a, b = ctx.ab
         d = _contig(d)
-        zero = d                                   # a*d + 0*d
         dx = dy = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(d)
-            check(lib.glf_axpby(_p(d), _p(zero), _p(dx), a, 0.0, d.numel(), _stream()), "axpby_bwd")
+            _launch("axpby", d, d, d, dx, a, 0.0, d.numel())          # a*d + 0*d
         if ctx.needs_input_grad[1]:
             dy = torch.empty_like(d)
-            check(lib.glf_axpby(_p(d), _p(zero), _p(dy), b, 0.0, d.numel(), _stream()), "axpby_bwd")
+            _launch("axpby", d, d, d, dy, b, 0.0, d.numel())
         return dx, dy, None, None
 
 
 def axpby(x, y, a: float, b: float):
-    if _is16(x):
-        from . import ops16
-        return ops16.Axpby16Fn.apply(x, y, float(a), float(b))
     return AxpbyFn.apply(x, y, float(a), float(b))
 
 
@@ -1859,28 +1869,35 @@ class GateMapFn(GateFn):
 
 
 def local_gate_with_map(cls_logits, ctr_logits, f4, weight: float):
-    if _is16(f4):
-        from . import ops16
-        y, a = ops16.Gate16Fn.apply(cls_logits, ctr_logits, f4, float(weight))
-        n, h, w = f4.shape[0], f4.shape[1], f4.shape[2]
-        return y, a.view(n, 1, h, w).clone()
     return GateMapFn.apply(cls_logits, ctr_logits, f4, float(weight))
 
 
 # ----------------------------------------------------------------------------------------
 # view stacking / slicing for the fusion block
 # ----------------------------------------------------------------------------------------
+def _frames_into(dys, n, v, h, w, c):
+    """[N,V,h,w,C] gradient of V per-view outputs: frame i is dys[i], zero where a view got no gradient."""
+    inner = h * w * c
+    ref = next(d for d in dys if d is not None)
+    dg = (zeros if any(d is None for d in dys) else torch.empty)(n, v, h, w, c, dtype=ref.dtype, device=ref.device)
+    for i, d in enumerate(dys):
+        if d is not None:
+            _launch("copy_frames", dg, _contig(d), inner, dg[:, i], v * inner, n, inner)
+    return dg
+
+
 class StackViewsFn(Function):
     """[N,h,w,C] x V -> [N,V,h,w,C] (ours.py:1819-1820: unsqueeze(2) + cat(dim=2) in NCDHW terms)."""
 
     @staticmethod
     def forward(ctx, *xs):
-        xs = [_contig(_chk(t, "view feature")) for t in xs]
+        dt = BF if _is16(xs[0]) else torch.float32
+        xs = [_contig(_chk(t, "view feature", dt)) for t in xs]
         n, h, w, c = xs[0].shape
         v = len(xs)
-        out = torch.empty(n, v, h, w, c, dtype=torch.float32, device=xs[0].device)
+        out = torch.empty(n, v, h, w, c, dtype=xs[0].dtype, device=xs[0].device)
         inner = h * w * c
-        amax_bound(out, xs)                  # known BEFORE the copy: the largest of the views' maxima
+        amax_bound(out, xs)                  # known BEFORE the copy: the largest of the views' maxima (fp32 storage only)
         am = getattr(out, "_glf_amax", None)
         am = am[2] if am is not None else None
         if am is not None and presplit_ok(out, am) and retain_ok(out.device):
@@ -1891,7 +1908,7 @@ class StackViewsFn(Function):
             out._glf_packed = (out._version, out.data_ptr(), am, pk, torch.cuda.current_stream() if STREAMS else None)
         else:
             for i, t in enumerate(xs):
-                check(lib.glf_copy_frames(_p(t), inner, _p(out[:, i]), v * inner, n, inner, _stream()), "stack_views")
+                _launch("copy_frames", out, t, inner, out[:, i], v * inner, n, inner)
         ctx.cfg = (n, v, h, w, c)
         return out
 
@@ -1903,16 +1920,13 @@ class StackViewsFn(Function):
         inner = h * w * c
         outs = []
         for i in range(v):
-            g = torch.empty(n, h, w, c, dtype=torch.float32, device=dy.device)
-            check(lib.glf_copy_frames(_p(dy[:, i]), v * inner, _p(g), inner, n, inner, _stream()), "unstack_views")
+            g = torch.empty(n, h, w, c, dtype=dy.dtype, device=dy.device)
+            _launch("copy_frames", dy, dy[:, i], v * inner, g, inner, n, inner)
             outs.append(g)
         return tuple(outs)
 
 
 def stack_views(xs: Sequence[torch.Tensor]):
-    if _is16(xs[0]):
-        from . import ops16
-        return ops16.StackViews16Fn.apply(*xs)
     return StackViewsFn.apply(*xs)
 
 
@@ -1922,13 +1936,14 @@ class AddViewsFn(Function):
 
     @staticmethod
     def forward(ctx, g, l):
-        g, l = _contig(_chk(g, "global")), _contig(_chk(l, "local"))
+        g = _contig(_chk(g, "global", None))
+        l = _contig(_chk(l, "local", g.dtype))
         n, v, h, w, c = g.shape
         inner = h * w * c
         outs = []
         for i in range(v):
-            out = torch.empty(n, h, w, c, dtype=torch.float32, device=g.device)
-            check(lib.glf_add_frames(_p(g[:, i]), v * inner, _p(l[:, i]), v * inner, _p(out), inner, n, inner, _stream()), "add_views")
+            out = torch.empty(n, h, w, c, dtype=g.dtype, device=g.device)
+            _launch("add_frames", g, g[:, i], v * inner, l[:, i], v * inner, out, inner, n, inner)
             amax_bound(out, [g, l], sum_=True)
             outs.append(out)
         ctx.cfg = (n, v, h, w, c)
@@ -1937,20 +1952,11 @@ class AddViewsFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, *dys):
-        n, v, h, w, c = ctx.cfg
-        inner = h * w * c
-        dev = next(d.device for d in dys if d is not None)
-        dg = (zeros if any(d is None for d in dys) else torch.empty)(n, v, h, w, c, dtype=torch.float32, device=dev)
-        for i, d in enumerate(dys):
-            if d is not None:
-                check(lib.glf_copy_frames(_p(_contig(d)), inner, _p(dg[:, i]), v * inner, n, inner, _stream()), "add_views_bwd")
+        dg = _frames_into(dys, *ctx.cfg)
         return dg, dg
 
 
 def add_views(g, l):
-    if _is16(g):
-        from . import ops16
-        return ops16.AddViews16Fn.apply(g, l)
     return AddViewsFn.apply(g, l)
 
 
@@ -1959,13 +1965,13 @@ class SplitViewsFn(Function):
 
     @staticmethod
     def forward(ctx, g):
-        g = _contig(_chk(g, "stacked views"))
+        g = _contig(_chk(g, "stacked views", None))
         n, v, h, w, c = g.shape
         inner = h * w * c
         outs = []
         for i in range(v):
-            out = torch.empty(n, h, w, c, dtype=torch.float32, device=g.device)
-            check(lib.glf_copy_frames(_p(g[:, i]), v * inner, _p(out), inner, n, inner, _stream()), "split_views")
+            out = torch.empty(n, h, w, c, dtype=g.dtype, device=g.device)
+            _launch("copy_frames", g, g[:, i], v * inner, out, inner, n, inner)
             outs.append(out)
         ctx.cfg = (n, v, h, w, c)
         return tuple(outs)
@@ -1973,20 +1979,10 @@ class SplitViewsFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, *dys):
-        n, v, h, w, c = ctx.cfg
-        inner = h * w * c
-        dev = next(d.device for d in dys if d is not None)
-        dg = (zeros if any(d is None for d in dys) else torch.empty)(n, v, h, w, c, dtype=torch.float32, device=dev)
-        for i, d in enumerate(dys):
-            if d is not None:
-                check(lib.glf_copy_frames(_p(_contig(d)), inner, _p(dg[:, i]), v * inner, n, inner, _stream()), "split_views_bwd")
-        return dg
+        return _frames_into(dys, *ctx.cfg)
 
 
 def split_views(g):
-    if _is16(g):
-        from . import ops16
-        return ops16.SplitViews16Fn.apply(g)
     return SplitViewsFn.apply(g)
 
 

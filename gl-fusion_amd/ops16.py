@@ -5,6 +5,10 @@ activation gradients in HBM, fp32 master weights and weight gradients, fp32 MFMA
 (torch.bfloat16), so the model code is the same for every precision.  Every function launches glf_s16_* kernels from
 libglfusion_hip.so on the current HIP stream; nothing here is a torch compute op and there is no fallback.
 
+Only what the storage mode does differently lives here: the contractions, convolutions, BatchNorm, the fusion block and the casts.
+The streaming ops in between (ReLU, dropout, pooling, broadcast, gate, axpby, fan-in sums, view stacking) are the nodes of
+glfusion_amd.ops, which serve both storage dtypes.
+
 What stays fp32 in this mode: the input images, the 5- / 1-channel head logits and everything after them (bilinear
 up-sampling, loss, metrics), per-channel statistics and every parameter / parameter gradient.
 """
@@ -21,18 +25,10 @@ from torch.autograd.function import once_differentiable
 from ._lib import AttnParams, GemmParams, TpaviParams, WJ_CVT_BF16, check, lib
 from . import ops as _o
 
-BF = torch.bfloat16
+BF, DT_F32, DT_BF16 = _o.BF, _o.DT_F32, _o.DT_BF16
 _p, _stream, _contig = _o._p, _o._stream, _o._contig
-DT_F32, DT_BF16 = 0, 1
 # block sequences through their single-call C entry points (glf_s16_tpavi_fwd / _bwd); 0 = composed from Python, the same launches
 BLOCK_CALLS = os.environ.get("GLF_BLOCK_CALLS", "1") != "0"
-
-
-def _chk16(t: torch.Tensor, name: str = "tensor") -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != BF:
-        raise RuntimeError(f"glfusion_amd: {name} must be a CUDA(HIP) bfloat16 tensor in 16-bit storage mode (got "
-                           f"{getattr(t, 'device', None)}, {getattr(t, 'dtype', None)}). The engine has no CPU fallback.")
-    return t
 
 
 def weight16(layout: torch.Tensor, owner: torch.Tensor, tag: str) -> torch.Tensor:
@@ -122,7 +118,7 @@ def s16_conv_ok(cin: int, cout: int) -> bool:
 class ToF32Fn(Function):
     @staticmethod
     def forward(ctx, x):
-        x = _contig(_chk16(x, "cast input"))
+        x = _contig(_o._chk(x, "cast input", BF))
         y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
         check(lib.glf_s16_cast(_p(x), DT_BF16, _p(y), DT_F32, x.numel(), _stream()), "s16_cast")
         return y
@@ -184,7 +180,7 @@ class Conv2d16Fn(Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride: int, pad: int, dil: int, colstats=None):
-        _chk16(x, "conv input"); _o._chk(weight, "conv weight")
+        _o._chk(x, "conv input", BF); _o._chk(weight, "conv weight")
         x = _contig(x)
         n, h, w, cin = x.shape
         cout, cin_w, kh, kw = weight.shape
@@ -283,12 +279,12 @@ class ConvCat16Fn(Function):
     def forward(ctx, weight, bias, colstats, *xs):
         _o._chk(weight, "weight")
         cout, ctot = weight.shape[0], weight.shape[1]
-        t0 = _chk16(xs[0], "input")
+        t0 = _o._chk(xs[0], "input", BF)
         offs = [0]
         for t in xs:
             offs.append(offs[-1] + t.shape[-1])
         cat = (offs[-1] == ctot and t0.stride(-1) == 1 and t0.stride(-2) == ctot
-               and all(_chk16(t, "input").stride() == t0.stride() and t.shape[:-1] == t0.shape[:-1]
+               and all(_o._chk(t, "input", BF).stride() == t0.stride() and t.shape[:-1] == t0.shape[:-1]
                        and t.data_ptr() == t0.data_ptr() + 2 * o for t, o in zip(xs, offs)))
         if not cat:
             raise RuntimeError("glfusion_amd: 16-bit conv1x1_cat needs its inputs to be the column slices of one buffer")
@@ -371,31 +367,10 @@ def stem7x7(x, weight, bias, pad: int):
 # ----------------------------------------------------------------------------------------
 # BatchNorm (+ residual, + ReLU)
 # ----------------------------------------------------------------------------------------
-def _take_out16(shape, device):
-    """(output tensor, row stride): the pending ops.output_into view when it matches, a fresh bf16 tensor otherwise."""
-    item = _o._OUT_VIEW[0]
-    if item is not None and tuple(item[0].shape) == tuple(shape) and item[0].stride(-1) == 1 and item[0].dtype == BF:
-        _o._OUT_VIEW[0] = None
-        return item[0], int(item[0].stride(-2))
-    return torch.empty(tuple(shape), dtype=BF, device=device), int(shape[-1])
-
-
-def _rows_view16(t: torch.Tensor):
-    if t.is_contiguous():
-        return t, int(t.shape[-1])
-    if t.dim() >= 2 and t.stride(-1) == 1:
-        ld = int(t.stride(-2))
-        ok = all(t.stride(d) == t.stride(d + 1) * t.shape[d + 1] for d in range(t.dim() - 2))
-        if ok and ld >= t.shape[-1] and ld % 8 == 0 and t.data_ptr() % 16 == 0:
-            return t, ld
-    t = t.contiguous()
-    return t, int(t.shape[-1])
-
-
 class BatchNormAct16Fn(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, running_mean, running_var, nbt, training: bool, momentum: float, eps: float, relu: bool, sums=None):
-        _chk16(x, "bn input"); _o._chk(gamma, "bn weight"); _o._chk(beta, "bn bias")
+        _o._chk(x, "bn input", BF); _o._chk(gamma, "bn weight"); _o._chk(beta, "bn bias")
         x = _contig(x)
         c = x.shape[-1]
         rows = x.numel() // c
@@ -412,8 +387,8 @@ class BatchNormAct16Fn(Function):
             check(lib.glf_bn_eval_coeffs(_p(running_mean), _p(running_var), eps, _p(mean), _p(invstd), c, _stream()), "bn_eval_coeffs")
             sums = None
         if residual is not None:
-            residual = _contig(_chk16(residual, "bn residual"))
-        y, ldy = _take_out16(x.shape, dev)
+            residual = _contig(_o._chk(residual, "bn residual", BF))
+        y, ldy, _ = _o._take_out(x.shape, dev, BF)
         # (grad mode is always off inside Function.forward: what says that a backward may follow is needs_input_grad)
         need_mask = relu and residual is not None and any(ctx.needs_input_grad[:4])
         mask = torch.empty(rows * (c // 8), dtype=torch.uint8, device=dev) if need_mask else None
@@ -433,11 +408,11 @@ class BatchNormAct16Fn(Function):
         rows, c, relu, training, has_res = ctx.cfg
         dy2 = getattr(dy, "_glf_addend", None)
         lddy2 = 0
-        dy, lddy = _rows_view16(dy)
+        dy, lddy = _o._rows_view(dy)
         if dy2 is not None:
             if dy2.shape != dy.shape:
                 raise RuntimeError("glfusion_amd: the two addends of a lazy fan-in gradient differ in shape")
-            dy2, lddy2 = _rows_view16(dy2)
+            dy2, lddy2 = _o._rows_view(dy2)
         dev = dy.device
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if (has_res and ctx.needs_input_grad[3]) else None
@@ -447,273 +422,6 @@ class BatchNormAct16Fn(Function):
         check(lib.glf_s16_bn_bwd(_p(dy), lddy, _p(dy2), lddy2, _p(x), c, _p(mean), _p(invstd), _p(gamma), _p(beta), _p(dx), c, _p(dres), c,
                                  _p(dgamma), _p(dbeta), rows, c, int(relu), int(training), _p(sums), _p(mask), _stream()), "s16_bn_bwd")
         return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None
-
-
-# ----------------------------------------------------------------------------------------
-# pooling / dropout / broadcast / relu / fan-in
-# ----------------------------------------------------------------------------------------
-class MaxPool16Fn(Function):
-    @staticmethod
-    def forward(ctx, x):
-        x = _contig(_chk16(x, "maxpool input"))
-        n, h, w, c = x.shape
-        ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-        y = torch.empty(n, ho, wo, c, dtype=BF, device=x.device)
-        idx = torch.empty(n, ho, wo, c, dtype=torch.uint8, device=x.device)
-        check(lib.glf_s16_maxpool3x3s2_fwd(_p(x), _p(y), _p(idx), n, h, w, c, _stream()), "s16_maxpool_fwd")
-        ctx.save_for_backward(idx)
-        ctx.cfg = (n, h, w, c)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        (idx,) = ctx.saved_tensors
-        n, h, w, c = ctx.cfg
-        dy = _contig(dy)
-        dx = torch.empty(n, h, w, c, dtype=BF, device=dy.device)
-        check(lib.glf_s16_maxpool3x3s2_bwd(_p(dy), _p(idx), _p(dx), n, h, w, c, _stream()), "s16_maxpool_bwd")
-        return dx
-
-
-class AvgPool16Fn(Function):
-    """AdaptiveAvgPool2d(1) on a bf16 map -> fp32 [N,1,1,C]: the ASPP pooled branch (deeplabv3.py:123-135) stays fp32 up to its
-    broadcast -- its BatchNorm normalises over the N per-frame averages, which differ by less than a few bf16 steps."""
-
-    @staticmethod
-    def forward(ctx, x):
-        x = _contig(_chk16(x, "avgpool input"))
-        n, h, w, c = x.shape
-        y = torch.empty(n, 1, 1, c, dtype=torch.float32, device=x.device)
-        check(lib.glf_s16_sum_rows(_p(x), c, _p(y), DT_F32, 1.0 / (h * w), n, h * w, c, _stream()), "s16_avgpool_fwd")
-        ctx.cfg = (n, h, w, c)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        n, h, w, c = ctx.cfg
-        dy = _contig(dy)
-        dx = torch.empty(n, h, w, c, dtype=BF, device=dy.device)
-        check(lib.glf_s16_bcast_rows(_p(dy), DT_F32, _p(dx), c, 1.0 / (h * w), n, h * w, c, _stream()), "s16_avgpool_bwd")
-        return dx
-
-
-class Broadcast16Fn(Function):
-    """bilinear up-sampling from a 1x1 map == broadcast: fp32 or bf16 [N,1,1,C] -> bf16 [N,H,W,C] (into the pending output view)."""
-
-    @staticmethod
-    def forward(ctx, x, h: int, w: int):
-        x = _contig(x)
-        if not x.is_cuda or x.dtype not in (BF, torch.float32):
-            raise RuntimeError("glfusion_amd: broadcast input must be a CUDA fp32 / bf16 tensor")
-        n, c = x.shape[0], x.shape[-1]
-        y, ldy = _take_out16((n, h, w, c), x.device)
-        check(lib.glf_s16_bcast_rows(_p(x), DT_BF16 if x.dtype == BF else DT_F32, _p(y), ldy, 1.0, n, h * w, c, _stream()), "s16_bcast_rows")
-        ctx.cfg = (n, h, w, c, x.dtype)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        n, h, w, c, xdt = ctx.cfg
-        dy, lddy = _rows_view16(dy)
-        dx = torch.empty(n, 1, 1, c, dtype=xdt, device=dy.device)
-        check(lib.glf_s16_sum_rows(_p(dy), lddy, _p(dx), DT_BF16 if xdt == BF else DT_F32, 1.0, n, h * w, c, _stream()), "s16_bcast_rows_bwd")
-        return dx, None, None
-
-
-class Dropout16Fn(Function):
-    @staticmethod
-    def forward(ctx, x, p: float, seed: int):
-        x = _contig(_chk16(x, "dropout input"))
-        y = torch.empty_like(x)
-        check(lib.glf_s16_dropout(_p(x), _p(y), x.numel(), p, seed, _p(_o.step_counter(x.device)), _stream()), "s16_dropout")
-        ctx.cfg = (p, seed)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        p, seed = ctx.cfg
-        dy = _contig(dy)
-        dx = torch.empty_like(dy)
-        check(lib.glf_s16_dropout(_p(dy), _p(dx), dy.numel(), p, seed, _p(_o.step_counter(dy.device)), _stream()), "s16_dropout_bwd")
-        return dx, None, None
-
-
-class Relu16Fn(Function):
-    @staticmethod
-    def forward(ctx, x):
-        x = _contig(_chk16(x, "relu input"))
-        y = torch.empty_like(x)
-        check(lib.glf_s16_relu_fwd(_p(x), _p(y), x.numel(), _stream()), "s16_relu_fwd")
-        ctx.save_for_backward(y)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        (y,) = ctx.saved_tensors
-        dy = _contig(dy)
-        dx = torch.empty_like(dy)
-        check(lib.glf_s16_relu_bwd(_p(dy), _p(y), _p(dx), dy.numel(), _stream()), "s16_relu_bwd")
-        return dx
-
-
-class Axpby16Fn(Function):
-    @staticmethod
-    def forward(ctx, x, y, a: float, b: float):
-        x, y = _contig(_chk16(x, "x")), _contig(_chk16(y, "y"))
-        if x.shape != y.shape:
-            raise RuntimeError("axpby: shapes differ")
-        out = torch.empty_like(x)
-        check(lib.glf_s16_axpby(_p(x), _p(y), _p(out), a, b, x.numel(), _stream()), "s16_axpby")
-        ctx.ab = (a, b)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, d):
-        a, b = ctx.ab
-        d = _contig(d)
-        dx = dy = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(d)
-            check(lib.glf_s16_axpby(_p(d), _p(d), _p(dx), a, 0.0, d.numel(), _stream()), "s16_axpby_bwd")
-        if ctx.needs_input_grad[1]:
-            dy = torch.empty_like(d)
-            check(lib.glf_s16_axpby(_p(d), _p(d), _p(dy), b, 0.0, d.numel(), _stream()), "s16_axpby_bwd")
-        return dx, dy, None, None
-
-
-def add_n16(live) -> torch.Tensor:
-    out = torch.empty_like(live[0])
-    n = out.numel()
-    if n % 8 != 0 or any(d.shape != out.shape for d in live) or len(live) > 8:
-        raise RuntimeError("fan_out: gradients must share one shape with numel % 8 == 0 (<= 8 branches)")
-    arr = (C.c_void_p * len(live))(*[d.data_ptr() for d in live])
-    check(lib.glf_s16_add_n(arr, len(live), _p(out), n, _stream()), "s16_add_n")
-    return out
-
-
-# ----------------------------------------------------------------------------------------
-# local gate, view stacking
-# ----------------------------------------------------------------------------------------
-class Gate16Fn(Function):
-    @staticmethod
-    def forward(ctx, cls, ctr, f, weight: float):
-        cls, ctr, f = _contig(_o._chk(cls, "cls")), _contig(_o._chk(ctr, "ctr")), _contig(_chk16(f, "f4"))
-        c = f.shape[-1]
-        rows = f.numel() // c
-        ncls = cls.shape[-1]
-        y = torch.empty_like(f)
-        a = torch.empty(rows, dtype=torch.float32, device=f.device)
-        am = torch.empty(rows, dtype=torch.int32, device=f.device)
-        check(lib.glf_s16_gate_fwd(_p(cls), ncls, _p(ctr), _p(f), _p(y), _p(a), _p(am), weight, rows, c, _stream()), "s16_gate_fwd")
-        ctx.save_for_backward(cls, ctr, f, a, am)
-        ctx.cfg = (rows, c, ncls, weight)
-        ctx.mark_non_differentiable(a)
-        return y, a
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy, _da):
-        cls, ctr, f, a, am = ctx.saved_tensors
-        rows, c, ncls, weight = ctx.cfg
-        dy = _contig(dy)
-        df = torch.empty_like(f)
-        dcls = torch.empty_like(cls)
-        dctr = torch.empty_like(ctr)
-        check(lib.glf_s16_gate_bwd(_p(dy), _p(f), _p(cls), ncls, _p(ctr), _p(a), _p(am), weight, _p(df), _p(dcls), _p(dctr), rows, c, _stream()),
-              "s16_gate_bwd")
-        return dcls, dctr, df, None
-
-
-def _copy_frames16(src, sfs, dst, dfs, n, inner):
-    """glf_copy_frames moves 16-byte pieces: counted in floats, a bf16 extent is half as long."""
-    check(lib.glf_copy_frames(_p(src), sfs // 2, _p(dst), dfs // 2, n, inner // 2, _stream()), "copy_frames(s16)")
-
-
-class StackViews16Fn(Function):
-    @staticmethod
-    def forward(ctx, *xs):
-        xs = [_contig(_chk16(t, "view feature")) for t in xs]
-        n, h, w, c = xs[0].shape
-        v = len(xs)
-        out = torch.empty(n, v, h, w, c, dtype=BF, device=xs[0].device)
-        inner = h * w * c
-        for i, t in enumerate(xs):
-            _copy_frames16(t, inner, out[:, i], v * inner, n, inner)
-        ctx.cfg = (n, v, h, w, c)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        n, v, h, w, c = ctx.cfg
-        dy = _contig(dy)
-        inner = h * w * c
-        outs = []
-        for i in range(v):
-            g = torch.empty(n, h, w, c, dtype=BF, device=dy.device)
-            _copy_frames16(dy[:, i], v * inner, g, inner, n, inner)
-            outs.append(g)
-        return tuple(outs)
-
-
-class AddViews16Fn(Function):
-    @staticmethod
-    def forward(ctx, g, l):
-        g, l = _contig(_chk16(g, "global")), _contig(_chk16(l, "local"))
-        n, v, h, w, c = g.shape
-        inner = h * w * c
-        outs = []
-        for i in range(v):
-            out = torch.empty(n, h, w, c, dtype=BF, device=g.device)
-            check(lib.glf_s16_add_frames(_p(g[:, i]), v * inner, _p(l[:, i]), v * inner, _p(out), inner, n, inner, _stream()), "s16_add_views")
-            outs.append(out)
-        ctx.cfg = (n, v, h, w, c)
-        return tuple(outs)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, *dys):
-        n, v, h, w, c = ctx.cfg
-        inner = h * w * c
-        dev = next(d.device for d in dys if d is not None)
-        dg = (_o.zeros if any(d is None for d in dys) else torch.empty)(n, v, h, w, c, dtype=BF, device=dev)
-        for i, d in enumerate(dys):
-            if d is not None:
-                _copy_frames16(_contig(d), inner, dg[:, i], v * inner, n, inner)
-        return dg, dg
-
-
-class SplitViews16Fn(Function):
-    @staticmethod
-    def forward(ctx, g):
-        g = _contig(_chk16(g, "stacked views"))
-        n, v, h, w, c = g.shape
-        inner = h * w * c
-        outs = []
-        for i in range(v):
-            out = torch.empty(n, h, w, c, dtype=BF, device=g.device)
-            _copy_frames16(g[:, i], v * inner, out, inner, n, inner)
-            outs.append(out)
-        ctx.cfg = (n, v, h, w, c)
-        return tuple(outs)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, *dys):
-        n, v, h, w, c = ctx.cfg
-        inner = h * w * c
-        dev = next(d.device for d in dys if d is not None)
-        dg = (_o.zeros if any(d is None for d in dys) else torch.empty)(n, v, h, w, c, dtype=BF, device=dev)
-        for i, d in enumerate(dys):
-            if d is not None:
-                _copy_frames16(_contig(d), inner, dg[:, i], v * inner, n, inner)
-        return dg
 
 
 def transpose16(x: torch.Tensor, rows: int, cols: int, batch: int = 1) -> torch.Tensor:
@@ -740,7 +448,7 @@ class Tpavi16Fn(Function):
     def forward(ctx, x, th_w, th_b, ph_w, ph_b, g_w, g_b, wz_w, wz_b, bn_g, bn_b, ln_g, ln_b, rmean, rvar, nbt, training: bool,
                 momentum: float, bn_eps: float, ln_eps: float, mode: str):
         from .fusion import _qkv_weights
-        x = _contig(_chk16(x, "TPAVI input"))
+        x = _contig(_o._chk(x, "TPAVI input", BF))
         if x.dim() != 5:
             raise RuntimeError("TPAVI input must be [N, V, h, w, C]")
         if mode not in ("dot", "embedded"):
