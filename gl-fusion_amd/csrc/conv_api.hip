@@ -110,23 +110,26 @@ void fill_geo(glf_gemm_params& g, const glf_conv_params* p, bool to_input, int h
 
 extern "C" int glf_conv2d_plan(const glf_conv_params* p, int pass, glf_conv_plan* plan) {
     if (int rc = check_params(p, "conv2d_plan")) return rc;
-    GLF_REQUIRE(plan != nullptr && pass >= 0 && pass <= 2, GLF_ERR_NULL, "conv2d_plan: plan missing or pass not in {0 fwd, 1 dgrad, 2 wgrad}");
+    GLF_REQUIRE(plan != nullptr && pass >= 0 && pass <= 3, GLF_ERR_NULL, "conv2d_plan: plan missing or pass not in {0 fwd, 1 dgrad, 2 wgrad, 3 folded fwd}");
     std::memset(plan, 0, sizeof(*plan));
     const int prec = effective_precision(p);
     const int ho = conv_out(p->h, p->kh, p->stride, p->pad, p->dil), wo = conv_out(p->w, p->kw, p->stride, p->pad, p->dil);
     const int taps = p->kh * p->kw;
     const bool plain = taps == 1 && p->stride == 1 && p->pad == 0;
     plan->ho = ho; plan->wo = wo; plan->taps = taps; plan->plain = plain; plan->split = 1;
-    if (pass == 0 || pass == 2) {
+    if (pass == 0 || pass == 2 || pass == 3) {
         const unsigned mask = plain ? 1u : tap_mask_of(1, ho, wo, p->h, p->w, p->kh, p->kw, p->stride, p->pad, p->dil);
         const int kept = __builtin_popcount(mask);
         const double frac = (plain || p->stride != 1) ? 1.0 : rect_fraction(1, ho, wo, p->h, p->w, p->kw, p->pad, p->dil, mask);
         plan->tap_mask = mask; plan->kept_taps = kept;
-        if (pass == 0) {
+        if (pass != 2) {
             plan->M = p->n * ho * wo; plan->N = p->cout; plan->K = p->cin;
             plan->rect = (!plain && taps > 1 && p->stride == 1 && kept > 1 && frac < THR_FWD) ? 1 : 0;
+            // folded forward: the epilogue needs every element stored once -- regions instead of per-tap rectangles where they exist
+            if (pass == 3 && plan->rect == 1 && prec >= 2 && taps == 9 && p->kh == 3 && p->pad == p->dil && ho == p->h && wo == p->w && p->cin % 32 == 0)
+                plan->rect = 2;
             plan->zero_fill = plan->rect == 1;
-            plan->colstats_ok = prec >= 2 && p->cin % 32 == 0 && p->cout % 4 == 0 && plan->rect == 0;
+            plan->colstats_ok = pass == 0 && prec >= 2 && p->cin % 32 == 0 && p->cout % 4 == 0 && plan->rect == 0;
         } else {
             const bool rect = !plain && taps > 1 && p->stride == 1 && kept > 1 && frac < THR_WGRAD;
             const long long rows_o = (long long)p->n * ho * wo;
@@ -195,6 +198,32 @@ extern "C" int glf_conv2d_fwd(const float* x, const float* w_tap, const float* b
         return GLF_OK;
     }
     return glf_gemm_nt(x, w_tap, bias, y, &g, s);
+}
+
+extern "C" int glf_conv2d_fwd_folded(const float* x, const float* w_tap_folded, const float* shift, const float* residual, int64_t ld_res,
+                                     int relu, float* y, const glf_conv_params* p, glf_stream_t s) {
+    GLF_REQUIRE(x && w_tap_folded && shift && y && p, GLF_ERR_NULL, "conv2d_fwd_folded: null argument");
+    glf_conv_plan pl;
+    if (int rc = glf_conv2d_plan(p, 3, &pl)) return rc;
+    GLF_REQUIRE(relu == 0 || relu == 1, GLF_ERR_BAD_SHAPE, "conv2d_fwd_folded: relu must be 0 or 1");
+    GLF_REQUIRE(!residual || ld_res >= p->cout, GLF_ERR_BAD_SHAPE, "conv2d_fwd_folded: ld_res (%lld) < cout (%d)", (long long)ld_res, p->cout);
+    GLF_REQUIRE(effective_precision(p) >= 2, GLF_ERR_UNSUPPORTED, "conv2d_fwd_folded: built on the split-fp16 kernels only (precision 3 / 4)");
+    GLF_REQUIRE(!p->colstats, GLF_ERR_UNSUPPORTED, "conv2d_fwd_folded: column statistics of a folded (inference) conv are not defined");
+    GLF_REQUIRE(pl.rect != 1, GLF_ERR_UNSUPPORTED,
+                "conv2d_fwd_folded: this conv runs as per-tap rectangles with atomics (no region form): use glf_conv2d_fwd + glf_bn_act");
+    glf_gemm_params g;
+    std::memset(&g, 0, sizeof(g));
+    g.M = pl.M; g.N = pl.N; g.K = pl.K; g.lda = p->cin; g.ldb = p->cin; g.ldc = p->cout;
+    g.taps = pl.taps; g.tap_mask = pl.tap_mask; g.tap_stride_b = (int64_t)p->cout * p->cin;
+    g.gather = pl.plain ? 0 : 1;
+    fill_geo(g, p, false, pl.ho, pl.wo);
+    if (pl.plain) { g.n_img = 1; g.hs = g.ws = g.hd = g.wd = 1; g.kh = g.kw = 1; g.stride = 1; g.pad = 0; g.dil = 1; }
+    g.batch = 1; g.alpha = 1.f; g.split = 1; g.rect = pl.rect;
+    g.amax_a = p->amax_x; g.amax_b = p->amax_w; g.amax_c = p->amax_out; g.precision = p->precision;
+    glf_gemm_epilogue e;
+    std::memset(&e, 0, sizeof(e));
+    e.shift = shift; e.residual = residual; e.ld_res = ld_res; e.relu = relu;
+    return glf_gemm_nt_epilogue(x, w_tap_folded, y, &g, &e, s);
 }
 
 extern "C" int glf_conv2d_dgrad(const float* dy, const float* w_tap, const float* w_tap_t, float* dx, const glf_conv_params* p, glf_stream_t s) {

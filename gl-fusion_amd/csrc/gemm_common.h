@@ -27,6 +27,10 @@ struct GemmArgs {
     unsigned long long* stamps;                 // diagnostic builds (-DGLF_STAMPS) only
     int a_presplit, b_presplit;                 // f16x3 / f16 kernels: the operand pointer is the packed pre-split image (glf_split_f16_packed)
     int flags;                                  // f16x3 rows kernel: bits 8-15 = tile-group size (row tiles walked together, 0 = plain row-major order)
+    // fused output epilogue (glf_gemm_nt_epilogue; split-fp16 rows kernels, EPI instantiations only): C = act(alpha * acc + bias[n] + res[m][n])
+    int epi;                                    // 1 = launch the epilogue instantiation
+    const float* res; long long ld_res;         // residual rows indexed like C's (null = none), its row stride in floats
+    int relu;                                   // act: 0 = identity, 1 = max(., 0)
 };
 constexpr int ZERO_PAGE_FLOATS = 1 << 18;
 
@@ -188,6 +192,7 @@ GemmArgs make_args(const float* A, const float* B, const float* bias, float* C, 
     a.tiles_m = (p->M + BM - 1) / BM; a.tiles_n = (p->N + BN - 1) / BN;
     a.vec_a = 0; a.vec_b = 0; a.rect = 0;
     a.amax_a = p->amax_a; a.amax_b = p->amax_b; a.zeros = nullptr; a.amax_c = p->amax_c; a.colstats = p->colstats; a.colmax = p->colstats ? p->colmax : nullptr; a.partial = nullptr; a.flags = 0; a.stamps = nullptr; a.a_presplit = p->a_presplit; a.b_presplit = p->b_presplit;
+    a.epi = 0; a.res = nullptr; a.ld_res = 0; a.relu = 0;
     return a;
 }
 

@@ -64,7 +64,11 @@ constexpr size_t SMEM_ROWS_H8 = 3 * BUF8 + 16;
 // operand is split ONCE (by glf_split_f16_packed, per tensor) instead of in every tile of every launch that reads it.
 // (The variants that were measured and dropped -- deeper register prefetch, ping-pong segments, sched_group_barrier interleave,
 // static wave priorities, other tile-group sizes -- are described with their numbers in DESIGN.md section 8; their code is gone.)
-template <bool GATHER, int NP, bool BP, bool PA = false>
+// EPI: the fused output epilogue of glf_gemm_nt_epilogue -- C = act(alpha * acc + bias[n] (+ res[m][n])), res indexed by the OUTPUT row
+// (after the region mapping) with its own row stride, act = identity or ReLU; amax_c then is the maximum of the value stored.
+// Only for launches that store every output element exactly once (no rect = 1, accumulate, colstats: refused by the entry point).
+// EPI = false compiles to the code it was before the parameter existed.
+template <bool GATHER, int NP, bool BP, bool PA = false, bool EPI = false>
 __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs args) {
     const int pM = args.M, pN = args.N, pK = args.K, p_lda = args.lda, p_ldb = args.ldb, p_ldc = args.ldc;
     const int p_taps = args.taps, p_gather = args.gather, p_accumulate = args.accumulate;
@@ -568,6 +572,10 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
 
     float cmax = 0.f;
     const bool p_colstats = args.colstats != nullptr;
+    const float* __restrict__ p_res = EPI ? args.res : nullptr;
+    const long long p_ldr = args.ld_res;
+    const bool p_relu = EPI && args.relu != 0;
+    const bool res_vec = (p_ldr % 4) == 0 && (reinterpret_cast<size_t>(p_res) % 16) == 0;
     // one result element -> C (plain / accumulate / region store, or the atomic of per-tap rectangles); cs / cq: the calling
     // lane's column sum and sum of squares over the elements it stores (colstats)
     auto put = [&](float a, int row, int col, float bv, double& cs, double& cq) __attribute__((always_inline)) {
@@ -582,6 +590,10 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
         }
         float* dst = C + orow * p_ldc + col;
         float v = p_alpha * a + bv;
+        if constexpr (EPI) {
+            if (p_res) v += p_res[orow * p_ldr + col];
+            if (p_relu) v = fmaxf(v, 0.f);
+        }
         if (p_accumulate) v += *dst;
         *dst = v;
         cmax = fmaxf(cmax, fabsf(v));
@@ -658,6 +670,17 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
                 const float4 a = *reinterpret_cast<const float4*>(tile + rin * 64 + c4);
                 float* dst = C + orow * p_ldc + col;
                 float v[4] = {p_alpha * a.x + bv[0], p_alpha * a.y + bv[1], p_alpha * a.z + bv[2], p_alpha * a.w + bv[3]};
+                if constexpr (EPI) {
+                    if (p_res) {
+                        const float* rp = p_res + orow * p_ldr + col;
+                        const float4 r = ld4(rp, 4, res_vec);
+                        v[0] += r.x; v[1] += r.y; v[2] += r.z; v[3] += r.w;
+                    }
+                    if (p_relu) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
+                    }
+                }
                 if (p_accumulate) {
                     const float4 o = *reinterpret_cast<const float4*>(dst);
                     v[0] += o.x; v[1] += o.y; v[2] += o.z; v[3] += o.w;
@@ -1367,7 +1390,7 @@ int init_gemm_f16s_attrs() {
 #define SET_ATTR(fn, bytes)                                                                              \
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)); \
     if (e != hipSuccess) return fail(GLF_ERR_LAUNCH, "hipFuncSetAttribute(" #fn "): %s", hipGetErrorString(e));
-#define SET_ROWS(G, NP_, PA_, PB_) SET_ATTR((gemm_rows_f16s8_kernel<G, NP_, PB_, PA_>), SMEM_ROWS_H8)
+#define SET_ROWS(G, NP_, PA_, PB_) SET_ATTR((gemm_rows_f16s8_kernel<G, NP_, PB_, PA_>), SMEM_ROWS_H8) SET_ATTR((gemm_rows_f16s8_kernel<G, NP_, PB_, PA_, true>), SMEM_ROWS_H8)
 #define SET_TN(G, NP_, PA_, PB_) SET_ATTR((gemm_tn_f16s_kernel<G, NP_, PA_, PB_>), SMEM_TN_H) SET_ATTR((gemm_tn_f16s_kernel<G, NP_, PA_, PB_, true>), SMEM_TN_H) \
                                  SET_ATTR((gemm_tn_f16s8_kernel<G, NP_, PA_, PB_>), SMEM_TN_H8)
 #define SET_ALL(G, NP_) SET_ROWS(G, NP_, false, false) SET_ROWS(G, NP_, true, false) SET_ROWS(G, NP_, false, true) SET_ROWS(G, NP_, true, true) \
@@ -1432,10 +1455,12 @@ int launch_rows_f16s(const GemmArgs& a0, dim3 grid, bool gather, int nprod, hipS
 #ifdef GLF_STAMPS
     a.partial = reinterpret_cast<float*>(stamps_buffer());
 #endif
-#define GLF_LAUNCH_ROWS(G, NP_, PA_, PB_) hipLaunchKernelGGL((gemm_rows_f16s8_kernel<G, NP_, PB_, PA_>), g2, dim3(NT8), SMEM_ROWS_H8, s, a)
+#define GLF_LAUNCH_ROWS(G, NP_, PA_, PB_)                                                                                  \
+    { if (a.epi) hipLaunchKernelGGL((gemm_rows_f16s8_kernel<G, NP_, PB_, PA_, true>), g2, dim3(NT8), SMEM_ROWS_H8, s, a); \
+      else hipLaunchKernelGGL((gemm_rows_f16s8_kernel<G, NP_, PB_, PA_>), g2, dim3(NT8), SMEM_ROWS_H8, s, a); }
 #define GLF_ROWS_P(G, NP_)                                                                     \
-    { if (pa && pb) GLF_LAUNCH_ROWS(G, NP_, true, true); else if (pa) GLF_LAUNCH_ROWS(G, NP_, true, false); \
-      else if (pb) GLF_LAUNCH_ROWS(G, NP_, false, true); else GLF_LAUNCH_ROWS(G, NP_, false, false); }
+    { if (pa && pb) GLF_LAUNCH_ROWS(G, NP_, true, true) else if (pa) GLF_LAUNCH_ROWS(G, NP_, true, false) \
+      else if (pb) GLF_LAUNCH_ROWS(G, NP_, false, true) else GLF_LAUNCH_ROWS(G, NP_, false, false) }
     if (nprod == 3) { if (gather) GLF_ROWS_P(true, 3) else GLF_ROWS_P(false, 3) }
     else { if (gather) GLF_ROWS_P(true, 1) else GLF_ROWS_P(false, 1) }
 #undef GLF_ROWS_P

@@ -37,7 +37,8 @@ constexpr int PL4 = 128 * 64;            // one fp16 plane of an operand tile: 1
 constexpr int BUF4 = 4 * PL4;            // A high, A low, B high, B low
 constexpr size_t SMEM_ROWS_H4 = 2 * BUF4 + 16;
 
-template <bool GATHER, int NP, bool PA, bool BP>
+// EPI: the fused output epilogue of glf_gemm_nt_epilogue (see gemm_rows_f16s8_kernel)
+template <bool GATHER, int NP, bool PA, bool BP, bool EPI = false>
 __global__ __launch_bounds__(NT4, 2) void gemm_rows_f16s4_kernel(const GemmArgs args) {
     const int pM = args.M, pN = args.N, pK = args.K, p_lda = args.lda, p_ldb = args.ldb, p_ldc = args.ldc;
     const int p_taps = args.taps, p_gather = args.gather, p_accumulate = args.accumulate;
@@ -326,6 +327,10 @@ __global__ __launch_bounds__(NT4, 2) void gemm_rows_f16s4_kernel(const GemmArgs 
 
     float cmax = 0.f;
     const bool p_colstats = args.colstats != nullptr;
+    const float* __restrict__ p_res = EPI ? args.res : nullptr;
+    const long long p_ldr = args.ld_res;
+    const bool p_relu = EPI && args.relu != 0;
+    const bool res_vec = (p_ldr % 4) == 0 && (reinterpret_cast<size_t>(p_res) % 16) == 0;
     // one result element -> C (plain / accumulate / region store, or the atomic of per-tap rectangles); cs / cq: the calling
     // lane's column sum and sum of squares over the elements it stores (colstats)
     auto put = [&](float a, int row, int col, float bv, double& cs, double& cq) __attribute__((always_inline)) {
@@ -340,6 +345,10 @@ __global__ __launch_bounds__(NT4, 2) void gemm_rows_f16s4_kernel(const GemmArgs 
         }
         float* dst = C + orow * p_ldc + col;
         float v = p_alpha * a + bv;
+        if constexpr (EPI) {
+            if (p_res) v += p_res[orow * p_ldr + col];
+            if (p_relu) v = fmaxf(v, 0.f);
+        }
         if (p_accumulate) v += *dst;
         *dst = v;
         cmax = fmaxf(cmax, fabsf(v));
@@ -418,6 +427,17 @@ __global__ __launch_bounds__(NT4, 2) void gemm_rows_f16s4_kernel(const GemmArgs 
                 const float4 a = *reinterpret_cast<const float4*>(tile + rin * 64 + c4);
                 float* dst = C + orow * p_ldc + col;
                 float v[4] = {p_alpha * a.x + bv[0], p_alpha * a.y + bv[1], p_alpha * a.z + bv[2], p_alpha * a.w + bv[3]};
+                if constexpr (EPI) {
+                    if (p_res) {
+                        const float* rp = p_res + orow * p_ldr + col;
+                        const float4 r = ld4(rp, 4, res_vec);
+                        v[0] += r.x; v[1] += r.y; v[2] += r.z; v[3] += r.w;
+                    }
+                    if (p_relu) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
+                    }
+                }
                 if (p_accumulate) {
                     const float4 o = *reinterpret_cast<const float4*>(dst);
                     v[0] += o.x; v[1] += o.y; v[2] += o.z; v[3] += o.w;
@@ -503,9 +523,11 @@ int init_gemm_f16s4_attrs() {
 #define SET_ATTR(fn)                                                                                     \
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM_ROWS_H4); \
     if (e != hipSuccess) return fail(GLF_ERR_LAUNCH, "hipFuncSetAttribute(" #fn "): %s", hipGetErrorString(e));
-#define SET_P(G, NP_) SET_ATTR((gemm_rows_f16s4_kernel<G, NP_, false, false>)) SET_ATTR((gemm_rows_f16s4_kernel<G, NP_, true, false>)) \
-                      SET_ATTR((gemm_rows_f16s4_kernel<G, NP_, false, true>)) SET_ATTR((gemm_rows_f16s4_kernel<G, NP_, true, true>))
+#define SET_E(G, NP_, E_) SET_ATTR((gemm_rows_f16s4_kernel<G, NP_, false, false, E_>)) SET_ATTR((gemm_rows_f16s4_kernel<G, NP_, true, false, E_>)) \
+                          SET_ATTR((gemm_rows_f16s4_kernel<G, NP_, false, true, E_>)) SET_ATTR((gemm_rows_f16s4_kernel<G, NP_, true, true, E_>))
+#define SET_P(G, NP_) SET_E(G, NP_, false) SET_E(G, NP_, true)
     SET_P(false, 3) SET_P(true, 3) SET_P(false, 1) SET_P(true, 1)
+#undef SET_E
 #undef SET_P
 #undef SET_ATTR
     return GLF_OK;
@@ -547,10 +569,12 @@ int launch_rows_f16s4(const GemmArgs& a0, dim3 grid, bool gather, int nprod, hip
     dim3 g2((unsigned)(tiles_m * a.tiles_n), 1, grid.z);
     a.flags = (a.rect == 0 && a.tiles_n >= 8 ? 4 : 0) << 8;          // grouped tile order, as the 8-wave kernel
     const bool pa = a.a_presplit != 0, pb = a.b_presplit != 0;
-#define GLF_L4(G, NP_, PA_, PB_) hipLaunchKernelGGL((gemm_rows_f16s4_kernel<G, NP_, PA_, PB_>), g2, dim3(NT4), SMEM_ROWS_H4, s, a)
+#define GLF_L4(G, NP_, PA_, PB_)                                                                                          \
+    { if (a.epi) hipLaunchKernelGGL((gemm_rows_f16s4_kernel<G, NP_, PA_, PB_, true>), g2, dim3(NT4), SMEM_ROWS_H4, s, a);  \
+      else hipLaunchKernelGGL((gemm_rows_f16s4_kernel<G, NP_, PA_, PB_>), g2, dim3(NT4), SMEM_ROWS_H4, s, a); }
 #define GLF_L4P(G, NP_)                                                                   \
-    { if (pa && pb) GLF_L4(G, NP_, true, true); else if (pa) GLF_L4(G, NP_, true, false); \
-      else if (pb) GLF_L4(G, NP_, false, true); else GLF_L4(G, NP_, false, false); }
+    { if (pa && pb) GLF_L4(G, NP_, true, true) else if (pa) GLF_L4(G, NP_, true, false) \
+      else if (pb) GLF_L4(G, NP_, false, true) else GLF_L4(G, NP_, false, false) }
     if (nprod == 3) { if (gather) GLF_L4P(true, 3) else GLF_L4P(false, 3) }
     else { if (gather) GLF_L4P(true, 1) else GLF_L4P(false, 1) }
 #undef GLF_L4P

@@ -896,6 +896,43 @@ extern "C" int glf_gemm_nt(const float* A, const float* B, const float* bias, fl
     return glf::check_launch("gemm_nt");
 }
 
+// glf_gemm_nt with the fused output epilogue C = act(alpha * acc + shift[n] (+ residual[m][n])): the EPI instantiations of the
+// split-fp16 rows kernels.  Everything that can be refused is refused before the first HIP runtime call.
+extern "C" int glf_gemm_nt_epilogue(const float* A, const float* B, float* C, const glf_gemm_params* p, const glf_gemm_epilogue* e,
+                                    glf_stream_t stream) {
+    GLF_REQUIRE(A && B && C && p && e && e->shift, GLF_ERR_NULL, "gemm_nt_epilogue: null argument");
+    if (int rc = validate(p, A, B, C)) return rc;
+    if (p->gather) GLF_REQUIRE((long long)p->n_img * p->hd * p->wd == p->M, GLF_ERR_BAD_SHAPE, "gemm_nt_epilogue: M (%d) != n_img*hd*wd", p->M);
+    GLF_REQUIRE(p->tap_mask != 0, GLF_ERR_BAD_SHAPE, "gemm_nt_epilogue: empty tap_mask");
+    GLF_REQUIRE(p->ldc >= p->N, GLF_ERR_BAD_SHAPE, "gemm_nt_epilogue: ldc (%d) < N (%d)", p->ldc, p->N);
+    GLF_REQUIRE(e->relu == 0 || e->relu == 1, GLF_ERR_BAD_SHAPE, "gemm_nt_epilogue: relu must be 0 or 1");
+    GLF_REQUIRE(!e->residual || e->ld_res >= p->N, GLF_ERR_BAD_SHAPE, "gemm_nt_epilogue: ld_res (%lld) < N (%d)", (long long)e->ld_res, p->N);
+    const int prec = call_precision(p);
+    GLF_REQUIRE(prec >= 2, GLF_ERR_UNSUPPORTED, "gemm_nt_epilogue: built on the split-fp16 kernels only (precision 3 / 4, effective %d)", prec + 1);
+    GLF_REQUIRE(p->rect != 1 && !p->accumulate && p->split <= 1 && !p->colstats && !p->colmax && p->batch == 1, GLF_ERR_UNSUPPORTED,
+                "gemm_nt_epilogue: rect = 1, accumulate, split > 1, colstats / colmax and batch > 1 cannot be combined with the epilogue");
+    GemmArgs a = make_args(A, B, e->shift, C, p);
+    a.vec_a = aligned16(A) && (p->lda % 4 == 0);
+    a.vec_b = aligned16(B) && (p->ldb % 4 == 0) && (p->tap_stride_b % 4 == 0);
+    GLF_REQUIRE(a.vec_a && a.vec_b && p->K % BK == 0 && p->K <= glf::ZERO_PAGE_FLOATS, GLF_ERR_UNSUPPORTED,
+                "gemm_nt_epilogue: needs the aligned fast path (K %% 32 == 0, 16-byte aligned A / B, lda / ldb / tap_stride_b %% 4 == 0)");
+    GLF_REQUIRE((!p->a_presplit || p->amax_a) && (!p->b_presplit || p->amax_b), GLF_ERR_UNSUPPORTED,
+                "gemm_nt_epilogue: a pre-split operand needs the amax it was split with");
+    if (p->rect == 2) {
+        GLF_REQUIRE(p->gather != 0 && p->kh == 3 && p->kw == 3 && p->stride == 1 && p->pad == p->dil && p->hs == p->hd && p->ws == p->wd,
+                    GLF_ERR_UNSUPPORTED, "gemm_nt_epilogue: region mode needs a 3x3 stride-1 conv with pad == dil on equal maps");
+        a.rect = 2;
+    } else {
+        GLF_REQUIRE(p->rect == 0, GLF_ERR_UNSUPPORTED, "gemm_nt_epilogue: rect must be 0 or 2");
+    }
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(glf::f16s_rows_ok(a), GLF_ERR_UNSUPPORTED, "gemm_nt_epilogue: the split-fp16 rows kernel cannot take this call");
+    a.epi = 1; a.res = e->residual; a.ld_res = e->ld_res; a.relu = e->relu;
+    if (int rc = self_amax(a, p, false, glf::S(stream))) return rc;
+    dim3 grid(a.tiles_m * a.tiles_n, 1, 1);
+    return glf::launch_rows_f16s(a, grid, p->gather != 0, prec == 2 ? 3 : 1, glf::S(stream));
+}
+
 extern "C" int glf_gemm_nn(const float* A, const float* B, const float* bias, float* C,
                            const glf_gemm_params* p, glf_stream_t stream) {
     if (int rc = glf::ensure_init()) return rc;

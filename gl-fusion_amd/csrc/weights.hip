@@ -151,7 +151,40 @@ long long job_workgroups(const glf_weight_job& j) {
     }
 }
 
+// Eval-mode BatchNorm folded into the conv weights (glf_fold_bn): w_out[t][o][i] = w[t][o][i] * s_o, shift[o] = beta_o + (bias_o - mean_o) * s_o
+// with s_o = gamma_o / sqrt(var_o + eps) evaluated in double and rounded to fp32 once -- the folded weight carries ONE extra fp32
+// rounding (the product w * s_o) against the unfolded conv -> BatchNorm pair.  One element per thread and grid-stride step; the
+// first cout threads of the grid also write the shift.
+__global__ __launch_bounds__(WB) void fold_bn_kernel(const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ gamma,
+                                                     const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ var,
+                                                     float eps, float* __restrict__ w_out, float* __restrict__ shift_out, int cout, int cin, long long total) {
+    const long long gid = (long long)blockIdx.x * WB + threadIdx.x, step = (long long)gridDim.x * WB;
+    for (long long o = gid; o < cout; o += step) {
+        const double sc = (double)gamma[o] / sqrt((double)var[o] + (double)eps);
+        shift_out[o] = (float)((double)beta[o] + ((bias ? (double)bias[o] : 0.0) - (double)mean[o]) * sc);
+    }
+    for (long long i = gid; i < total; i += step) {
+        const int o = (int)((i / cin) % cout);
+        const float sc = (float)((double)gamma[o] / sqrt((double)var[o] + (double)eps));
+        w_out[i] = w[i] * sc;
+    }
+}
+
 }  // namespace
+
+extern "C" int glf_fold_bn(const float* w_tap, const float* conv_bias, const float* gamma, const float* beta, const float* mean, const float* var,
+                           float eps, float* w_out, float* shift_out, int taps, int cout, int cin, glf_stream_t s) {
+    GLF_REQUIRE(w_tap && gamma && beta && mean && var && w_out && shift_out, GLF_ERR_NULL, "fold_bn: null argument");
+    GLF_REQUIRE(taps >= 1 && cout >= 1 && cin >= 1 && eps >= 0.f, GLF_ERR_BAD_SHAPE, "fold_bn: taps, cout, cin must be >= 1 and eps >= 0");
+    GLF_REQUIRE(w_out != w_tap, GLF_ERR_BAD_SHAPE, "fold_bn: w_out may not alias w_tap");
+    if (int rc = glf::ensure_init()) return rc;
+    const long long total = (long long)taps * cout * cin;
+    long long blocks = (total + WB - 1) / WB;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(fold_bn_kernel, dim3((unsigned)blocks), dim3(WB), 0, glf::S(s), w_tap, conv_bias, gamma, beta, mean, var, eps, w_out, shift_out,
+                       cout, cin, total);
+    return glf::check_launch("fold_bn");
+}
 
 extern "C" int glf_weights_plan(glf_weight_job* jobs_host, int n_jobs, int* pass_first, int* pass_count, int64_t* pass_wgs) {
     GLF_REQUIRE(jobs_host && pass_first && pass_count && pass_wgs && n_jobs >= 0, GLF_ERR_NULL, "weights_plan: null argument");

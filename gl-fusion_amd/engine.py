@@ -9,6 +9,7 @@ frames per view (main.py:213-218).  `is_cycle=True` adds the temporal cycle-cons
 """
 from __future__ import annotations
 
+import functools
 import os
 from typing import Dict, Iterator, Tuple
 
@@ -118,6 +119,7 @@ class StepGraph:
     def replay(self):
         """Run the recorded step on the current stream.  Returns step_fn()'s (static) result."""
         self.graph.replay()
+        ops.stats_moved()                            # a recorded training step moves running statistics without Python seeing it
         if self.reducer is not None and self.reducer.world > 1:
             self.reducer.finalize()                  # re-points .grad at the reduced bucket slices
         else:
@@ -136,6 +138,20 @@ class StepGraph:
         self.wtable = None
 
 
+def _fold_bn_scope(fn):
+    """Run a Trainer method with ops.set_fold_bn(True) when config['train']['fold_bn'] asks for it; the previous value comes back."""
+    @functools.wraps(fn)
+    def wrapped(self, *args, **kwargs):
+        prev = ops.fold_bn()
+        if self.fold_bn:
+            ops.set_fold_bn(True)
+        try:
+            return fn(self, *args, **kwargs)
+        finally:
+            ops.set_fold_bn(prev)
+    return wrapped
+
+
 class Trainer:
     def __init__(self, config: dict):
         self.config = config
@@ -150,6 +166,9 @@ class Trainer:
         # BASELINE.json configs[2] / [4]); absent = whatever glfusion_amd.ops is set to
         if tr.get("precision"):
             ops.set_precision(tr["precision"])
+        # config['train']['fold_bn'] (absent = False): eval() and validation_and_test() run with BatchNorm folded into the convolutions
+        # (ops.set_fold_bn; takes effect under "f16x3" / "f16" only, training is never touched)
+        self.fold_bn = bool(tr.get("fold_bn", False))
         self.model = Global_and_Local(view_num=self.view_num).to(self.device)  # main.py:150
         opt = config["net"]["opt"]
         if opt.get("opt_name", "Adam") != "Adam":
@@ -249,6 +268,7 @@ class Trainer:
             self.save(epoch)
 
     @torch.no_grad()
+    @_fold_bn_scope
     def eval(self, net_path: str = None, is_fuse: bool = True, raw_data: bool = True, patients=None):
         """main.py:417-543.  Per patient and view a raw clip volume goes through the data path (data.prepare_frames: the
         loader's resize / centre crop / part masks / 255 and the `[1,1,H,W,T] -> [T,1,H,W]` reshape of main.py:495-499),
@@ -299,6 +319,7 @@ class Trainer:
         return result
 
     @torch.no_grad()
+    @_fold_bn_scope
     def validation_and_test(self, net_root: str = None, is_fuse: bool = True, raw_data: bool = True, infos: dict = None,
                             val_list=("0_0", "0_2"), test_list=("0_1", "0_3", "0_4", "0_5", "0_6", "0_7", "0_8", "0_9"), first_scored: int = 50,
                             reduce: bool = True):

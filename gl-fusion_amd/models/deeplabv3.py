@@ -91,6 +91,11 @@ class ASPP(nn.Module):
             sums = ops.stats_slot(self.project[0].out_channels, x.device)
             y = ops.conv1x1_cat(self.project[0].weight, branches, colstats=sums)
             return pbn.forward_nhwc(y, relu=True, sums=sums)
+        if ops.fold_bn() and self.project[0].bias is None:
+            # folded inference: the projection over the shared branch buffer with its BatchNorm + ReLU in the epilogue
+            plan = ops.fold_plan(cat, self.project[0].weight, pbn, 1, 0, 1)
+            if plan is not None:
+                return ops.conv_bn_folded(cat, self.project[0].weight, None, pbn, 1, 0, 1, True, None, plan, amax_x=ops.amax_of(branches[0]))
         y = ops.conv1x1_cat(self.project[0].weight, branches)
         # (the projection's gradient is consumed by ConvCatFn's dgrad / wgrad only -- and only its single-buffer form reads it packed)
         pg = torch.is_grad_enabled() and ops.takes_packed_grad(self.project[0].weight)

@@ -86,6 +86,12 @@ def conv_bn_act(x, conv: Conv2d, bn: BatchNorm2d, relu: bool, residual=None, con
     take a packed pre-split input, the result is written once in that form and has no fp32 copy: do not read it as floats."""
     training = bn.training or bn.running_mean is None
     stem = conv.in_channels == 1 and conv.kernel_size == (7, 7)
+    if ops.fold_bn() and not training and not stem:
+        # opt-in inference path: BatchNorm folded into the conv, shift / residual / ReLU in its epilogue -- one launch, one write
+        stride, pad, dil = conv._geom()
+        plan = ops.fold_plan(x, conv.weight, bn, stride, pad, dil)
+        if plan is not None:
+            return ops.conv_bn_folded(x, conv.weight, conv.bias, bn, stride, pad, dil, relu, residual, plan)
     # the conv output's gradient has ONE consumer, this conv's backward: BatchNorm backward may hand it over as a packed image
     pg = (not stem) and conv.bias is None and torch.is_grad_enabled() and ops.takes_packed_grad(conv.weight)
     if training and not stem:

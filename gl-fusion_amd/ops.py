@@ -19,7 +19,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ._lib import GemmParams, WeightJob, WJ_AMAX, WJ_COPY, WJ_PACK, WJ_PASSES, WJ_PASS_OF, WJ_TAP_MAJOR, WJ_TAP_MAJOR_T, WJ_TRANSPOSE, WJ_ZERO, check, lib
+from ._lib import GemmEpilogue, GemmParams, WeightJob, WJ_AMAX, WJ_COPY, WJ_PACK, WJ_PASSES, WJ_PASS_OF, WJ_TAP_MAJOR, WJ_TAP_MAJOR_T, WJ_TRANSPOSE, WJ_ZERO, check, lib
 
 
 # ----------------------------------------------------------------------------------------
@@ -185,8 +185,10 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
          split: int = 1, rect: bool = False, amax_a: Optional[torch.Tensor] = None,
          amax_b: Optional[torch.Tensor] = None, amax_c: Optional[torch.Tensor] = None,
          colstats: Optional[torch.Tensor] = None, a_packed: bool = False, b_packed: bool = False,
-         colmax: Optional[torch.Tensor] = None) -> None:
+         colmax: Optional[torch.Tensor] = None, epilogue=None) -> None:
     """mode in {'nt','nn','tn'}; geo = (n_img, hs, ws, hd, wd, kh, kw, stride, pad, dil).
+    epilogue ('nt' only): (residual or None, its row stride, relu) -- the call goes to glf_gemm_nt_epilogue, which stores
+    act(alpha * acc + bias[n] + residual[m][n]) once (bias is then required: the folded BatchNorm shift).
     amax_a / amax_b: device scalars bounding max|A| / max|B| (f16x3 precision only; None = measured by the library);
     amax_c: a slot from amax_slot() that receives max|C written| (ignored by rect / split > 1 / non-f16x3 calls -- pass
     it only to calls that store C directly).
@@ -216,7 +218,13 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
     if prof is not None:
         ev0 = torch.cuda.Event(enable_timing=True)
         ev0.record()
-    if mode == "nt":
+    if mode == "nt" and epilogue is not None:
+        e = GemmEpilogue()
+        e.shift, e.residual, e.ld_res, e.relu = _p(bias), _p(epilogue[0]), int(epilogue[1]), int(bool(epilogue[2]))
+        check(lib.glf_gemm_nt_epilogue(_p(A), _p(B), _p(Cm), C.byref(p), C.byref(e), _stream()), "gemm_nt_epilogue")
+    elif epilogue is not None:
+        raise ValueError("gemm: the fused epilogue exists for mode 'nt' only")
+    elif mode == "nt":
         check(lib.glf_gemm_nt(_p(A), _p(B), _p(bias), _p(Cm), C.byref(p), _stream()), "gemm_nt")
     elif mode == "nn":
         check(lib.glf_gemm_nn(_p(A), _p(B), _p(bias), _p(Cm), C.byref(p), _stream()), "gemm_nn")
@@ -1404,6 +1412,7 @@ def replay_bn_updates(records) -> None:
     for bn, mean, invstd, rows in records:
         if not bn.track_running_stats or bn.running_mean is None:
             continue
+        stats_moved(bn)
         check(lib.glf_bn_replay_running(_p(mean), _p(invstd), int(rows), mean.numel(), float(bn.eps), float(bn.momentum),
                                         _p(bn.running_mean), _p(bn.running_var), _p(bn.num_batches_tracked), _stream()), "bn_replay_running")
 
@@ -1450,6 +1459,8 @@ def batch_norm_act(x, bn: torch.nn.modules.batchnorm._BatchNorm, relu: bool, res
     if bn.momentum is None and training and bn.track_running_stats:
         raise RuntimeError("glfusion_amd: cumulative-average BatchNorm (momentum=None) is not built")
     track = training and bn.track_running_stats
+    if track:
+        stats_moved(bn)                   # the kernels write the running statistics in place: tell the folded images
     if _is16(x):
         from . import ops16
         y = ops16.BatchNormAct16Fn.apply(x, bn.weight, bn.bias, residual,
@@ -1467,6 +1478,137 @@ def batch_norm_act(x, bn: torch.nn.modules.batchnorm._BatchNorm, relu: bool, res
                              training, momentum, float(bn.eps), relu, sums if training else None, packed_grad, packed_out)
     if BN_TAP is not None and track:
         BN_TAP.append((bn,) + _last_bn[0])
+    return y
+
+
+# ----------------------------------------------------------------------------------------
+# Folded-BatchNorm inference (opt-in: set_fold_bn).  With frozen statistics BatchNorm is an affine map per output channel,
+#     W'[o] = W[o] * s_o,   shift_o = beta_o + (bias_o - mean_o) * s_o,   s_o = gamma_o / sqrt(var_o + eps)
+# so conv -> BatchNorm (-> + residual) (-> ReLU) is ONE contraction whose epilogue adds the shift and the residual and clamps
+# (glf_gemm_nt_epilogue): the conv output is written once instead of written, re-read, and written again.
+# ----------------------------------------------------------------------------------------
+_FOLD_BN = [False]
+FOLD_COUNT = [0]            # glf_fold_bn launches so far (a folded image is rebuilt only when one of its six sources changed)
+_STATS_GEN = [0]            # bumped when running statistics moved behind Python's back (a replayed training graph)
+_fold_cache = {}
+
+
+def set_fold_bn(flag: bool) -> None:
+    """Route eval-mode, no-grad conv -> BatchNorm groups under 'f16x3' / 'f16' through the folded one-launch path.  Off by default;
+    every other call (training, recorded graphs, the other precisions, convs the epilogue kernels do not cover) is untouched."""
+    _FOLD_BN[0] = bool(flag)
+
+
+def fold_bn() -> bool:
+    return _FOLD_BN[0]
+
+
+def stats_moved(bn=None) -> None:
+    """Running statistics were written by a kernel (torch's version counter does not see raw writes): of `bn`, or -- None -- of
+    modules unknown to the caller (engine.StepGraph.replay)."""
+    if bn is None:
+        _STATS_GEN[0] += 1
+        return
+    for t in (bn.running_mean, bn.running_var):
+        if t is not None:
+            t._glf_moved = getattr(t, "_glf_moved", 0) + 1
+
+
+def _src_stamp(t):
+    return None if t is None else (t._version, t.data_ptr(), getattr(t, "_glf_moved", 0))
+
+
+class _Folded:
+    __slots__ = ("wref", "bref", "wf", "shift", "stamp", "gen")
+
+
+def fold_plan(x: torch.Tensor, weight: torch.Tensor, bn, stride: int, pad: int, dil: int):
+    """(plain, mask, rect, ho, wo) when conv(x, weight) -> bn runs on the folded path right now, else None: switch on, split-fp16
+    precision, no autograd graph, BatchNorm in eval mode with running statistics, and a conv the epilogue kernels cover (aligned
+    fast path, more than 64 output rows, every output element stored once: dense, or region mode where the unfolded conv would
+    sum per-tap rectangles with atomics and the conv is a 3x3 'same' one; other per-tap-rectangle convs stay unfolded)."""
+    if not _FOLD_BN[0] or _PREC[0] < 2 or _S16[0] or torch.is_grad_enabled():
+        return None
+    if bn.training or bn.running_mean is None or bn.running_var is None or bn.weight is None or bn.bias is None:
+        return None
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda or packed_only(x):
+        return None
+    n, h, w, cin = x.shape
+    cout, cin_w, kh, kw = weight.shape
+    if cin_w != cin or cin % 32 != 0 or cin > (1 << 18) or cout % 4 != 0:
+        return None
+    ho, wo = _conv_out(h, kh, stride, pad, dil), _conv_out(w, kw, stride, pad, dil)
+    if ho <= 0 or wo <= 0 or n * ho * wo <= 64:               # <= 64 rows: the skinny kernel of the ASPP pooled branch keeps its path
+        return None
+    taps = kh * kw
+    plain = taps == 1 and stride == 1 and pad == 0
+    mask = 1 if plain else tap_mask(1, ho, wo, h, w, kh, kw, stride, pad, dil)
+    if mask == 0:
+        return None
+    rect = 0
+    if (not plain and taps > 1 and stride == 1 and bin(mask).count("1") > 1
+            and rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) < _rect_thr("fwd")):
+        if not (taps == 9 and kh == 3 and pad == dil and ho == h and wo == w):
+            return None
+        rect = 2
+    return plain, mask, rect, ho, wo
+
+
+def _folded_images(weight: torch.Tensor, bias: Optional[torch.Tensor], bn):
+    """(folded tap-major weights [taps][Cout][Cin], shift [Cout]) of a conv -> BatchNorm pair: derived images of SIX sources
+    (conv weight and bias, gamma, beta, running_mean, running_var), rebuilt in place by one glf_fold_bn launch when the stamp
+    (version counter, data pointer, raw-write note) of any of them changed and never otherwise.  The folded weight carries its
+    own generation as `_glf_version_fn`, so its maximum and packed pre-split image (registered weight images) follow it."""
+    key = (id(weight), id(bn))
+    hit = _fold_cache.get(key)
+    cout, cin, kh, kw = weight.shape
+    if hit is None or hit.wref() is not weight or hit.bref() is not bn or hit.wf.device != weight.device or tuple(hit.wf.shape) != (kh * kw, cout, cin):
+        hit = _Folded()
+        hit.wref = weakref.ref(weight, lambda _r, k=key: _fold_cache.pop(k, None))
+        hit.bref = weakref.ref(bn)
+        hit.wf = torch.empty(kh * kw, cout, cin, dtype=torch.float32, device=weight.device)
+        hit.shift = torch.empty(cout, dtype=torch.float32, device=weight.device)
+        hit.stamp, hit.gen = None, 0
+        href = weakref.ref(hit.wf)
+        hit.wf._glf_version_fn = lambda c=_fold_cache, k=key, r=href: (c[k].gen if (k in c and c[k].wf is r()) else -1)
+        _fold_cache[key] = hit
+    stamp = tuple(_src_stamp(t) for t in (weight, bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)) + (_STATS_GEN[0], float(bn.eps))
+    if hit.stamp != stamp:
+        wt = tap_major(weight)
+        check(lib.glf_fold_bn(_p(wt), _p(bias.detach()) if bias is not None else None, _p(bn.weight.detach()), _p(bn.bias.detach()),
+                              _p(bn.running_mean), _p(bn.running_var), float(bn.eps), _p(hit.wf), _p(hit.shift), kh * kw, cout, cin,
+                              _stream()), "fold_bn")
+        FOLD_COUNT[0] += 1
+        hit.gen += 1
+        hit.stamp = stamp
+    return hit.wf, hit.shift
+
+
+def conv_bn_folded(x, weight, bias, bn, stride: int, pad: int, dil: int, relu: bool, residual=None, plan=None, amax_x=None):
+    """relu?(bn_eval(conv(x)) + residual?) in one launch on NHWC tensors; plan = fold_plan(...) (not None).  amax_x: the bound of
+    max|x| when x itself does not carry one (the ASPP concat buffer)."""
+    plain, mask, rect, ho, wo = plan
+    x = _contig(_chk(x, "conv input"))
+    n, h, w, cin = x.shape
+    cout, _, kh, kw = weight.shape
+    taps = kh * kw
+    wf, shift = _folded_images(weight, bias, bn)
+    y, ldy, shared = _take_out((n, ho, wo, cout), x.device)
+    am = shared if shared is not None else amax_slot(x.device)
+    am_w, am_x = amax_of(wf), (amax_x if amax_x is not None else amax_of(x))
+    ok = nt_presplit_ok(cin, cin, cin)
+    ok_x = ok and (cout * bin(mask).count("1") >= PRESPLIT_MIN_COLS or packed_hit(x, am_x) is not None)
+    xa, pa = pick(x, act_packed(x, am_x) if ok_x else None, ok_x)
+    wb, pb = pick(wf, weight_packed(wf, wf, "w", am_w) if ok else None, ok)
+    res, ldr = (None, 0)
+    if residual is not None:
+        res, ldr = _rows_view(_chk(residual, "bn residual"))
+        if res.numel() // res.shape[-1] != n * ho * wo or res.shape[-1] != cout:
+            raise RuntimeError("conv_bn_folded: residual shape does not match the conv output")
+    gemm("nt", xa, wb, y, M=n * ho * wo, N=cout, K=cin, lda=cin, ldb=cin, ldc=ldy, bias=shift, taps=taps, mask=mask,
+         tap_stride_b=cout * cin, gather=0 if plain else 1, geo=None if plain else (n, h, w, ho, wo, kh, kw, stride, pad, dil), rect=rect,
+         amax_a=am_x, amax_b=am_w, amax_c=am, a_packed=pa, b_packed=pb, epilogue=(res, ldr, relu))
+    set_amax(y, am)
     return y
 
 

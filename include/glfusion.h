@@ -178,6 +178,26 @@ int glf_gemm_tn(const float* A, const float* B, float* C,
 /* bytes of glf_gemm_params.workspace the two-stage reduction of this call needs (0 when p->split <= 1). */
 size_t glf_gemm_tn_workspace_bytes(const glf_gemm_params* p);
 
+/* glf_gemm_nt with a fused output epilogue (split-fp16 kernels, precision 3 / 4 only):
+ *     C[m][n] = act( alpha * sum_k A[m][k] B[n][k] + shift[n] (+ residual[m][n]) ),   act = identity or max(., 0)
+ * -- a convolution followed by an eval-mode BatchNorm whose scale has been folded into the weights (glf_fold_bn), the
+ * block's residual add and its ReLU, with the output written once.  residual rows are indexed like C's (row stride
+ * ld_res floats).  p->amax_c receives the maximum of the value actually STORED (after the epilogue).  Works wherever
+ * the kernels store every output element exactly once: plain and gathered contractions, rect = 0 or 2.  Arguments are
+ * checked before any HIP runtime call: GLF_ERR_NULL (a null pointer wins over every other error), GLF_ERR_BAD_SHAPE
+ * (extents, relu not 0 / 1, ld_res < N), GLF_ERR_UNSUPPORTED for what the epilogue cannot honour and therefore never
+ * ignores: an effective precision other than 3 / 4, rect = 1, accumulate, split > 1, colstats / colmax, batch > 1,
+ * operands off the aligned fast path (K % 32, 16-byte alignment, strides % 4). */
+typedef struct {
+    const float* shift;         /* [N], required                                                                 */
+    const float* residual;      /* optional [M][ld_res]                                                          */
+    int64_t ld_res;             /* row stride of residual in floats (>= N)                                       */
+    int32_t relu;               /* 0 identity, 1 ReLU                                                            */
+    int32_t reserved0;          /* leave 0                                                                       */
+} glf_gemm_epilogue;
+int glf_gemm_nt_epilogue(const float* A, const float* B, float* C, const glf_gemm_params* p, const glf_gemm_epilogue* e,
+                         glf_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * 16-bit storage ("S16": BASELINE.json configs[2] and [4] -- bf16 activations, saved tensors and
  * activation gradients in HBM, fp32 master weights, fp32 accumulate).  Same contraction
@@ -230,8 +250,17 @@ typedef struct {
     int32_t colstats_ok;        /* fwd: glf_conv_params.colstats can be honoured                                  */
     int64_t workspace_bytes;    /* wgrad: scratch for the two-stage split-K reduction (0: none needed)            */
 } glf_conv_plan;
-int glf_conv2d_plan(const glf_conv_params* p, int pass /* 0 fwd, 1 dgrad, 2 wgrad */, glf_conv_plan* plan);
+/* pass 3 = the folded forward (glf_conv2d_fwd_folded): as pass 0, except that a 3x3 stride-1 conv with pad == dil on
+ * equal maps and cin % 32 == 0 that pass 0 would run as per-tap rectangles runs in region mode (rect = 2: every output
+ * element stored once, no zero fill); rect = 1 in a pass-3 plan means the folded entry point refuses the conv. */
+int glf_conv2d_plan(const glf_conv_params* p, int pass /* 0 fwd, 1 dgrad, 2 wgrad, 3 folded fwd */, glf_conv_plan* plan);
 int glf_conv2d_fwd(const float* x, const float* w_tap, const float* bias, float* y, const glf_conv_params* p, glf_stream_t s);
+/* Inference forward with the BatchNorm folded in: y = act(conv(x, w_tap_folded) + shift[cout] (+ residual)), one launch,
+ * y written once.  w_tap_folded / shift from glf_fold_bn; residual (optional) [n*ho*wo][ld_res] rows like y's; relu 0 / 1.
+ * Precision 3 / 4 only.  Checked before any HIP runtime call: GLF_ERR_NULL, GLF_ERR_BAD_SHAPE, and GLF_ERR_UNSUPPORTED
+ * for p->colstats, other precisions and a conv whose pass-3 plan is rect = 1 (run glf_conv2d_fwd + glf_bn_act for it). */
+int glf_conv2d_fwd_folded(const float* x, const float* w_tap_folded, const float* shift, const float* residual, int64_t ld_res,
+                          int relu, float* y, const glf_conv_params* p, glf_stream_t s);
 /* w_tap_t: the same weights as [tap][cin][cout] (glf_oihw_to_tap_major_t); needed by the split-precision kernels,
  * may be NULL for exact fp32 (then w_tap is used). */
 int glf_conv2d_dgrad(const float* dy, const float* w_tap, const float* w_tap_t, float* dx, const glf_conv_params* p, glf_stream_t s);
@@ -281,6 +310,12 @@ int glf_s16_attn_softmax_bwd(const void* theta, const void* phi, const void* g, 
  * Weight layout: torch OIHW [Cout][Cin][kh][kw] <-> tap-major [kh*kw][Cout][Cin].
  * ------------------------------------------------------------------------------------- */
 int glf_oihw_to_tap_major(const float* w, float* out, int cout, int cin, int taps, glf_stream_t s);
+/* Eval-mode BatchNorm folded into tap-major conv weights, one launch per conv (fp32, scale computed in double):
+ *     s_o = gamma_o / sqrt(var_o + eps),   w_out[t][o][i] = w_tap[t][o][i] * s_o,   shift_out[o] = beta_o + (bias_o - mean_o) * s_o
+ * conv_bias may be NULL (0).  w_out may not alias w_tap.  GLF_ERR_NULL / GLF_ERR_BAD_SHAPE (taps, cout, cin < 1, eps < 0)
+ * before any HIP runtime call. */
+int glf_fold_bn(const float* w_tap, const float* conv_bias, const float* gamma, const float* beta, const float* mean, const float* var,
+                float eps, float* w_out, float* shift_out, int taps, int cout, int cin, glf_stream_t s);
 int glf_tap_major_to_oihw(const float* w, float* out, int cout, int cin, int taps, glf_stream_t s);
 /* [kh*kw][Cin][Cout] (k = Cout contiguous): the dgrad weight operand when dgrad runs as an NT contraction. */
 int glf_oihw_to_tap_major_t(const float* w, float* out, int cout, int cin, int taps, glf_stream_t s);

@@ -21,7 +21,15 @@ def main(rank, config):
     config["train"]["device"] = torch.device("cuda", config["train"]["local_rank"])
     parser = argparse.ArgumentParser()
     parser.add_argument("--mode", type=str, required=True)
+    parser.add_argument("--precision", type=str, default=None, choices=("f32", "bf16x6", "f16x3", "f16", "bf16"),
+                        help="contraction precision (config['train']['precision']); default: the engine's")
+    parser.add_argument("--fold-bn", action="store_true",
+                        help="evaluation with BatchNorm folded into the convolutions (config['train']['fold_bn']; f16x3 / f16 only)")
     args = parser.parse_args()
+    if args.precision:
+        config["train"]["precision"] = args.precision
+    if args.fold_bn:
+        config["train"]["fold_bn"] = True
     from glfusion_amd.engine import Trainer
     trainer = Trainer(config)
     if args.mode == "train":
