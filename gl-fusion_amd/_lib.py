@@ -45,6 +45,11 @@ class GemmEpilogue(C.Structure):
     _fields_ = [("shift", C.c_void_p), ("residual", C.c_void_p), ("ld_res", C.c_int64), ("relu", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class S16GemmEpilogue(C.Structure):
+    """Mirror of glf_s16_gemm_epilogue (include/glfusion.h)."""
+    _fields_ = [("shift", C.c_void_p), ("residual", C.c_void_p), ("ld_res", C.c_int64), ("relu", C.c_int32), ("reserved", C.c_int32)]
+
+
 class AttnParams(C.Structure):
     """Mirror of glf_attn_params (include/glfusion.h)."""
     _fields_ = [("frames", C.c_int32), ("L", C.c_int32), ("ci", C.c_int32),

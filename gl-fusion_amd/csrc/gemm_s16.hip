@@ -12,12 +12,15 @@
 //     chunk ^= (row >> 1) & 7: conflict-free ds_read_b128 for the 32x32x16 operand map (row = lane & 31, chunk = 2 s + lane >> 5).
 //     Epilogue: accumulators parked in LDS (fp32), rows written back as whole 16-byte pieces (8 bf16 / 4 floats); optional
 //     per-column sum / sum of squares (BatchNorm statistics) folded through LDS to one f64 atomic per column and workgroup.
+//     EPI instantiations (glf_s16_gemm_nt_epilogue; folded-BatchNorm inference): bias = the folded shift, and the write-out adds a
+//     bf16 residual row piece (one 16-byte load per lane) and clamps at zero in fp32 before the ONE rounding to bf16.
 //     Gather modes as in gemm_common.h: forward conv (1), transposed conv (2), region mode (rect = 2) for 3x3 "same" convs.
 //   tn kernel: C_tap[m][n] = alpha * sum_r A[r][m] * B[src(r,tap)][n]      (weight gradients; attention M = phi^T g)
 //     256 x 128 tiles over 64 reduction rows per stage; LDS images stay [r][m] / [r][n] (dense 512 / 256-byte rows, 64-byte
 //     chunks XORed with r & 3) and fragments are transposed on the way out by ds_read_b64_tr_b16; split-K slices store
 //     partial slabs that s16_tn_reduce_kernel folds in slice order (no atomics: bitwise reproducible gradients).
 #include "gemm_common.h"
+#include <type_traits>
 
 namespace {
 
@@ -40,6 +43,11 @@ struct S16Args {
     double* colstats;                             // NT: [2][N] += column sums of C and C^2 (null = not wanted)
     float* partial;                               // TN: partial slabs [batch*split][kept taps][M][N] (null = direct store)
     int accumulate;                               // NT, fp32 or bf16 C: C += result
+};
+// what the EPI instantiations of the rows kernel take on top (glf_s16_gemm_nt_epilogue); the plain ones keep S16Args as it is
+struct S16EpiArgs : S16Args {
+    const u16* res; long long ld_res;             // bf16 residual, rows indexed like C's (null = none), its row stride in elements
+    int relu;                                     // act: 0 = identity, 1 = max(., 0)
 };
 
 #define GLF_MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
@@ -83,8 +91,8 @@ template <int BN_, int TK_> struct RowsCfg {
 // ----------------------------------------------------------------------------------------------------------------------
 // rows kernel (NT)
 // ----------------------------------------------------------------------------------------------------------------------
-template <bool GATHER, int BN_, int TK_>
-__global__ __launch_bounds__(NTH, TK_ == 64 ? 2 : 4) void s16_rows_kernel(const S16Args args) {
+template <bool GATHER, int BN_, int TK_, bool EPI = false>
+__global__ __launch_bounds__(NTH, TK_ == 64 ? 2 : 4) void s16_rows_kernel(const std::conditional_t<EPI, S16EpiArgs, S16Args> args) {
     using Cfg = RowsCfg<BN_, TK_>;
     constexpr int NJ = Cfg::NJ, WNC = Cfg::WNC, PS = Cfg::PS, A_STAGE = Cfg::A_STAGE;
     constexpr int ROWB = TK_ * 2;                       // bytes of an LDS row
@@ -340,7 +348,7 @@ __global__ __launch_bounds__(NTH, TK_ == 64 ? 2 : 4) void s16_rows_kernel(const 
     float* park = reinterpret_cast<float*>(smem + wave * Cfg::PARK);
     const float p_alpha = args.alpha;
     const float* __restrict__ p_bias = args.bias;
-    const bool stats = args.colstats != nullptr;
+    const bool stats = !EPI && args.colstats != nullptr;
     float cs[NJ], cq[NJ], bv[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -353,6 +361,15 @@ __global__ __launch_bounds__(NTH, TK_ == 64 ? 2 : 4) void s16_rows_kernel(const 
     const int esz = args.c_bf16 ? 2 : 4;
     Cb += (long long)bz * args.bsc * esz;
     const bool wide = (p_ldc % 8) == 0 && (pN % 8) == 0 && (reinterpret_cast<size_t>(args.C) % 16) == 0 && (args.bsc % 8) == 0;
+    // EPI: residual rows (indexed like C's, region mode included) and the clamp; both fold away in the plain instantiations
+    const u16* __restrict__ p_res = nullptr;
+    long long p_ldr = 0;
+    bool p_relu = false;
+    if constexpr (EPI) { p_res = args.res; p_ldr = args.ld_res; p_relu = args.relu != 0; }
+    auto act2 = [&](float a, float b, unsigned r) __attribute__((always_inline)) -> unsigned {
+        a += __uint_as_float(r << 16); b += __uint_as_float(r & 0xffff0000u);
+        return pack_bf16(p_relu ? fmaxf(a, 0.f) : a, p_relu ? fmaxf(b, 0.f) : b);
+    };
     auto out_row = [&](int row) __attribute__((always_inline)) -> long long {
         if (p_rect != 2) return row;
         const int hw = r_h * r_w;
@@ -398,7 +415,11 @@ __global__ __launch_bounds__(NTH, TK_ == 64 ? 2 : 4) void s16_rows_kernel(const 
                         const float4 v1 = *reinterpret_cast<const float4*>(park + rl * PS + c0 + 4);
                         uint4 o;
                         u16* dst = reinterpret_cast<u16*>(Cb) + orow * p_ldc + col;
-                        if (args.accumulate) {
+                        if constexpr (EPI) {
+                            // 8 residual values in one 16-byte load (col % 8 == 0, ld_res % 8 == 0, 16-byte aligned: host-checked)
+                            const uint4 rr = p_res ? *reinterpret_cast<const uint4*>(p_res + orow * p_ldr + col) : make_uint4(0u, 0u, 0u, 0u);
+                            o.x = act2(v0.x, v0.y, rr.x); o.y = act2(v0.z, v0.w, rr.y); o.z = act2(v1.x, v1.y, rr.z); o.w = act2(v1.z, v1.w, rr.w);
+                        } else if (args.accumulate) {
                             const uint4 old = *reinterpret_cast<const uint4*>(dst);
                             o.x = pack_bf16(v0.x + __uint_as_float(old.x << 16), v0.y + __uint_as_float(old.x & 0xffff0000u));
                             o.y = pack_bf16(v0.z + __uint_as_float(old.y << 16), v0.w + __uint_as_float(old.y & 0xffff0000u));
@@ -431,7 +452,10 @@ __global__ __launch_bounds__(NTH, TK_ == 64 ? 2 : 4) void s16_rows_kernel(const 
                     float v = park[rl * PS + c];
                     if (args.c_bf16) {
                         u16* dst = reinterpret_cast<u16*>(Cb) + orow * p_ldc + col;
-                        if (args.accumulate) v += __uint_as_float((unsigned)*dst << 16);
+                        if constexpr (EPI) {
+                            if (p_res) v += __uint_as_float((unsigned)p_res[orow * p_ldr + col] << 16);
+                            if (p_relu) v = fmaxf(v, 0.f);
+                        } else if (args.accumulate) v += __uint_as_float((unsigned)*dst << 16);
                         *dst = (u16)(pack_bf16(v, 0.f) & 0xffffu);
                     } else {
                         float* dst = reinterpret_cast<float*>(Cb) + orow * p_ldc + col;
@@ -919,6 +943,12 @@ int init_gemm_s16_attrs() {
     SET_ATTR((s16_rows_kernel<true, 128, 32>), (RowsCfg<128, 32>::SMEM))
     SET_ATTR((s16_rows_kernel<false, 64, 64>), (RowsCfg<64, 64>::SMEM))
     SET_ATTR((s16_rows_kernel<true, 64, 64>), (RowsCfg<64, 64>::SMEM))
+    SET_ATTR((s16_rows_kernel<false, 128, 64, true>), (RowsCfg<128, 64>::SMEM))
+    SET_ATTR((s16_rows_kernel<true, 128, 64, true>), (RowsCfg<128, 64>::SMEM))
+    SET_ATTR((s16_rows_kernel<false, 128, 32, true>), (RowsCfg<128, 32>::SMEM))
+    SET_ATTR((s16_rows_kernel<true, 128, 32, true>), (RowsCfg<128, 32>::SMEM))
+    SET_ATTR((s16_rows_kernel<false, 64, 64, true>), (RowsCfg<64, 64>::SMEM))
+    SET_ATTR((s16_rows_kernel<true, 64, 64, true>), (RowsCfg<64, 64>::SMEM))
     SET_ATTR((s16_tn_kernel<false>), SMEM_TN16)
     SET_ATTR((s16_tn_kernel<true>), SMEM_TN16)
 #undef SET_ATTR
@@ -926,51 +956,103 @@ int init_gemm_s16_attrs() {
 }
 }  // namespace glf
 
+namespace {
+
+// tile shape, region layout and grid of a rows-kernel launch: host arithmetic only (no HIP runtime call)
+struct RowsPlan16 { int bn, tiles_n, rect; bool tk32; long long tiles_m; };
+
+int rows_plan16(const glf_gemm_params* p, RowsPlan16& r, const char* who) {
+    GLF_REQUIRE(p->rect == 0 || p->rect == 2, GLF_ERR_UNSUPPORTED, "%s: rect must be 0 or 2 (region mode); per-tap rectangles need float atomics", who);
+    // (halving the column tile of the region-mode ASPP forward launches, whose 392 workgroups leave slots empty while the longest tap
+    // chains run, was measured: +1.4 ms per step -- profiles/r04_ab_s16.txt)
+    r.bn = p->N <= 64 ? 64 : 128;
+    r.tiles_n = (p->N + r.bn - 1) / r.bn;
+    r.tiles_m = (p->M + TM - 1) / TM;
+    r.rect = 0;
+    if (p->rect == 2) {
+        GLF_REQUIRE(p->gather != 0 && p->kh == 3 && p->kw == 3 && p->stride == 1 && p->pad == p->dil && p->hs == p->hd && p->ws == p->wd && p->batch == 1,
+                    GLF_ERR_UNSUPPORTED, "%s: region mode needs a 3x3 stride-1 conv with pad == dil on equal maps, batch 1", who);
+        r.rect = 2;
+        r.tiles_m = 0;
+        for (int i = 0; i < 9; ++i) {
+            int y0, y1, x0, x1;
+            unsigned rm;
+            region_of(p->gather, i, p->dil, p->hd, p->wd, y0, y1, x0, x1, rm);
+            r.tiles_m += ((long long)p->n_img * (y1 - y0) * (x1 - x0) + TM - 1) / TM;
+        }
+    }
+    GLF_REQUIRE(r.tiles_m * r.tiles_n < 2147483647LL, GLF_ERR_BAD_SHAPE, "%s: grid out of range", who);
+    // stage depth: 32 = two workgroups per CU (the default), 64 = one per CU with half the barriers; GLF_S16_TK=32|64 forces one
+    static const int tk_force = []() { const char* e = getenv("GLF_S16_TK"); return e ? atoi(e) : 0; }();
+    // measured (profiles/r04_s16_tk_ab.txt): two workgroups per CU win on every shape of the model (K = 256: +29 %, the 3x3 convs
+    // +13-18 %, the M = 150 528 projections +3 %) except the region-mode launches with many short region blocks (rate 12: -10 %)
+    r.tk32 = r.bn == 128 && (tk_force ? tk_force == 32 : p->rect != 2);
+    return GLF_OK;
+}
+
+template <bool EPI, typename Args>
+void launch_rows16(const Args& a, const RowsPlan16& r, int batch, bool gather, hipStream_t s) {
+    const dim3 grid((unsigned)(r.tiles_m * r.tiles_n), 1, batch);
+    if (r.bn == 64) {
+        if (gather) hipLaunchKernelGGL((s16_rows_kernel<true, 64, 64, EPI>), grid, dim3(NTH), (RowsCfg<64, 64>::SMEM), s, a);
+        else hipLaunchKernelGGL((s16_rows_kernel<false, 64, 64, EPI>), grid, dim3(NTH), (RowsCfg<64, 64>::SMEM), s, a);
+    } else if (r.tk32) {
+        if (gather) hipLaunchKernelGGL((s16_rows_kernel<true, 128, 32, EPI>), grid, dim3(NTH), (RowsCfg<128, 32>::SMEM), s, a);
+        else hipLaunchKernelGGL((s16_rows_kernel<false, 128, 32, EPI>), grid, dim3(NTH), (RowsCfg<128, 32>::SMEM), s, a);
+    } else {
+        if (gather) hipLaunchKernelGGL((s16_rows_kernel<true, 128, 64, EPI>), grid, dim3(NTH), (RowsCfg<128, 64>::SMEM), s, a);
+        else hipLaunchKernelGGL((s16_rows_kernel<false, 128, 64, EPI>), grid, dim3(NTH), (RowsCfg<128, 64>::SMEM), s, a);
+    }
+}
+
+}  // namespace
+
 extern "C" int glf_s16_gemm_nt(const void* A, const void* B, const float* bias, void* C, const glf_gemm_params* p, glf_stream_t stream) {
     if (int rc = glf::ensure_init()) return rc;
     if (int rc = validate16(p, A, B, C, "s16_gemm_nt")) return rc;
     GLF_REQUIRE(p->K % TK == 0 && p->K <= (1 << 18), GLF_ERR_UNSUPPORTED, "s16_gemm_nt: K must be a multiple of %d (got %d)", TK, p->K);
     if (p->gather) GLF_REQUIRE((long long)p->n_img * p->hd * p->wd == p->M, GLF_ERR_BAD_SHAPE, "s16_gemm_nt: M (%d) != n_img*hd*wd", p->M);
     if (p->tap_mask == 0) return glf::fail(GLF_ERR_BAD_SHAPE, "s16_gemm_nt: empty tap_mask");
-    GLF_REQUIRE(p->rect == 0 || p->rect == 2, GLF_ERR_UNSUPPORTED, "s16_gemm_nt: rect must be 0 or 2 (region mode); per-tap rectangles need float atomics");
     GLF_REQUIRE(!p->colstats || p->batch == 1, GLF_ERR_UNSUPPORTED, "s16_gemm_nt: colstats needs batch 1");
+    RowsPlan16 r;
+    if (int rc = rows_plan16(p, r, "s16_gemm_nt")) return rc;
     S16Args a = make_args16(A, B, bias, C, p);
-    // (halving the column tile of the region-mode ASPP forward launches, whose 392 workgroups leave slots empty while the longest tap
-    // chains run, was measured: +1.4 ms per step -- profiles/r04_ab_s16.txt)
-    const int bn = p->N <= 64 ? 64 : 128;
-    a.tiles_n = (p->N + bn - 1) / bn;
-    long long tiles_m = (p->M + TM - 1) / TM;
-    if (p->rect == 2) {
-        GLF_REQUIRE(p->gather != 0 && p->kh == 3 && p->kw == 3 && p->stride == 1 && p->pad == p->dil && p->hs == p->hd && p->ws == p->wd && p->batch == 1,
-                    GLF_ERR_UNSUPPORTED, "s16_gemm_nt: region mode needs a 3x3 stride-1 conv with pad == dil on equal maps, batch 1");
-        a.rect = 2;
-        tiles_m = 0;
-        for (int r = 0; r < 9; ++r) {
-            int y0, y1, x0, x1;
-            unsigned rm;
-            region_of(p->gather, r, p->dil, p->hd, p->wd, y0, y1, x0, x1, rm);
-            tiles_m += ((long long)p->n_img * (y1 - y0) * (x1 - x0) + TM - 1) / TM;
-        }
-    }
-    GLF_REQUIRE(tiles_m * a.tiles_n < 2147483647LL, GLF_ERR_BAD_SHAPE, "s16_gemm_nt: grid out of range");
-    dim3 grid((unsigned)(tiles_m * a.tiles_n), 1, p->batch);
-    const bool gather = p->gather != 0;
-    // stage depth: 32 = two workgroups per CU (the default), 64 = one per CU with half the barriers; GLF_S16_TK=32|64 forces one
-    static const int tk_force = []() { const char* e = getenv("GLF_S16_TK"); return e ? atoi(e) : 0; }();
-    // measured (profiles/r04_s16_tk_ab.txt): two workgroups per CU win on every shape of the model (K = 256: +29 %, the 3x3 convs
-    // +13-18 %, the M = 150 528 projections +3 %) except the region-mode launches with many short region blocks (rate 12: -10 %)
-    const bool tk32 = bn == 128 && (tk_force ? tk_force == 32 : p->rect != 2);
-    if (bn == 64) {
-        if (gather) hipLaunchKernelGGL((s16_rows_kernel<true, 64, 64>), grid, dim3(NTH), (RowsCfg<64, 64>::SMEM), glf::S(stream), a);
-        else hipLaunchKernelGGL((s16_rows_kernel<false, 64, 64>), grid, dim3(NTH), (RowsCfg<64, 64>::SMEM), glf::S(stream), a);
-    } else if (tk32) {
-        if (gather) hipLaunchKernelGGL((s16_rows_kernel<true, 128, 32>), grid, dim3(NTH), (RowsCfg<128, 32>::SMEM), glf::S(stream), a);
-        else hipLaunchKernelGGL((s16_rows_kernel<false, 128, 32>), grid, dim3(NTH), (RowsCfg<128, 32>::SMEM), glf::S(stream), a);
-    } else {
-        if (gather) hipLaunchKernelGGL((s16_rows_kernel<true, 128, 64>), grid, dim3(NTH), (RowsCfg<128, 64>::SMEM), glf::S(stream), a);
-        else hipLaunchKernelGGL((s16_rows_kernel<false, 128, 64>), grid, dim3(NTH), (RowsCfg<128, 64>::SMEM), glf::S(stream), a);
-    }
+    a.tiles_n = r.tiles_n; a.rect = r.rect;
+    launch_rows16<false>(a, r, p->batch, p->gather != 0, glf::S(stream));
     return glf::check_launch("s16_gemm_nt");
+}
+
+// glf_s16_gemm_nt with the fused output epilogue C = bf16(act(alpha * acc + shift[n] (+ residual[m][n]))): the EPI instantiations of
+// the rows kernel.  Everything that can be refused is refused before the first HIP runtime call: NULL, then extents, then support.
+extern "C" int glf_s16_gemm_nt_epilogue(const void* A, const void* B, void* C, const glf_gemm_params* p, const glf_s16_gemm_epilogue* e,
+                                        glf_stream_t stream) {
+    const char* who = "s16_gemm_nt_epilogue";
+    GLF_REQUIRE(A && B && C && p && e && e->shift, GLF_ERR_NULL, "%s: null argument", who);
+    {
+        glf_gemm_params q = *p;
+        q.c_dtype = GLF_DT_BF16;                      // the element type is a question of support: asked below, after the extents
+        if (int rc = validate16(&q, A, B, C, who)) return rc;
+    }
+    if (p->gather) GLF_REQUIRE((long long)p->n_img * p->hd * p->wd == p->M, GLF_ERR_BAD_SHAPE, "%s: M (%d) != n_img*hd*wd", who, p->M);
+    GLF_REQUIRE(p->tap_mask != 0, GLF_ERR_BAD_SHAPE, "%s: empty tap_mask", who);
+    GLF_REQUIRE(p->ldc >= p->N, GLF_ERR_BAD_SHAPE, "%s: ldc (%d) < N (%d)", who, p->ldc, p->N);
+    GLF_REQUIRE(e->relu == 0 || e->relu == 1, GLF_ERR_BAD_SHAPE, "%s: relu must be 0 or 1 (got %d)", who, e->relu);
+    GLF_REQUIRE(!e->residual || e->ld_res >= p->N, GLF_ERR_BAD_SHAPE, "%s: ld_res (%lld) < N (%d)", who, (long long)e->ld_res, p->N);
+    GLF_REQUIRE(p->c_dtype == GLF_DT_BF16, GLF_ERR_UNSUPPORTED, "%s: C must be GLF_DT_BF16 (the epilogue rounds to bf16 once)", who);
+    GLF_REQUIRE(!p->accumulate && !p->colstats && p->split <= 1 && p->batch == 1 && p->gather != 2, GLF_ERR_UNSUPPORTED,
+                "%s: accumulate, colstats, split > 1, batch != 1 and the transposed gather cannot be combined with the epilogue", who);
+    GLF_REQUIRE(!e->residual || (aligned16(e->residual) && e->ld_res % 8 == 0), GLF_ERR_UNSUPPORTED,
+                "%s: the residual must be 16-byte aligned with a row stride that is a multiple of 8 elements", who);
+    GLF_REQUIRE(p->K % TK == 0 && p->K <= (1 << 18), GLF_ERR_UNSUPPORTED, "%s: K must be a multiple of %d (got %d)", who, TK, p->K);
+    RowsPlan16 r;
+    if (int rc = rows_plan16(p, r, who)) return rc;
+    if (int rc = glf::ensure_init()) return rc;
+    S16EpiArgs a;
+    static_cast<S16Args&>(a) = make_args16(A, B, e->shift, C, p);
+    a.tiles_n = r.tiles_n; a.rect = r.rect;
+    a.res = static_cast<const u16*>(e->residual); a.ld_res = e->ld_res; a.relu = e->relu;
+    launch_rows16<true>(a, r, 1, p->gather != 0, glf::S(stream));
+    return glf::check_launch(who);
 }
 
 extern "C" size_t glf_s16_gemm_tn_workspace_bytes(const glf_gemm_params* p) {

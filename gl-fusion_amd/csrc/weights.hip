@@ -170,7 +170,62 @@ __global__ __launch_bounds__(WB) void fold_bn_kernel(const float* __restrict__ w
     }
 }
 
+// The fold for 16-bit storage (glf_s16_fold_bn): the bf16 weight image straight from the double product -- ONE rounding, to nearest
+// even, where fp32 W' -> bf16 would round twice.  Bit arithmetic on the double: 45 of the 52 mantissa bits go, a carry out of the
+// kept 7 runs into the exponent field (and from the largest exponent into infinity) as it should; below 2^-126 the result is a
+// bf16 subnormal, a count of 2^-133 units.
+__device__ __forceinline__ unsigned short bf16_rne_f64(double d) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(d);
+    const unsigned sign = (unsigned)(u >> 48) & 0x8000u;
+    const unsigned long long mag = u & 0x7fffffffffffffffULL;
+    if (mag > 0x7ff0000000000000ULL) return (unsigned short)(sign | 0x7fc0u);
+    const int e = (int)(mag >> 52) - 1023 + 127;
+    if (e >= 255) return (unsigned short)(sign | 0x7f80u);
+    if (e <= 0) return (unsigned short)(sign | (unsigned)rint(fabs(d) * 0x1p133));
+    const unsigned long long m = mag & 0x000fffffffffffffULL;
+    const unsigned r = (unsigned)((m + 0x00000fffffffffffULL + ((m >> 45) & 1ULL)) >> 45);      // 0 .. 128
+    return (unsigned short)(sign | (((unsigned)e << 7) + r));
+}
+
+// one thread per 8 consecutive cin (one 16-byte store); the first cout threads of the grid also write the shift
+__global__ __launch_bounds__(WB) void s16_fold_bn_kernel(const float* __restrict__ w, const float* __restrict__ bias, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ var,
+                                                         float eps, unsigned short* __restrict__ w_out, float* __restrict__ shift_out, int cout, int cin8,
+                                                         long long total8) {
+    const long long gid = (long long)blockIdx.x * WB + threadIdx.x, step = (long long)gridDim.x * WB;
+    for (long long o = gid; o < cout; o += step) {
+        const double sc = (double)gamma[o] / sqrt((double)var[o] + (double)eps);
+        shift_out[o] = (float)((double)beta[o] + ((bias ? (double)bias[o] : 0.0) - (double)mean[o]) * sc);
+    }
+    for (long long i = gid; i < total8; i += step) {
+        const int o = (int)((i / cin8) % cout);
+        const double sc = (double)gamma[o] / sqrt((double)var[o] + (double)eps);
+        const float4 a = *reinterpret_cast<const float4*>(w + 8 * i), b = *reinterpret_cast<const float4*>(w + 8 * i + 4);
+        const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        unsigned h[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) h[k] = bf16_rne_f64((double)v[k] * sc);
+        *reinterpret_cast<uint4*>(w_out + 8 * i) = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+    }
+}
+
 }  // namespace
+
+extern "C" int glf_s16_fold_bn(const float* w_tap, const float* conv_bias, const float* gamma, const float* beta, const float* mean, const float* var,
+                               float eps, void* w_out, float* shift_out, int taps, int cout, int cin, glf_stream_t s) {
+    GLF_REQUIRE(w_tap && gamma && beta && mean && var && w_out && shift_out, GLF_ERR_NULL, "s16_fold_bn: null argument");
+    GLF_REQUIRE(taps >= 1 && cout >= 1 && cin >= 1 && eps >= 0.f, GLF_ERR_BAD_SHAPE, "s16_fold_bn: taps, cout, cin must be >= 1 and eps >= 0");
+    GLF_REQUIRE(w_out != (const void*)w_tap, GLF_ERR_BAD_SHAPE, "s16_fold_bn: w_folded_bf16 may not alias w_tap");
+    GLF_REQUIRE(cin % 8 == 0 && (reinterpret_cast<uintptr_t>(w_tap) & 15u) == 0 && (reinterpret_cast<uintptr_t>(w_out) & 15u) == 0, GLF_ERR_UNSUPPORTED,
+                "s16_fold_bn: cin must be a multiple of 8 (got %d) and both weight images 16-byte aligned", cin);
+    if (int rc = glf::ensure_init()) return rc;
+    const long long total8 = (long long)taps * cout * (cin / 8);
+    long long blocks = (total8 + WB - 1) / WB;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(s16_fold_bn_kernel, dim3((unsigned)blocks), dim3(WB), 0, glf::S(s), w_tap, conv_bias, gamma, beta, mean, var, eps,
+                       static_cast<unsigned short*>(w_out), shift_out, cout, cin / 8, total8);
+    return glf::check_launch("s16_fold_bn");
+}
 
 extern "C" int glf_fold_bn(const float* w_tap, const float* conv_bias, const float* gamma, const float* beta, const float* mean, const float* var,
                            float eps, float* w_out, float* shift_out, int taps, int cout, int cin, glf_stream_t s) {

@@ -139,16 +139,20 @@ class StepGraph:
 
 
 def _fold_bn_scope(fn):
-    """Run a Trainer method with ops.set_fold_bn(True) when config['train']['fold_bn'] asks for it; the previous value comes back."""
+    """Run a Trainer method with ops.set_fold_bn(True) / ops.set_fold_bn_s16(True) when config['train']['fold_bn'] /
+    config['train']['fold_bn_s16'] ask for it; the previous values come back."""
     @functools.wraps(fn)
     def wrapped(self, *args, **kwargs):
-        prev = ops.fold_bn()
+        prev, prev16 = ops.fold_bn(), ops.fold_bn_s16()
         if self.fold_bn:
             ops.set_fold_bn(True)
+        if self.fold_bn_s16:
+            ops.set_fold_bn_s16(True)
         try:
             return fn(self, *args, **kwargs)
         finally:
             ops.set_fold_bn(prev)
+            ops.set_fold_bn_s16(prev16)
     return wrapped
 
 
@@ -169,6 +173,8 @@ class Trainer:
         # config['train']['fold_bn'] (absent = False): eval() and validation_and_test() run with BatchNorm folded into the convolutions
         # (ops.set_fold_bn; takes effect under "f16x3" / "f16" only, training is never touched)
         self.fold_bn = bool(tr.get("fold_bn", False))
+        # config['train']['fold_bn_s16'] (absent = False): the same for 16-bit storage (ops.set_fold_bn_s16; takes effect under "bf16" only)
+        self.fold_bn_s16 = bool(tr.get("fold_bn_s16", False))
         self.model = Global_and_Local(view_num=self.view_num).to(self.device)  # main.py:150
         opt = config["net"]["opt"]
         if opt.get("opt_name", "Adam") != "Adam":

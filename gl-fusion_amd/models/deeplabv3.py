@@ -12,7 +12,7 @@ from typing import List
 import torch
 from torch import nn
 
-from .. import ops
+from .. import ops, ops16
 from .layers import AdaptiveAvgPool2d, BatchNorm2d, Conv2d, Dropout, ReLU, conv_bn_act
 from ._utils import _SimpleSegmentationModel_iekd
 
@@ -96,6 +96,10 @@ class ASPP(nn.Module):
             plan = ops.fold_plan(cat, self.project[0].weight, pbn, 1, 0, 1)
             if plan is not None:
                 return ops.conv_bn_folded(cat, self.project[0].weight, None, pbn, 1, 0, 1, True, None, plan, amax_x=ops.amax_of(branches[0]))
+        if ops.fold_bn_s16() and self.project[0].bias is None:
+            plan = ops16.fold_plan16(cat, self.project[0].weight, pbn, 1, 0, 1)
+            if plan is not None:
+                return ops16.conv_bn_folded16(cat, self.project[0].weight, None, pbn, 1, 0, 1, True, None, plan)
         y = ops.conv1x1_cat(self.project[0].weight, branches)
         # (the projection's gradient is consumed by ConvCatFn's dgrad / wgrad only -- and only its single-buffer form reads it packed)
         pg = torch.is_grad_enabled() and ops.takes_packed_grad(self.project[0].weight)

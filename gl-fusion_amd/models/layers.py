@@ -11,7 +11,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from .. import ops
+from .. import ops, ops16
 
 
 def _one(v) -> int:
@@ -92,6 +92,12 @@ def conv_bn_act(x, conv: Conv2d, bn: BatchNorm2d, relu: bool, residual=None, con
         plan = ops.fold_plan(x, conv.weight, bn, stride, pad, dil)
         if plan is not None:
             return ops.conv_bn_folded(x, conv.weight, conv.bias, bn, stride, pad, dil, relu, residual, plan)
+    if ops.fold_bn_s16() and not training and not stem:
+        # the same under 16-bit storage: the affine map on the fp32 accumulator, ONE rounding to bf16 after normalisation
+        stride, pad, dil = conv._geom()
+        plan = ops16.fold_plan16(x, conv.weight, bn, stride, pad, dil)
+        if plan is not None:
+            return ops16.conv_bn_folded16(x, conv.weight, conv.bias, bn, stride, pad, dil, relu, residual, plan)
     # the conv output's gradient has ONE consumer, this conv's backward: BatchNorm backward may hand it over as a packed image
     pg = (not stem) and conv.bias is None and torch.is_grad_enabled() and ops.takes_packed_grad(conv.weight)
     if training and not stem:

@@ -1488,7 +1488,8 @@ def batch_norm_act(x, bn: torch.nn.modules.batchnorm._BatchNorm, relu: bool, res
 # (glf_gemm_nt_epilogue): the conv output is written once instead of written, re-read, and written again.
 # ----------------------------------------------------------------------------------------
 _FOLD_BN = [False]
-FOLD_COUNT = [0]            # glf_fold_bn launches so far (a folded image is rebuilt only when one of its six sources changed)
+_FOLD_BN_S16 = [False]
+FOLD_COUNT = [0]            # glf_fold_bn / glf_s16_fold_bn launches so far (a folded image is rebuilt only when one of its six sources changed)
 _STATS_GEN = [0]            # bumped when running statistics moved behind Python's back (a replayed training graph)
 _fold_cache = {}
 
@@ -1501,6 +1502,17 @@ def set_fold_bn(flag: bool) -> None:
 
 def fold_bn() -> bool:
     return _FOLD_BN[0]
+
+
+def set_fold_bn_s16(flag: bool) -> None:
+    """The same switch for 16-bit storage: eval-mode, no-grad conv -> BatchNorm groups under 'bf16' go through
+    ops16.conv_bn_folded16 (one launch, the value rounded to bf16 once, after normalisation).  Off by default and independent of
+    set_fold_bn: each switch acts under its own precisions only."""
+    _FOLD_BN_S16[0] = bool(flag)
+
+
+def fold_bn_s16() -> bool:
+    return _FOLD_BN_S16[0]
 
 
 def stats_moved(bn=None) -> None:
@@ -1554,25 +1566,35 @@ def fold_plan(x: torch.Tensor, weight: torch.Tensor, bn, stride: int, pad: int, 
     return plain, mask, rect, ho, wo
 
 
+def _fold_entry(cache: dict, weight: torch.Tensor, bias: Optional[torch.Tensor], bn, dtype):
+    """(cache entry, current stamp) of a conv -> BatchNorm pair in `cache` (one cache per storage type of the folded weights: the
+    fp32 images here, the bf16 ones of ops16).  The entry owns the folded weight [taps][Cout][Cin] of `dtype` and the fp32 shift;
+    whoever finds entry.stamp != stamp re-folds in place and stores the stamp.  The stamp covers the six sources (version counter,
+    data pointer, raw-write note), the global note of statistics moved behind Python's back, and eps."""
+    key = (id(weight), id(bn))
+    hit = cache.get(key)
+    cout, cin, kh, kw = weight.shape
+    if hit is None or hit.wref() is not weight or hit.bref() is not bn or hit.wf.device != weight.device or tuple(hit.wf.shape) != (kh * kw, cout, cin):
+        hit = _Folded()
+        hit.wref = weakref.ref(weight, lambda _r, k=key: cache.pop(k, None))
+        hit.bref = weakref.ref(bn)
+        hit.wf = torch.empty(kh * kw, cout, cin, dtype=dtype, device=weight.device)
+        hit.shift = torch.empty(cout, dtype=torch.float32, device=weight.device)
+        hit.stamp, hit.gen = None, 0
+        href = weakref.ref(hit.wf)
+        hit.wf._glf_version_fn = lambda c=cache, k=key, r=href: (c[k].gen if (k in c and c[k].wf is r()) else -1)
+        cache[key] = hit
+    stamp = tuple(_src_stamp(t) for t in (weight, bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)) + (_STATS_GEN[0], float(bn.eps))
+    return hit, stamp
+
+
 def _folded_images(weight: torch.Tensor, bias: Optional[torch.Tensor], bn):
     """(folded tap-major weights [taps][Cout][Cin], shift [Cout]) of a conv -> BatchNorm pair: derived images of SIX sources
     (conv weight and bias, gamma, beta, running_mean, running_var), rebuilt in place by one glf_fold_bn launch when the stamp
     (version counter, data pointer, raw-write note) of any of them changed and never otherwise.  The folded weight carries its
     own generation as `_glf_version_fn`, so its maximum and packed pre-split image (registered weight images) follow it."""
-    key = (id(weight), id(bn))
-    hit = _fold_cache.get(key)
     cout, cin, kh, kw = weight.shape
-    if hit is None or hit.wref() is not weight or hit.bref() is not bn or hit.wf.device != weight.device or tuple(hit.wf.shape) != (kh * kw, cout, cin):
-        hit = _Folded()
-        hit.wref = weakref.ref(weight, lambda _r, k=key: _fold_cache.pop(k, None))
-        hit.bref = weakref.ref(bn)
-        hit.wf = torch.empty(kh * kw, cout, cin, dtype=torch.float32, device=weight.device)
-        hit.shift = torch.empty(cout, dtype=torch.float32, device=weight.device)
-        hit.stamp, hit.gen = None, 0
-        href = weakref.ref(hit.wf)
-        hit.wf._glf_version_fn = lambda c=_fold_cache, k=key, r=href: (c[k].gen if (k in c and c[k].wf is r()) else -1)
-        _fold_cache[key] = hit
-    stamp = tuple(_src_stamp(t) for t in (weight, bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)) + (_STATS_GEN[0], float(bn.eps))
+    hit, stamp = _fold_entry(_fold_cache, weight, bias, bn, torch.float32)
     if hit.stamp != stamp:
         wt = tap_major(weight)
         check(lib.glf_fold_bn(_p(wt), _p(bias.detach()) if bias is not None else None, _p(bn.weight.detach()), _p(bn.bias.detach()),

@@ -22,7 +22,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ._lib import AttnParams, GemmParams, TpaviParams, WJ_CVT_BF16, check, lib
+from ._lib import AttnParams, GemmParams, S16GemmEpilogue, TpaviParams, WJ_CVT_BF16, check, lib
 from . import ops as _o
 
 BF, DT_F32, DT_BF16 = _o.BF, _o.DT_F32, _o.DT_BF16
@@ -50,8 +50,10 @@ KERNEL_NAMES = {("nt", False): "s16_rows_kernel<false>", ("nt", True): "s16_rows
 def gemm16(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: int, N: int, K: int, lda: int, ldb: int, ldc: int,
            bias: Optional[torch.Tensor] = None, taps: int = 1, mask: int = 1, tap_stride_b: int = 0, gather: int = 0, geo=None,
            batch: int = 1, bsa: int = 0, bsb: int = 0, bsc: int = 0, alpha: float = 1.0, accumulate: bool = False, split: int = 1,
-           rect: int = 0, colstats: Optional[torch.Tensor] = None) -> None:
-    """glf_s16_gemm_nt / glf_s16_gemm_tn (include/glfusion.h).  A, B: bf16; Cm: bf16 or fp32 (its dtype is what is stored)."""
+           rect: int = 0, colstats: Optional[torch.Tensor] = None, epilogue=None) -> None:
+    """glf_s16_gemm_nt / glf_s16_gemm_tn (include/glfusion.h).  A, B: bf16; Cm: bf16 or fp32 (its dtype is what is stored).
+    epilogue ('nt' only): (bf16 residual or None, its row stride, relu) -- the call goes to glf_s16_gemm_nt_epilogue, which stores
+    bf16(act(alpha * acc + bias[n] + residual[m][n])) once (bias is then required: the folded BatchNorm shift)."""
     p = GemmParams()
     p.M, p.N, p.K, p.lda, p.ldb, p.ldc = M, N, K, lda, ldb, ldc
     p.taps, p.tap_mask, p.tap_stride_b, p.gather = taps, mask, tap_stride_b, gather
@@ -69,7 +71,13 @@ def gemm16(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: 
     if prof is not None:
         ev0 = torch.cuda.Event(enable_timing=True)
         ev0.record()
-    if mode == "nt":
+    if mode == "nt" and epilogue is not None:
+        e = S16GemmEpilogue()
+        e.shift, e.residual, e.ld_res, e.relu = _p(bias), _p(epilogue[0]), int(epilogue[1]), int(bool(epilogue[2]))
+        check(lib.glf_s16_gemm_nt_epilogue(_p(A), _p(B), _p(Cm), C.byref(p), C.byref(e), _stream()), "s16_gemm_nt_epilogue")
+    elif epilogue is not None:
+        raise ValueError("gemm16: the fused epilogue exists for mode 'nt' only")
+    elif mode == "nt":
         check(lib.glf_s16_gemm_nt(_p(A), _p(B), _p(bias), _p(Cm), C.byref(p), _stream()), "s16_gemm_nt")
     elif mode == "tn":
         check(lib.glf_s16_gemm_tn(_p(A), _p(B), _p(Cm), C.byref(p), _stream()), "s16_gemm_tn")
@@ -327,6 +335,80 @@ class ConvCat16Fn(Function):
 
 def conv1x1_cat(weight, xs: Sequence[torch.Tensor], bias=None, colstats=None):
     return ConvCat16Fn.apply(weight, bias, colstats, *xs)
+
+
+# ----------------------------------------------------------------------------------------
+# Folded-BatchNorm inference under 16-bit storage (opt-in: ops.set_fold_bn_s16).  Unfolded, the conv result is rounded to bf16 and
+# THEN normalised; folded, W' = W * s_o is the bf16 B operand, the shift (and the residual, and the clamp) are applied to the fp32
+# accumulator and the value is rounded to bf16 once, after normalisation.
+# ----------------------------------------------------------------------------------------
+_fold_cache16 = {}          # keyed apart from ops._fold_cache: one model may run folded under 'f16x3' and under 'bf16' in one process
+
+
+def fold_plan16(x: torch.Tensor, weight: torch.Tensor, bn, stride: int, pad: int, dil: int):
+    """(plain, mask, rect, ho, wo) when conv(x, weight) -> bn runs on the folded 16-bit path right now, else None: switch on,
+    precision 'bf16', no autograd graph, BatchNorm in eval mode with running statistics and affine parameters, a bf16 NHWC device
+    tensor, a conv the 16-bit kernels take, more than 64 output rows (the ASPP pooled branch keeps its path) and at least one tap
+    that can touch the map.  Every conv forward of this mode stores each element once (the ASPP rates run in region mode), so
+    nothing has to be planned around."""
+    if not _o._FOLD_BN_S16[0] or not _o._S16[0] or torch.is_grad_enabled():
+        return None
+    if bn.training or bn.running_mean is None or bn.running_var is None or bn.weight is None or bn.bias is None:
+        return None
+    if x.dim() != 4 or x.dtype != BF or not x.is_cuda:
+        return None
+    n, h, w, cin = x.shape
+    cout, cin_w, kh, kw = weight.shape
+    if cin_w != cin or not s16_conv_ok(cin, cout) or cin > (1 << 18):
+        return None
+    ho, wo = _o._conv_out(h, kh, stride, pad, dil), _o._conv_out(w, kw, stride, pad, dil)
+    if ho <= 0 or wo <= 0 or n * ho * wo <= 64:
+        return None
+    taps = kh * kw
+    plain = taps == 1 and stride == 1 and pad == 0
+    mask = 1 if plain else _o.tap_mask(1, ho, wo, h, w, kh, kw, stride, pad, dil)
+    if mask == 0:
+        return None
+    rect = 0 if plain else _region(taps, kh, stride, pad, dil, h, w, ho, wo, mask, 1)
+    return plain, mask, rect, ho, wo
+
+
+def _folded_images16(weight: torch.Tensor, bias: Optional[torch.Tensor], bn):
+    """(folded tap-major bf16 weights [taps][Cout][Cin], fp32 shift [Cout]): ops._folded_images with a cache of its own and
+    glf_s16_fold_bn as the fold -- the same stamp of the six sources, re-folded in place only when it differs."""
+    cout, cin, kh, kw = weight.shape
+    hit, stamp = _o._fold_entry(_fold_cache16, weight, bias, bn, BF)
+    if hit.stamp != stamp:
+        wt = _o.tap_major(weight)
+        check(lib.glf_s16_fold_bn(_p(wt), _p(bias.detach()) if bias is not None else None, _p(bn.weight.detach()), _p(bn.bias.detach()),
+                                  _p(bn.running_mean), _p(bn.running_var), float(bn.eps), _p(hit.wf), _p(hit.shift), kh * kw, cout, cin,
+                                  _stream()), "s16_fold_bn")
+        _o.FOLD_COUNT[0] += 1
+        hit.gen += 1
+        hit.stamp = stamp
+    return hit.wf, hit.shift
+
+
+def conv_bn_folded16(x, weight, bias, bn, stride: int, pad: int, dil: int, relu: bool, residual=None, plan=None):
+    """relu?(bn_eval(conv(x)) + residual?) in ONE glf_s16_gemm_nt_epilogue launch on bf16 NHWC tensors; plan = fold_plan16(...)
+    (not None).  Writes into a pending ops.output_into view (the ASPP branches' column slices of the shared buffer)."""
+    if plan is None:
+        raise RuntimeError("conv_bn_folded16: needs the plan of fold_plan16 (None = this conv does not run folded)")
+    plain, mask, rect, ho, wo = plan
+    x = _contig(_o._chk(x, "conv input", BF))
+    n, h, w, cin = x.shape
+    cout, _, kh, kw = weight.shape
+    wf, shift = _folded_images16(weight, bias, bn)
+    res, ldr = (None, 0)
+    if residual is not None:
+        res, ldr = _o._rows_view(_o._chk(residual, "bn residual", BF))
+        if res.numel() // res.shape[-1] != n * ho * wo or res.shape[-1] != cout:
+            raise RuntimeError("conv_bn_folded16: residual shape does not match the conv output")
+    y, ldy, _ = _o._take_out((n, ho, wo, cout), x.device, BF)
+    gemm16("nt", x, wf, y, M=n * ho * wo, N=cout, K=cin, lda=cin, ldb=cin, ldc=ldy, bias=shift, taps=kh * kw, mask=mask,
+           tap_stride_b=cout * cin, gather=0 if plain else 1, geo=None if plain else (n, h, w, ho, wo, kh, kw, stride, pad, dil), rect=rect,
+           epilogue=(res, ldr, relu))
+    return y
 
 
 # ----------------------------------------------------------------------------------------

@@ -219,6 +219,24 @@ int glf_gemm_nt_epilogue(const float* A, const float* B, float* C, const glf_gem
 int glf_s16_gemm_nt(const void* A, const void* B, const float* bias, void* C, const glf_gemm_params* p, glf_stream_t stream);
 int glf_s16_gemm_tn(const void* A, const void* B, void* C, const glf_gemm_params* p, glf_stream_t stream);
 size_t glf_s16_gemm_tn_workspace_bytes(const glf_gemm_params* p);
+/* glf_s16_gemm_nt with a fused output epilogue (folded-BatchNorm inference under 16-bit storage):
+ *     C[m][n] = bf16( act( alpha * acc[m][n] + shift[n] (+ float(residual[m][n])) ) ),   act = identity or max(., 0)
+ * All arithmetic is fp32 on the fp32 accumulator; the value is rounded to bf16 ONCE, after the epilogue.  residual (bf16) rows
+ * are indexed like C's rows (region mode included), ld_res elements apart.  Every output element is stored exactly once
+ * (plain and forward-gathered contractions, rect = 0 or 2).  Checked before any HIP runtime call, in this order:
+ * GLF_ERR_NULL (A, B, C, p, e, e->shift); GLF_ERR_BAD_SHAPE (the extents glf_s16_gemm_nt checks, ldc < N, relu not 0 / 1,
+ * ld_res < N with a residual); GLF_ERR_UNSUPPORTED -- never ignored -- for c_dtype != GLF_DT_BF16, accumulate, colstats,
+ * split > 1, batch != 1, gather == 2, a residual that is not 16-byte aligned or whose ld_res % 8 != 0, K % 64 != 0 and a
+ * rect other than 0 / 2. */
+typedef struct {
+    const float* shift;         /* [N], required                                                                 */
+    const void* residual;       /* optional bf16 [M][ld_res]                                                     */
+    int64_t ld_res;             /* row stride of residual in elements (>= N, % 8 == 0)                           */
+    int32_t relu;               /* 0 identity, 1 ReLU                                                            */
+    int32_t reserved;           /* leave 0                                                                       */
+} glf_s16_gemm_epilogue;
+int glf_s16_gemm_nt_epilogue(const void* A, const void* B, void* C, const glf_gemm_params* p, const glf_s16_gemm_epilogue* e,
+                             glf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Convolution entry points (F.conv2d forward / backward: models/_utils.py:192 excluded -- glf_stem7x7_* --,
@@ -316,6 +334,12 @@ int glf_oihw_to_tap_major(const float* w, float* out, int cout, int cin, int tap
  * before any HIP runtime call. */
 int glf_fold_bn(const float* w_tap, const float* conv_bias, const float* gamma, const float* beta, const float* mean, const float* var,
                 float eps, float* w_out, float* shift_out, int taps, int cout, int cin, glf_stream_t s);
+/* The same fold for 16-bit storage: w_folded_bf16[t][o][i] = bf16(w_tap[t][o][i] * s_o) with the product taken in double and
+ * rounded ONCE, to nearest even (no fp32 W' in between); shift as glf_fold_bn (fp32).  cin % 8 == 0 (16-byte rows of bf16), else
+ * GLF_ERR_UNSUPPORTED.  GLF_ERR_NULL, then GLF_ERR_BAD_SHAPE (taps, cout, cin < 1, eps < 0), before any HIP runtime call. */
+int glf_s16_fold_bn(const float* w_tap, const float* bias /* may be NULL */, const float* gamma, const float* beta,
+                    const float* mean, const float* var, float eps, void* w_folded_bf16, float* shift,
+                    int taps, int cout, int cin, glf_stream_t s);
 int glf_tap_major_to_oihw(const float* w, float* out, int cout, int cin, int taps, glf_stream_t s);
 /* [kh*kw][Cin][Cout] (k = Cout contiguous): the dgrad weight operand when dgrad runs as an NT contraction. */
 int glf_oihw_to_tap_major_t(const float* w, float* out, int cout, int cin, int taps, glf_stream_t s);

@@ -25,11 +25,15 @@ def main(rank, config):
                         help="contraction precision (config['train']['precision']); default: the engine's")
     parser.add_argument("--fold-bn", action="store_true",
                         help="evaluation with BatchNorm folded into the convolutions (config['train']['fold_bn']; f16x3 / f16 only)")
+    parser.add_argument("--fold-bn-s16", action="store_true",
+                        help="the same under 16-bit storage (config['train']['fold_bn_s16']; bf16 only)")
     args = parser.parse_args()
     if args.precision:
         config["train"]["precision"] = args.precision
     if args.fold_bn:
         config["train"]["fold_bn"] = True
+    if args.fold_bn_s16:
+        config["train"]["fold_bn_s16"] = True
     from glfusion_amd.engine import Trainer
     trainer = Trainer(config)
     if args.mode == "train":
