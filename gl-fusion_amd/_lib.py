@@ -56,6 +56,12 @@ class AttnParams(C.Structure):
                 ("ldq", C.c_int64), ("ldk", C.c_int64), ("ldv", C.c_int64), ("ldy", C.c_int64), ("lddy", C.c_int64), ("ldd", C.c_int64)]
 
 
+class AttnPairParams(C.Structure):
+    """Mirror of glf_attn_pair_params (include/glfusion.h)."""
+    _fields_ = [("frames", C.c_int32), ("L", C.c_int32), ("ci", C.c_int32), ("reserved0", C.c_int32),
+                ("ldg", C.c_int64), ("ldy", C.c_int64), ("lddy", C.c_int64), ("lddg", C.c_int64)]
+
+
 class TpaviParams(C.Structure):
     """Mirror of glf_tpavi_params (include/glfusion.h)."""
     _fields_ = [("n", C.c_int32), ("L", C.c_int32), ("c", C.c_int32), ("ci", C.c_int32), ("training", C.c_int32),
@@ -100,6 +106,8 @@ def _ctype(decl: str):
         return C.POINTER(GemmParams)
     if "glf_attn_params" in decl:
         return C.POINTER(AttnParams)
+    if "glf_attn_pair_params" in decl:
+        return C.POINTER(AttnPairParams)
     if "glf_tpavi_params" in decl:
         return C.POINTER(TpaviParams)
     if "glf_conv_params" in decl:

@@ -10,6 +10,11 @@ so we re-associate exactly:  M_n = phi_n^T g_n / L  ([Ci,Ci] per frame), y_n = t
 formed and the matmul work drops from 2*L*L*Ci to 2*L*Ci*Ci MACs per frame.
 mode 'embedded' (softmax, ours.py:896-897): scores are materialised per frame, normalised by a
 row-softmax kernel, then contracted with g.
+mode 'gaussian' (ours.py:871-875): the softmax of x x^T -- no theta / phi, the scores contract over C.  Scores per group of
+frames (at most CHUNK_BYTES alive), row softmax, P g; backward recomputes them and adds dS x and dS^T x into dx.
+mode 'concatenate' (ours.py:883-894): f_ij = relu(w_theta . theta_i + w_phi . phi_j + c), y = (f / L) g.  The score is the
+sum of two scalars per position, a = theta w_theta and b = phi w_phi: one fused kernel (csrc/attn_pair.hip) forms the
+relu(a_i + b_j + c) tiles on the fly; the reference's [N, 2 Ci, L, L] tensor and the [N, L, L] scores never exist.
 
 Tail (ours.py:908-915): w = W_z y + b;  z = LayerNorm_C( BatchNorm3d(w) + x ) in one fused pass.
 """
@@ -23,7 +28,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ._lib import AttnParams, check, lib
+from ._lib import AttnPairParams, AttnParams, check, lib
 from .ops import (_chk, _contig, _p, _stream, _tn_split, _ws, _wimage, _registry, WJ_COPY, stats_slot, amax_of, amax_slot, colsum, gemm, set_amax, split_mode,
                   transpose2d, weight_T, weight_packed, nt_presplit_ok, tn_presplit_ok, act_packed, packed_hit, pick, zeros, _ones4)
 
@@ -64,6 +69,17 @@ def chunked_softmax_ok(ci: int, L: int) -> bool:
     return CHUNKED_SOFTMAX and split_mode() and ci % 32 == 0 and L % 4 == 0
 
 
+def gaussian_chunked_ok(ci: int) -> bool:
+    """'gaussian' runs the frame-group route under EVERY precision (exact fp32 included: the same bounded buffers on the exact
+    contractions); only widths the split kernels' K = 32 granularity excludes (toy modules) materialise the scores."""
+    return ci % 32 == 0
+
+
+def pair_relu_ok(ci: int) -> bool:
+    """Widths of the fused pairwise-ReLU kernel (glf_attn_pair_relu_*): the fused softmax kernel's."""
+    return ci % 32 == 0 and ci <= 1024
+
+
 def _frames_per_chunk(n: int, L: int) -> int:
     lp = (L + 31) // 32 * 32
     return max(1, min(n, CHUNK_BYTES // (L * lp * 4)))
@@ -89,6 +105,13 @@ def fused_softmax_ok(ci: int) -> bool:
     return FUSED_SOFTMAX and ci % 32 == 0 and ci <= 1024
 
 
+def _pair_params(n: int, L: int, ci: int, ldg: int, ldy: int, lddy: int, lddg: int) -> AttnPairParams:
+    pp = AttnPairParams()
+    pp.frames, pp.L, pp.ci = n, L, ci
+    pp.ldg, pp.ldy, pp.lddy, pp.lddg = ldg, ldy, lddy, lddg
+    return pp
+
+
 def _attn_params(n: int, L: int, ci: int, ldqkv: int, ldy: int) -> AttnParams:
     ap = AttnParams()
     ap.frames, ap.L, ap.ci = n, L, ci
@@ -101,28 +124,30 @@ _qkv_cache = {}
 
 
 def _qkv_weights(params):
-    """theta | phi | g weights stacked as ONE [3*ci, c] operand (+ the stacked bias), so the three projections run as a
-    single contraction over the shared input.  The stacked buffers live as long as theta's weight; each of the six slices is
+    """theta | phi | g weights (params = the k weights, then their k biases; k = 1 for 'gaussian', which projects g alone)
+    stacked as ONE [k*ci, c] operand (+ the stacked bias), so the projections run as a single contraction over the shared input.  The stacked buffers live as long as theta's weight; each of the six slices is
     a registered weight image (ops._wimage: re-copied when its source parameter changed, or by ops.refresh_weights), and the
     stacked operand carries the combined version stamp of its sources for the images derived from IT (maximum, transpose,
     packed forms)."""
-    th_w, ph_w, g_w, th_b, ph_b, g_b = params
+    k = len(params) // 2
+    ws_, bs_ = params[:k], params[k:]
+    th_w = ws_[0]
     ci, c = th_w.shape[0], th_w.shape[1]
     if ci % 4 != 0:                                    # odd toy widths only (the 16-byte copy kernel does not apply)
-        Wcat = torch.cat([_contig(t.detach()).view(ci, c) for t in (th_w, ph_w, g_w)], dim=0)
-        bcat = torch.cat((th_b.detach(), ph_b.detach(), g_b.detach()), dim=0)
+        Wcat = torch.cat([_contig(t.detach()).view(ci, c) for t in ws_], dim=0)
+        bcat = torch.cat([t.detach() for t in bs_], dim=0)
         return Wcat, bcat
     key = id(th_w)
     hit = _qkv_cache.get(key)
-    if hit is None or hit[0]() is not th_w or hit[1].device != th_w.device or hit[1].shape != (3 * ci, c):
-        Wcat = torch.empty(3 * ci, c, dtype=torch.float32, device=th_w.device)
-        bcat = torch.empty(3 * ci, dtype=torch.float32, device=th_w.device)
+    if hit is None or hit[0]() is not th_w or hit[1].device != th_w.device or hit[1].shape != (k * ci, c):
+        Wcat = torch.empty(k * ci, c, dtype=torch.float32, device=th_w.device)
+        bcat = torch.empty(k * ci, dtype=torch.float32, device=th_w.device)
         refs = [weakref.ref(t) for t in params]
         Wcat._glf_version_fn = lambda refs=refs: tuple((r()._version, r().data_ptr()) if r() is not None else None for r in refs)
         Wcat._glf_sources = refs
         hit = _qkv_cache[key] = (weakref.ref(th_w, lambda _r, k=key: _qkv_cache.pop(k, None)), Wcat, bcat)
     _, Wcat, bcat = hit
-    for i, (w, b) in enumerate(((th_w, th_b), (ph_w, ph_b), (g_w, g_b))):
+    for i, (w, b) in enumerate(zip(ws_, bs_)):
         for t, dst, n in ((w, Wcat[i * ci:(i + 1) * ci], ci * c), (b, bcat[i * ci:(i + 1) * ci], ci)):
             src = _contig(t.detach())
             im, fresh = _wimage(t, "qkvcat", WJ_COPY, src, (n, 0, 0), lambda dst=dst: dst)
@@ -137,23 +162,27 @@ def _qkv_weights(params):
 class TpaviFn(Function):
     @staticmethod
     def forward(ctx, x, th_w, th_b, ph_w, ph_b, g_w, g_b, wz_w, wz_b, bn_g, bn_b, ln_g, ln_b,
-                rmean, rvar, nbt, training: bool, momentum: float, bn_eps: float, ln_eps: float, mode: str):
+                rmean, rvar, nbt, training: bool, momentum: float, bn_eps: float, ln_eps: float, mode: str, wf_w=None, wf_b=None):
+        """th_* / ph_*: None for 'gaussian' (the mode owns no theta / phi); wf_w [1, 2 Ci, 1, 1], wf_b [1]: W_f of 'concatenate'."""
         x = _contig(_chk(x, "TPAVI input"))
         if x.dim() != 5:
             raise RuntimeError("TPAVI input must be [N, V, h, w, C]")
         n, v, h, w_, c = x.shape
         L = v * h * w_
         rows = n * L
-        ci = th_w.shape[0]
+        ci = g_w.shape[0]
         dev = x.device
         f32 = dict(dtype=torch.float32, device=dev)
         W = lambda t: _contig(t.detach()).view(t.shape[0], t.shape[1])       # Conv3d 1x1x1 weight -> [out, in]
         zW = W(wz_w)
+        if mode not in ("dot", "embedded", "gaussian", "concatenate"):
+            raise RuntimeError(f"TPAVI mode {mode!r} is not on the path (built: 'dot', 'embedded', 'gaussian', 'concatenate')")
+        npj = 1 if mode == "gaussian" else 3              # 'gaussian' projects g alone: its scores are x x^T
 
         # theta | phi | g in ONE contraction over the shared input: qkv[rows, 3*ci] (x is read once; the three
         # operands below are column slices with row stride 3*ci)
-        Wcat, bcat = _qkv_weights((th_w, ph_w, g_w, th_b, ph_b, g_b))         # [3*ci, c], [3*ci]
-        c3 = 3 * ci
+        Wcat, bcat = _qkv_weights((g_w, g_b) if npj == 1 else (th_w, ph_w, g_w, th_b, ph_b, g_b))      # [npj*ci, c], [npj*ci]
+        c3 = npj * ci
         qkv = torch.empty(rows, c3, **f32)
         am_x = amax_of(x)
         am_q = amax_slot(dev)                # max|qkv| from the epilogue: one bound for the theta | phi | g column slices
@@ -164,9 +193,9 @@ class TpaviFn(Function):
         gemm("nt", xa, wb, qkv, M=rows, N=c3, K=c, lda=c, ldb=c, ldc=c3, bias=bcat, amax_a=am_x, amax_b=am_wc, amax_c=am_q,
              a_packed=pa, b_packed=pb)
         ctx.x_packed = (xa, am_x) if (pa and packed_hit(x, am_x) is not None) else None      # retained while memory allows
-        ctx.qkv_owner = th_w                      # parameter the stacked operand (and its cached transpose) is keyed on
+        ctx.qkv_owner = g_w if npj == 1 else th_w    # parameter the stacked operand (and its cached transpose) is keyed on
         set_amax(qkv, am_q)
-        th, ph, g = qkv[:, 0:ci], qkv[:, ci:2 * ci], qkv[:, 2 * ci:]
+        th, ph, g = qkv[:, 0:ci], qkv[:, ci:2 * ci], qkv[:, (npj - 1) * ci:]
         bq = L * c3                                                          # batch (frame) stride inside qkv
 
         y = torch.empty(rows, ci, **f32)
@@ -215,8 +244,40 @@ class TpaviFn(Function):
                  amax_a=am_q, amax_b=am_q)
             check(lib.glf_softmax_rows(_p(att), n * L, L, _stream()), "softmax_rows")
             gemm("nn", att, g, y, M=L, N=ci, K=L, lda=L, ldb=c3, ldc=ci, batch=n, bsa=L * L, bsb=bq, bsc=L * ci)
+        elif mode == "gaussian" and gaussian_chunked_ok(ci):
+            # the 'embedded' frame-group route with theta = phi = x: S = x x^T over C, P = softmax(S) in place, y = P g
+            att = torch.empty(1, **f32)
+            x2 = x.view(rows, c)
+            lp = (L + 31) // 32 * 32
+            gpc = _frames_per_chunk(n, L)
+            S = torch.empty(gpc, L, lp, **f32)
+            gT = torch.empty(gpc, ci, lp, **f32)
+            one = _ones4(dev)[:1]
+            am_y = amax_slot(dev)
+            for f0 in range(0, n, gpc):
+                gc = min(gpc, n - f0)
+                _scores(x2, x2, f0, gc, L, lp, c, c, am_x, S)
+                _transposed(g, f0, gc, L, lp, ci, c3, gT)
+                gemm("nt", S, gT, y[f0 * L:], M=L, N=ci, K=lp, lda=lp, ldb=lp, ldc=ci, batch=gc, bsa=L * lp, bsb=ci * lp, bsc=L * ci,
+                     amax_a=one, amax_b=am_q, amax_c=am_y)
+            set_amax(y, am_y)
+            del S, gT
+        elif mode == "gaussian":
+            att = torch.empty(n, L, L, **f32)                                # softmax(x x^T), materialised (odd widths only)
+            x2 = x.view(rows, c)
+            gemm("nt", x2, x2, att, M=L, N=L, K=c, lda=c, ldb=c, ldc=L, batch=n, bsa=L * c, bsb=L * c, bsc=L * L, amax_a=am_x, amax_b=am_x)
+            check(lib.glf_softmax_rows(_p(att), n * L, L, _stream()), "softmax_rows")
+            gemm("nn", att, g, y, M=L, N=ci, K=L, lda=L, ldb=c3, ldc=ci, batch=n, bsa=L * L, bsb=bq, bsc=L * ci)
         else:
-            raise RuntimeError(f"TPAVI mode {mode!r} is not on the path (built: 'dot', 'embedded')")
+            # 'concatenate': a = theta w_theta, b = phi w_phi (one scalar per position), then ONE kernel forms the
+            # relu(a_i + b_j + c) tiles in LDS and contracts them with g; `att` keeps a | b for the backward pass
+            if not pair_relu_ok(ci):
+                raise RuntimeError(f"TPAVI mode 'concatenate' is built for Ci % 32 == 0, Ci <= 1024 (got {ci})")
+            wf = _contig(wf_w.detach()).view(2 * ci)
+            att = torch.empty(2, rows, **f32)
+            check(lib.glf_attn_pair_proj_fwd(_p(th), _p(ph), c3, _p(wf), _p(att[0]), _p(att[1]), rows, ci, _stream()), "attn_pair_proj_fwd")
+            pp = _pair_params(n, L, ci, c3, ci, ci, c3)
+            check(lib.glf_attn_pair_relu_fwd(_p(att[0]), _p(att[1]), _p(wf_b), _p(g), _p(y), C.byref(pp), _stream()), "attn_pair_relu_fwd")
 
         wz = torch.empty(rows, c, **f32)
         am_zw = amax_of(wz_w)
@@ -250,8 +311,9 @@ class TpaviFn(Function):
                                     _p(z), _p(rmu), _p(rrs), rows, c, _p(am_z), _stream()), "bn_res_ln_fwd")
         set_amax(z, am_z)
         ctx.save_for_backward(x, qkv, att, y, wz, mean, invstd, rmu, rrs, Wcat, zW, bn_g, bn_b, ln_g)
-        ctx.cfg = (n, L, c, ci, training, mode, tuple(th_w.shape), tuple(wz_w.shape))
+        ctx.cfg = (n, L, c, ci, training, mode, tuple(g_w.shape), tuple(wz_w.shape))
         ctx.owners = (wz_w,)                      # parameter owning zW (transposed-copy cache key)
+        ctx.wf = (wf_w, wf_b)
         return z
 
     @staticmethod
@@ -263,9 +325,11 @@ class TpaviFn(Function):
         dev = dz.device
         f32 = dict(dtype=torch.float32, device=dev)
         dz = _contig(dz)
-        c3 = 3 * ci
+        npj = 1 if mode == "gaussian" else 3
+        c3 = npj * ci
         bq = L * c3
-        th, ph, g = qkv[:, 0:ci], qkv[:, ci:2 * ci], qkv[:, 2 * ci:]
+        th, ph, g = qkv[:, 0:ci], qkv[:, ci:2 * ci], qkv[:, (npj - 1) * ci:]
+        dwf_w = dwf_b = None
 
         # LayerNorm backward -> du (gradient of u = BN(w) + x); it is also the residual's gradient
         du = torch.empty(rows, c, **f32)
@@ -320,7 +384,7 @@ class TpaviFn(Function):
 
         dqkv = torch.empty(rows, c3, **f32)                   # [d theta | d phi | d g], row stride 3*ci
         am_dq_slot = amax_slot(dev)                           # its three writers (below) all report into one slot
-        dth, dph, dg = dqkv[:, 0:ci], dqkv[:, ci:2 * ci], dqkv[:, 2 * ci:]
+        dth, dph, dg = dqkv[:, 0:ci], dqkv[:, ci:2 * ci], dqkv[:, (npj - 1) * ci:]
         bs = L * ci
         am_dy = amax_of(dy)
         if mode == "dot":
@@ -343,6 +407,67 @@ class TpaviFn(Function):
                 del dMT
             else:
                 gemm("nn", ph, dM, dg, M=L, N=ci, K=ci, lda=c3, ldb=ci, ldc=c3, batch=n, bsa=bq, bsb=ci * ci, bsc=bq, alpha=1.0 / L)
+        elif mode == "gaussian" and gaussian_chunked_ok(ci):
+            # per group of frames: P recomputed from x; dP = dY g^T; dg = P^T dY; dS = P (dP - rowsum(dP P)); x is BOTH operands of
+            # the scores, so dx (= du, which already holds the residual's gradient) += dS x + dS^T x
+            x2 = x.view(rows, c)
+            am_x = amax_of(x)
+            lp = (L + 31) // 32 * 32
+            gpc = _frames_per_chunk(n, L)
+            S = torch.empty(gpc, L, lp, **f32)
+            dP = torch.empty(gpc, L, lp, **f32)
+            xT = torch.empty(gpc, c, lp, **f32)
+            one = _ones4(dev)[:1]
+            for f0 in range(0, n, gpc):
+                gc = min(gpc, n - f0)
+                _scores(x2, x2, f0, gc, L, lp, c, c, am_x, S)
+                am_dP = amax_slot(dev)
+                gemm("nt", dy[f0 * L:], g[f0 * L:], dP, M=L, N=L, K=ci, lda=ci, ldb=c3, ldc=lp, batch=gc, bsa=bs, bsb=bq, bsc=L * lp,
+                     amax_a=am_dy, amax_b=am_q, amax_c=am_dP)
+                gemm("tn", S, dy[f0 * L:], dg[f0 * L:], M=L, N=ci, K=L, lda=lp, ldb=ci, ldc=c3, batch=gc, bsa=L * lp, bsb=bs, bsc=bq,
+                     amax_a=one, amax_b=am_dy, amax_c=am_dq_slot)
+                check(lib.glf_softmax_rows_bwd_ld(_p(S), _p(dP), gc * L, L, lp, _stream()), "softmax_rows_bwd_ld")       # dP <- dS
+                am_dS = amax_slot(dev)                                       # |dS| <= 2 max|dP| (as for 'embedded')
+                if am_dS is not None:
+                    check(lib.glf_amax_combine(_p(am_dP), None, 2.0, 0, _p(am_dS), _stream()), "amax_combine")
+                _transposed(x2, f0, gc, L, lp, c, c, xT)
+                gemm("nt", dP, xT, du[f0 * L:], M=L, N=c, K=lp, lda=lp, ldb=lp, ldc=c, batch=gc, bsa=L * lp, bsb=c * lp, bsc=L * c,
+                     accumulate=True, amax_a=am_dS, amax_b=am_x)
+                gemm("tn", dP, x2[f0 * L:], du[f0 * L:], M=L, N=c, K=L, lda=lp, ldb=c, ldc=c, batch=gc, bsa=L * lp, bsb=L * c, bsc=L * c,
+                     accumulate=True, amax_a=am_dS, amax_b=am_x)
+            if am_dq_slot is not None:
+                set_amax(dqkv, am_dq_slot)
+            del S, dP, xT
+        elif mode == "gaussian":
+            x2 = x.view(rows, c)
+            dP = torch.empty(n, L, L, **f32)
+            gemm("nt", dy, g, dP, M=L, N=L, K=ci, lda=ci, ldb=c3, ldc=L, batch=n, bsa=bs, bsb=bq, bsc=L * L, amax_a=am_dy, amax_b=am_q)
+            gemm("tn", att, dy, dg, M=L, N=ci, K=L, lda=L, ldb=ci, ldc=c3, batch=n, bsa=L * L, bsb=bs, bsc=bq,
+                 amax_a=amax_of(att), amax_b=am_dy)
+            check(lib.glf_softmax_rows_bwd(_p(att), _p(dP), n * L, L, _stream()), "softmax_rows_bwd")   # dP <- dS
+            gemm("nn", dP, x2, du, M=L, N=c, K=L, lda=L, ldb=c, ldc=c, batch=n, bsa=L * L, bsb=L * c, bsc=L * c, accumulate=True)
+            gemm("tn", dP, x2, du, M=L, N=c, K=L, lda=L, ldb=c, ldc=c, batch=n, bsa=L * L, bsb=L * c, bsc=L * c, accumulate=True,
+                 amax_a=amax_of(dP), amax_b=amax_of(x))
+            del dP
+        elif mode == "concatenate":
+            # dg, da, db, dc from the fused kernels (every element written once, fixed summation order), then the skinny ends:
+            # dtheta = da w_theta^T, dphi = db w_phi^T into dqkv, and W_f's gradient [theta^T da | phi^T db]
+            wf_w, wf_b = ctx.wf
+            wf = _contig(wf_w.detach()).view(2 * ci)
+            dab = torch.empty(2, rows, **f32)
+            dwf_w = torch.empty(2 * ci, **f32)
+            dwf_b = torch.empty(1, **f32)
+            pp = _pair_params(n, L, ci, c3, ci, ci, c3)
+            nb = int(lib.glf_attn_pair_relu_workspace_bytes(C.byref(pp)))
+            ws = torch.empty(nb // 4, **f32)
+            check(lib.glf_attn_pair_relu_bwd(_p(att[0]), _p(att[1]), _p(wf_b), _p(g), _p(dy), _p(dg), _p(dab[0]), _p(dab[1]), _p(dwf_b),
+                                             _p(ws), nb, C.byref(pp), _stream()), "attn_pair_relu_bwd")
+            nb = int(lib.glf_attn_pair_proj_workspace_bytes(rows, ci))
+            ws = torch.empty(nb // 4, **f32)
+            check(lib.glf_attn_pair_proj_bwd(_p(th), _p(ph), c3, _p(wf), _p(dab[0]), _p(dab[1]), _p(dth), _p(dph), c3, _p(dwf_w), _p(ws), nb,
+                                             rows, ci, _stream()), "attn_pair_proj_bwd")
+            dwf_w = dwf_w.view(wf_w.shape)
+            del ws, dab
         elif chunked_softmax_ok(ci, L):
             # per group of frames: P recomputed; dP = dY g^T; dg = P^T dY; dS = P (dP - rowsum(dP P)); dtheta = dS phi; dphi = dS^T theta
             lp = (L + 31) // 32 * 32
@@ -361,7 +486,8 @@ class TpaviFn(Function):
                      amax_a=one, amax_b=am_dy, amax_c=am_dq_slot)
                 check(lib.glf_softmax_rows_bwd_ld(_p(S), _p(dP), gc * L, L, lp, _stream()), "softmax_rows_bwd_ld")       # dP <- dS
                 am_dS = amax_slot(dev)                                       # |dS| <= P (|dP| + |sum dP P|) <= 2 max|dP|
-                check(lib.glf_amax_combine(_p(am_dP), None, 2.0, 0, _p(am_dS), _stream()), "amax_combine")
+                if am_dS is not None:
+                    check(lib.glf_amax_combine(_p(am_dP), None, 2.0, 0, _p(am_dS), _stream()), "amax_combine")
                 _transposed(ph, f0, gc, L, lp, ci, c3, phT)
                 gemm("nt", dP, phT, dth[f0 * L:], M=L, N=ci, K=lp, lda=lp, ldb=lp, ldc=c3, batch=gc, bsa=L * lp, bsb=ci * lp, bsc=bq,
                      amax_a=am_dS, amax_b=am_q, amax_c=am_dq_slot)
@@ -407,8 +533,10 @@ class TpaviFn(Function):
         xb, pb = pick(x, ctx.x_packed[0] if ctx.x_packed is not None else None, ok)
         gemm("tn", dq_a, xb, dWcat, M=c3, N=c, K=rows, lda=c3, ldb=c, ldc=c, split=sp, amax_a=am_dq, amax_b=am_x, a_packed=pa, b_packed=pb)
         dbcat = colsum(dqkv, rows, c3)
-        grads_w = [dWcat[i * ci:(i + 1) * ci].reshape(pshape) for i in range(3)]
-        grads_b = [dbcat[i * ci:(i + 1) * ci] for i in range(3)]
+        grads_w = [dWcat[i * ci:(i + 1) * ci].reshape(pshape) for i in range(npj)]
+        grads_b = [dbcat[i * ci:(i + 1) * ci] for i in range(npj)]
+        if npj == 1:                                         # 'gaussian': no theta / phi
+            grads_w, grads_b = [None, None] + grads_w, [None, None] + grads_b
         dx = du                                              # residual gradient, accumulated in place (one RMW)
         if split:
             WcatT = weight_T(Wcat, Wcat)                        # cached with the stacked operand (one rebuild per weight update)
@@ -422,7 +550,7 @@ class TpaviFn(Function):
             gemm("nn", dqkv, Wcat, dx, M=rows, N=c, K=c3, lda=c3, ldb=c, ldc=c, accumulate=True)
         dx = dx.view_as(x)
         return (dx, grads_w[0], grads_b[0], grads_w[1], grads_b[1], grads_w[2], grads_b[2], dzW.view(zshape), dzb,
-                dbn_g, dbn_b, dln_g, dln_b, None, None, None, None, None, None, None, None)
+                dbn_g, dbn_b, dln_g, dln_b, None, None, None, None, None, None, None, None, dwf_w, dwf_b)
 
 
 def tpavi_forward(x5: torch.Tensor, mod) -> torch.Tensor:
@@ -435,8 +563,13 @@ def tpavi_forward(x5: torch.Tensor, mod) -> torch.Tensor:
     if x5.dtype == torch.bfloat16:
         from .ops16 import Tpavi16Fn
         fn = Tpavi16Fn
-    return fn.apply(
-        x5, mod.theta.weight, mod.theta.bias, mod.phi.weight, mod.phi.bias, mod.g.weight, mod.g.bias,
-        mod.W_z[0].weight, mod.W_z[0].bias, bn.weight, bn.bias, mod.norm_layer.weight, mod.norm_layer.bias,
-        bn.running_mean, bn.running_var, bn.num_batches_tracked if training else None,
-        training, float(bn.momentum or 0.0), float(bn.eps), float(mod.norm_layer.eps), mod.mode)
+    theta, phi = getattr(mod, "theta", None), getattr(mod, "phi", None)          # 'gaussian' owns neither
+    args = (x5, theta.weight if theta is not None else None, theta.bias if theta is not None else None,
+            phi.weight if phi is not None else None, phi.bias if phi is not None else None, mod.g.weight, mod.g.bias,
+            mod.W_z[0].weight, mod.W_z[0].bias, bn.weight, bn.bias, mod.norm_layer.weight, mod.norm_layer.bias,
+            bn.running_mean, bn.running_var, bn.num_batches_tracked if training else None,
+            training, float(bn.momentum or 0.0), float(bn.eps), float(mod.norm_layer.eps), mod.mode)
+    if fn is TpaviFn:
+        wf = mod.W_f[0] if mod.mode == "concatenate" else None
+        args += (wf.weight if wf is not None else None, wf.bias if wf is not None else None)
+    return fn.apply(*args)

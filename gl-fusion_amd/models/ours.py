@@ -21,30 +21,34 @@ from .segmentation import deeplabv3_resnet50_iekd
 _FUSION_STREAMS = os.environ.get("GLF_FUSION_STREAMS", "1") != "0"
 
 class TPAVIModule(nn.Module):
-    """ours.py:770-917.  Built modes: 'dot' (shipped) and 'embedded' (softmax); dimension=3,
-    bn_layer=True.  forward(x [N,C,V,h,w]) -> (z [N,C,V,h,w], audio_temp=0)."""
+    """ours.py:770-917.  All four pairwise functions: 'dot' (shipped), 'embedded' (softmax), 'gaussian' (softmax of x x^T, no
+    theta / phi) and 'concatenate' (ReLU of a 1x1 convolution over [theta_i | phi_j]: W_f); dimension=3, bn_layer=True.
+    Parameters and state-dict keys per mode are the reference's.  forward(x [N,C,V,h,w]) -> (z [N,C,V,h,w], audio_temp=0)."""
 
     def __init__(self, in_channels: int, inter_channels=None, mode: str = "dot", dimension: int = 3, bn_layer: bool = True) -> None:
         super().__init__()
         if mode not in ("gaussian", "embedded", "dot", "concatenate"):
             raise ValueError("`mode` must be one of `gaussian`, `embedded`, `dot` or `concatenate`")
-        if mode not in ("dot", "embedded") or dimension != 3 or not bn_layer:
-            raise NotImplementedError("glfusion_amd builds TPAVIModule for mode in {'dot','embedded'}, dimension=3, bn_layer=True")
+        if dimension != 3 or not bn_layer:
+            raise NotImplementedError("glfusion_amd builds TPAVIModule for dimension=3, bn_layer=True")
         self.mode, self.dimension = mode, dimension
         self.in_channels = in_channels
         self.inter_channels = inter_channels
         if self.inter_channels is None:
             self.inter_channels = in_channels // 2 or 1
         ci = self.inter_channels
-        # registration order == the reference's (state_dict key order): align_channel, norm_layer, g, W_z, theta, phi
+        # registration order == the reference's (state_dict key order): align_channel, norm_layer, g, W_z, theta, phi, W_f
         self.align_channel = nn.Linear(128, in_channels)        # dead for this model (audio branch)
         self.norm_layer = nn.LayerNorm(in_channels)
         self.g = nn.Conv3d(in_channels, ci, kernel_size=1)
         self.W_z = nn.Sequential(nn.Conv3d(ci, in_channels, kernel_size=1), nn.BatchNorm3d(in_channels))
         nn.init.constant_(self.W_z[1].weight, 0)
         nn.init.constant_(self.W_z[1].bias, 0)
-        self.theta = nn.Conv3d(in_channels, ci, kernel_size=1)
-        self.phi = nn.Conv3d(in_channels, ci, kernel_size=1)
+        if mode != "gaussian":                                   # 'gaussian' scores x against x: it owns no theta / phi
+            self.theta = nn.Conv3d(in_channels, ci, kernel_size=1)
+            self.phi = nn.Conv3d(in_channels, ci, kernel_size=1)
+        if mode == "concatenate":
+            self.W_f = nn.Sequential(nn.Conv2d(2 * ci, 1, kernel_size=1), nn.ReLU())
 
     def forward_nvhwc(self, x5: torch.Tensor) -> torch.Tensor:
         """x5: [N, V, h, w, C] channels-last."""

@@ -325,6 +325,47 @@ int glf_s16_attn_softmax_bwd(const void* theta, const void* phi, const void* g, 
                              const glf_attn_params* p, glf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Fused pairwise-ReLU attention of TPAVIModule's `concatenate` mode (ours.py:883-894, 898-900, 902):
+ *   s_ij = a[i] + b[j] + c ;  y[n][i] = (1 / L) sum_j relu(s_ij) g[n][j]      per frame n,
+ * a = theta w_theta and b = phi w_phi being ONE scalar per position ([w_theta | w_phi] = the W_f.0.weight row, c = W_f.0.bias).
+ * a, b: [frames*L] fp32; c: a DEVICE scalar (no host synchronisation); g: [L][Ci] rows per frame with row stride ldg (a
+ * column slice of a wider buffer).  The 64 x 64 tiles of relu(s) are computed on the VALU, left in LDS and contracted with the
+ * g rows into MFMA accumulators: nothing of size L x L is written.  Exact fp32 arithmetic (v_mfma_f32_32x32x2_f32) under
+ * every precision setting.  Ci % 32 == 0, Ci <= 1024, any L >= 1; frame n of g / y / dy / dg starts L rows after frame n - 1.
+ * Backward: dg (row stride lddg), da, db [frames*L] and dc [1] from dy (row stride lddy; g and dy 16-byte aligned, ldg and
+ * lddy multiples of 4).  Every output element is written exactly once, no atomics, no zero fill; da, db and dc are summed in
+ * a fixed order, so two runs are bitwise equal.  workspace: caller-owned, glf_attn_pair_relu_workspace_bytes() bytes
+ * (one partial row of db per 64-query block: frames * ceil(L / 64) * L floats).
+ * Arguments are checked before any HIP runtime call: GLF_ERR_NULL, GLF_ERR_BAD_SHAPE, GLF_ERR_UNSUPPORTED (Ci),
+ * GLF_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t frames, L, ci;
+    int32_t reserved0;
+    int64_t ldg;                /* row stride of g (elements)   */
+    int64_t ldy;                /* row stride of y              */
+    int64_t lddy;               /* backward: row stride of dy   */
+    int64_t lddg;               /* backward: row stride of dg   */
+} glf_attn_pair_params;
+size_t glf_sizeof_attn_pair_params(void);
+size_t glf_attn_pair_relu_workspace_bytes(const glf_attn_pair_params* p);
+int glf_attn_pair_relu_fwd(const float* a, const float* b, const float* c, const float* g, float* y,
+                           const glf_attn_pair_params* p, glf_stream_t stream);
+int glf_attn_pair_relu_bwd(const float* a, const float* b, const float* c, const float* g, const float* dy, float* dg,
+                           float* da, float* db, float* dc, float* workspace, int64_t workspace_bytes,
+                           const glf_attn_pair_params* p, glf_stream_t stream);
+/* The skinny ends of the mode.  Forward: a[r] = theta[r] . w[0 .. Ci), b[r] = phi[r] . w[Ci .. 2 Ci) for rows of stride ld.
+ * Backward: dtheta[r] = da[r] w[0 .. Ci), dphi[r] = db[r] w[Ci .. 2 Ci) (row stride ldd) and dw[2 Ci] = [theta^T da | phi^T db],
+ * summed over slabs of 256 rows and then over the slabs in order, in double (bitwise reproducible).  workspace: caller-owned,
+ * glf_attn_pair_proj_workspace_bytes(rows, Ci) bytes. */
+size_t glf_attn_pair_proj_workspace_bytes(int64_t rows, int ci);
+int glf_attn_pair_proj_fwd(const float* theta, const float* phi, int64_t ld, const float* w, float* a, float* b, int64_t rows, int ci,
+                           glf_stream_t stream);
+int glf_attn_pair_proj_bwd(const float* theta, const float* phi, int64_t ld, const float* w, const float* da, const float* db,
+                           float* dtheta, float* dphi, int64_t ldd, float* dw, float* workspace, int64_t workspace_bytes, int64_t rows,
+                           int ci, glf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Weight layout: torch OIHW [Cout][Cin][kh][kw] <-> tap-major [kh*kw][Cout][Cin].
  * ------------------------------------------------------------------------------------- */
 int glf_oihw_to_tap_major(const float* w, float* out, int cout, int cin, int taps, glf_stream_t s);
