@@ -10,6 +10,7 @@ int init_gemm_attrs();   // gemm_f32.hip
 int init_attn_attrs();   // attn_softmax.hip
 int init_gemm_s16_attrs();   // gemm_s16.hip
 int init_attn_s16_attrs();   // attn_s16.hip
+int init_attn_pair_s16_attrs();   // attn_pair_s16.hip
 
 char* err_buf() {
     static thread_local char buf[512] = {0};
@@ -98,6 +99,7 @@ int ensure_init() {
         if (int rc = init_attn_attrs()) return rc;
         if (int rc = init_gemm_s16_attrs()) return rc;
         if (int rc = init_attn_s16_attrs()) return rc;
+        if (int rc = init_attn_pair_s16_attrs()) return rc;
         e = hipMalloc(reinterpret_cast<void**>(&st.zeros), ZERO_PAGE_FLOATS * sizeof(float));
         if (e == hipSuccess) e = hipMemset(st.zeros, 0, ZERO_PAGE_FLOATS * sizeof(float));
         if (e != hipSuccess) return fail(GLF_ERR_WORKSPACE, "hipMalloc(zero page): %s", hipGetErrorString(e));

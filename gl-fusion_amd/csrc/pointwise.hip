@@ -99,6 +99,26 @@ __global__ __launch_bounds__(256) void transpose2d_strided_kernel(const float* _
     }
 }
 
+// ... and for 16-bit elements (64 x 64 tiles): the g^T / x^T / dS^T operands of 'gaussian' under 16-bit storage (ops16.py)
+__global__ __launch_bounds__(256) void s16_transpose2d_strided_kernel(const u16* __restrict__ src, long long ld_src, long long bs_src,
+                                                                      u16* __restrict__ dst, long long ld_dst, long long bs_dst, int rows, int cols,
+                                                                      int rows_pad) {
+    __shared__ u16 tile[64][66];
+    const u16* sb = src + (long long)blockIdx.z * bs_src;
+    u16* db = dst + (long long)blockIdx.z * bs_dst;
+    const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (int i = ty; i < 64; i += 4) {
+        const int r = r0 + i, c = c0 + tx;
+        tile[i][tx] = (r < rows && c < cols) ? sb[(long long)r * ld_src + c] : (u16)0;
+    }
+    __syncthreads();
+    for (int i = ty; i < 64; i += 4) {
+        const int c = c0 + i, r = r0 + tx;
+        if (c < cols && r < rows_pad) db[(long long)c * ld_dst + r] = tile[tx][i];
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // stem 7x7, Cin = 1.  One workgroup = 16x16 output pixels; the 22x22 input patch and the
 // 49 x Cout weights sit in LDS; each thread owns one pixel x 16 output channels per pass.
@@ -786,6 +806,18 @@ extern "C" int glf_transpose2d_strided(const float* src, int64_t ld_src, int64_t
     hipLaunchKernelGGL(transpose2d_strided_kernel, dim3((cols + 31) / 32, (rows_pad + 31) / 32, batch), dim3(256), 0, glf::S(s), src, (long long)ld_src,
                        (long long)batch_stride_src, dst, (long long)ld_dst, (long long)batch_stride_dst, rows, cols, rows_pad);
     return glf::check_launch("transpose2d_strided");
+}
+
+extern "C" int glf_s16_transpose2d_strided(const void* src, int64_t ld_src, int64_t batch_stride_src, void* dst, int64_t ld_dst,
+                                           int64_t batch_stride_dst, int rows, int cols, int rows_pad, int batch, glf_stream_t s) {
+    GLF_REQUIRE(src && dst, GLF_ERR_NULL, "s16_transpose2d_strided: null argument");
+    GLF_REQUIRE(rows > 0 && cols > 0 && batch > 0 && batch <= 65535 && rows_pad >= rows && (rows_pad + 63) / 64 <= 65535 && ld_src >= cols &&
+                ld_dst >= rows_pad, GLF_ERR_BAD_SHAPE, "s16_transpose2d_strided: bad shape");
+    if (int rc = glf::ensure_init()) return rc;
+    hipLaunchKernelGGL(s16_transpose2d_strided_kernel, dim3((cols + 63) / 64, (rows_pad + 63) / 64, batch), dim3(256), 0, glf::S(s),
+                       static_cast<const u16*>(src), (long long)ld_src, (long long)batch_stride_src, static_cast<u16*>(dst), (long long)ld_dst,
+                       (long long)batch_stride_dst, rows, cols, rows_pad);
+    return glf::check_launch("s16_transpose2d_strided");
 }
 
 extern "C" int glf_stem7x7_fwd(const float* x, const float* w, const float* bias, float* y,

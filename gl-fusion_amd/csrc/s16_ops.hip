@@ -588,6 +588,111 @@ __global__ __launch_bounds__(256) void s16_from_f32_kernel(const float* __restri
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n8; i += (long long)gridDim.x * blockDim.x) st8(y + i * 8, ldf8(x + i * 8));
 }
 
+// ----------------------------------------------------------------------------------------------------------------------
+// row softmax of fp32 scores into a bf16 operand ('gaussian' under 16-bit storage, ops16.py): P = softmax(S) and
+// dS = P o (dP - rowsum(P o dP)) with P recomputed from the scores.  TPR threads per row (one wavefront, or the whole
+// workgroup for long rows), 8 columns per thread and access; row max / sum (/ sum of P dP) as ONE online pass in fp32, merged
+// in a fixed order, then the normalising pass; bf16 once, at the store; the pad columns [cols, ld) are written as zero.
+// ----------------------------------------------------------------------------------------------------------------------
+struct SmStat { float m, l, d; };      // running maximum, sum of exp(s - m), sum of exp(s - m) dp
+__device__ __forceinline__ SmStat sm_merge(const SmStat x, const SmStat y) {
+    const float m = fmaxf(x.m, y.m);
+    if (m == -INFINITY) return SmStat{m, 0.f, 0.f};
+    const float ax = __expf(x.m - m), ay = __expf(y.m - m);
+    return SmStat{m, x.l * ax + y.l * ay, x.d * ax + y.d * ay};
+}
+// columns c0 .. c0 + 7 of a row, `fill` at and beyond cols
+__device__ __forceinline__ F8 sm_ld8(const float* __restrict__ r, int c0, int cols, float fill) {
+    if (c0 + 8 <= cols) return ldf8(r + c0);
+    F8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o.v[e] = c0 + e < cols ? r[c0 + e] : fill;
+    return o;
+}
+template <int TPR, bool BWD>
+__device__ __forceinline__ SmStat sm_row_stats(const float* __restrict__ srow, const float* __restrict__ dprow, int cols, int t, SmStat* red) {
+    SmStat st{-INFINITY, 0.f, 0.f};
+    for (int c0 = 8 * t; c0 < cols; c0 += 8 * TPR) {
+        const F8 x = sm_ld8(srow, c0, cols, -INFINITY);
+        F8 dp;
+        if (BWD) dp = sm_ld8(dprow, c0, cols, 0.f);
+        float gm = x.v[0];
+#pragma unroll
+        for (int e = 1; e < 8; ++e) gm = fmaxf(gm, x.v[e]);
+        SmStat g{gm, 0.f, 0.f};                            // (column c0 < cols: the group's maximum is finite)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float p = __expf(x.v[e] - gm);
+            g.l += p;
+            if (BWD) g.d = fmaf(p, dp.v[e], g.d);
+        }
+        st = sm_merge(st, g);
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        SmStat y;
+        y.m = __shfl_xor(st.m, o, 64); y.l = __shfl_xor(st.l, o, 64); y.d = __shfl_xor(st.d, o, 64);
+        st = sm_merge(st, y);
+    }
+    // one value per wavefront: with contracted multiply-adds the two lanes of a butterfly pair can differ in the last bit
+    st.m = __shfl(st.m, 0, 64); st.l = __shfl(st.l, 0, 64); st.d = __shfl(st.d, 0, 64);
+    if (TPR > 64) {                                        // one row per workgroup: the four wavefronts' results, in wave order
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = st;
+        __syncthreads();
+        st = sm_merge(sm_merge(red[0], red[1]), sm_merge(red[2], red[3]));
+    }
+    return st;
+}
+template <int TPR, bool BWD>
+__global__ __launch_bounds__(256) void s16_softmax_rows_kernel(const float* __restrict__ s, const float* __restrict__ dp, u16* __restrict__ out,
+                                                               long long rows, int cols, long long ld_s, long long ld_dp, long long ld_o) {
+    __shared__ SmStat red[4];
+    const int t = threadIdx.x % TPR;
+    const long long row = (long long)blockIdx.x * (256 / TPR) + threadIdx.x / TPR;
+    if (row >= rows) return;                               // (whole wavefronts; TPR = 256 launches exactly `rows` workgroups)
+    const float* __restrict__ srow = s + row * ld_s;
+    const float* __restrict__ dprow = BWD ? dp + row * ld_dp : nullptr;
+    const SmStat st = sm_row_stats<TPR, BWD>(srow, dprow, cols, t, red);
+    const float inv = 1.f / st.l, dsum = st.d * inv;
+    u16* __restrict__ orow = out + row * ld_o;
+    for (int c0 = 8 * t; c0 < (int)ld_o; c0 += 8 * TPR) {
+        F8 o;
+        if (c0 < cols) {
+            const F8 x = sm_ld8(srow, c0, cols, -INFINITY);
+            F8 d;
+            if (BWD) d = sm_ld8(dprow, c0, cols, 0.f);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float p = __expf(x.v[e] - st.m) * inv;   // 0 at and beyond cols
+                o.v[e] = BWD ? p * (d.v[e] - dsum) : p;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o.v[e] = 0.f;
+        }
+        st8(orow + c0, o);
+    }
+}
+
+int softmax16_check(const void* s, const void* dp, const void* out, int64_t rows, int cols, int64_t ld_s, int64_t ld_dp, int64_t ld_o, bool bwd,
+                    const char* who) {
+    GLF_REQUIRE(s && out && (!bwd || dp), GLF_ERR_NULL, "%s: null argument", who);
+    GLF_REQUIRE(rows > 0 && rows < (1LL << 31) && cols > 0 && ld_s >= cols && ld_o >= cols && ld_o < (1LL << 31) && (!bwd || ld_dp >= cols),
+                GLF_ERR_BAD_SHAPE, "%s: rows (%lld) / cols (%d) / row strides out of range", who, (long long)rows, cols);
+    GLF_REQUIRE(ld_s % 4 == 0 && ld_o % 8 == 0 && al16(s) && al16(out) && (!bwd || (ld_dp % 4 == 0 && al16(dp))), GLF_ERR_UNSUPPORTED,
+                "%s: fp32 row strides must be multiples of 4, the bf16 row stride a multiple of 8, every operand 16-byte aligned", who);
+    return GLF_OK;
+}
+template <bool BWD>
+void softmax16_launch(const float* s, const float* dp, void* out, int64_t rows, int cols, int64_t ld_s, int64_t ld_dp, int64_t ld_o, glf_stream_t st) {
+    if (cols <= 1024)
+        hipLaunchKernelGGL((s16_softmax_rows_kernel<64, BWD>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, glf::S(st), s, dp, static_cast<u16*>(out),
+                           (long long)rows, cols, (long long)ld_s, (long long)ld_dp, (long long)ld_o);
+    else
+        hipLaunchKernelGGL((s16_softmax_rows_kernel<256, BWD>), dim3((unsigned)rows), dim3(256), 0, glf::S(st), s, dp, static_cast<u16*>(out),
+                           (long long)rows, cols, (long long)ld_s, (long long)ld_dp, (long long)ld_o);
+}
+
 }  // namespace
 
 extern "C" int glf_s16_colstats(const void* x, int ldx, int rows, int c, double* sums, glf_stream_t s) {
@@ -712,4 +817,18 @@ extern "C" int glf_s16_cast(const void* src, int src_dtype, void* dst, int dst_d
     else
         return glf::fail(GLF_ERR_UNSUPPORTED, "s16_cast: built for bf16 -> f32 and f32 -> bf16");
     return glf::check_launch("s16_cast");
+}
+
+extern "C" int glf_s16_softmax_rows_fwd(const float* s, void* p, int64_t rows, int cols, int64_t ld_s, int64_t ld_p, glf_stream_t stream) {
+    if (int rc = softmax16_check(s, nullptr, p, rows, cols, ld_s, 0, ld_p, false, "s16_softmax_rows_fwd")) return rc;
+    if (int rc = glf::ensure_init()) return rc;
+    softmax16_launch<false>(s, nullptr, p, rows, cols, ld_s, 0, ld_p, stream);
+    return glf::check_launch("s16_softmax_rows_fwd");
+}
+extern "C" int glf_s16_softmax_rows_bwd(const float* s, const float* dp, void* ds, int64_t rows, int cols, int64_t ld_s, int64_t ld_dp, int64_t ld_ds,
+                                        glf_stream_t stream) {
+    if (int rc = softmax16_check(s, dp, ds, rows, cols, ld_s, ld_dp, ld_ds, true, "s16_softmax_rows_bwd")) return rc;
+    if (int rc = glf::ensure_init()) return rc;
+    softmax16_launch<true>(s, dp, ds, rows, cols, ld_s, ld_dp, ld_ds, stream);
+    return glf::check_launch("s16_softmax_rows_bwd");
 }

@@ -569,7 +569,6 @@ def tpavi_forward(x5: torch.Tensor, mod) -> torch.Tensor:
             mod.W_z[0].weight, mod.W_z[0].bias, bn.weight, bn.bias, mod.norm_layer.weight, mod.norm_layer.bias,
             bn.running_mean, bn.running_var, bn.num_batches_tracked if training else None,
             training, float(bn.momentum or 0.0), float(bn.eps), float(mod.norm_layer.eps), mod.mode)
-    if fn is TpaviFn:
-        wf = mod.W_f[0] if mod.mode == "concatenate" else None
-        args += (wf.weight if wf is not None else None, wf.bias if wf is not None else None)
+    wf = mod.W_f[0] if mod.mode == "concatenate" else None
+    args += (wf.weight if wf is not None else None, wf.bias if wf is not None else None)
     return fn.apply(*args)

@@ -364,6 +364,30 @@ int glf_attn_pair_proj_fwd(const float* theta, const float* phi, int64_t ld, con
 int glf_attn_pair_proj_bwd(const float* theta, const float* phi, int64_t ld, const float* w, const float* da, const float* db,
                            float* dtheta, float* dphi, int64_t ldd, float* dw, float* workspace, int64_t workspace_bytes, int64_t rows,
                            int ci, glf_stream_t stream);
+/* The same mode under 16-bit storage (csrc/attn_pair_s16.hip): g, y, dy, dg (and theta, phi, dtheta, dphi of the skinny ends) are
+ * bf16 (void* = bf16 data); a, b, da, db, dc, w, dw and the workspaces stay fp32, so all three kernels evaluate
+ * s = (a_i + b_j) + c in fp32 and the backward mask is the forward's.  The relu(s) tile is computed in fp32 and rounded to bf16
+ * only as the A operand of v_mfma_f32_32x32x16_bf16; y and dg are accumulated in fp32, scaled by 1 / L in fp32 and stored as bf16
+ * once; t = dY g^T on the bf16 MFMA with fp32 accumulation, masked in fp32, summed to da / db / dc in a fixed order (dc: a fixed
+ * tree in double).  Every output element is written exactly once (no atomics, no zero fill: bitwise reproducible); the calls
+ * allocate nothing and never wait on the host.  Ci % 64 == 0, Ci <= 1024, any L >= 1; every row stride a multiple of 8 elements
+ * and >= Ci, g / dy 16-byte aligned.  Workspaces as for the fp32 entry points (their own *_workspace_bytes functions).
+ * Arguments are checked before any HIP runtime call, in this order: GLF_ERR_NULL, GLF_ERR_BAD_SHAPE (extents),
+ * GLF_ERR_UNSUPPORTED (Ci, strides, alignment), GLF_ERR_WORKSPACE. */
+size_t glf_s16_attn_pair_relu_workspace_bytes(const glf_attn_pair_params* p);
+int glf_s16_attn_pair_relu_fwd(const float* a, const float* b, const float* c, const void* g, void* y,
+                               const glf_attn_pair_params* p, glf_stream_t stream);
+int glf_s16_attn_pair_relu_bwd(const float* a, const float* b, const float* c, const void* g, const void* dy, void* dg,
+                               float* da, float* db, float* dc, float* workspace, int64_t workspace_bytes,
+                               const glf_attn_pair_params* p, glf_stream_t stream);
+/* a = theta w_theta, b = phi w_phi from bf16 rows and the fp32 W_f row (fp32 sums, one wavefront per row; Ci and ld multiples of
+ * 8); dtheta = da w_theta^T, dphi = db w_phi^T stored as bf16 (row stride ldd), dw fp32 over 256-row slabs added in order in double. */
+size_t glf_s16_attn_pair_proj_workspace_bytes(int64_t rows, int ci);
+int glf_s16_attn_pair_proj_fwd(const void* theta, const void* phi, int64_t ld, const float* w, float* a, float* b, int64_t rows, int ci,
+                               glf_stream_t stream);
+int glf_s16_attn_pair_proj_bwd(const void* theta, const void* phi, int64_t ld, const float* w, const float* da, const float* db,
+                               void* dtheta, void* dphi, int64_t ldd, float* dw, float* workspace, int64_t workspace_bytes, int64_t rows,
+                               int ci, glf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Weight layout: torch OIHW [Cout][Cin][kh][kw] <-> tap-major [kh*kw][Cout][Cin].
@@ -497,6 +521,20 @@ int glf_s16_add_n(const void* const* inputs, int k, void* out, int64_t numel, gl
 int glf_s16_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t numel, glf_stream_t s);
 /* dst[b][c][r] = src[b][r][c] for 16-bit elements. */
 int glf_s16_transpose2d(const void* src, void* dst, int rows, int cols, int batch, glf_stream_t s);
+/* glf_transpose2d_strided for 16-bit elements: dst[b][c][r] (row stride ld_dst) = src[b][r][c] (row stride ld_src) for r < rows,
+ * ZERO for rows <= r < rows_pad. */
+int glf_s16_transpose2d_strided(const void* src, int64_t ld_src, int64_t batch_stride_src, void* dst, int64_t ld_dst,
+                                int64_t batch_stride_dst, int rows, int cols, int rows_pad, int batch, glf_stream_t s);
+/* Row softmax of fp32 scores into a bf16 contraction operand ('gaussian' under 16-bit storage):
+ *   fwd: p[r][c] = softmax_c(s[r][0 .. cols));   bwd: ds[r][c] = P (dp - rowsum(P o dp)) with P recomputed from s in fp32.
+ * Row max / sum / normalisation in fp32, one rounding to bf16 at the store; the pad columns [cols, ld_p) / [cols, ld_ds) are
+ * written as ZERO (the operand's reduction extent is padded to the contraction kernels' K granule).  16-byte accesses, one row
+ * per wavefront (cols <= 1024) or per workgroup, no atomics: bitwise reproducible.  fp32 row strides multiples of 4, the bf16
+ * row stride a multiple of 8, all >= cols, every operand 16-byte aligned.  Checked before any HIP runtime call: GLF_ERR_NULL,
+ * GLF_ERR_BAD_SHAPE, GLF_ERR_UNSUPPORTED. */
+int glf_s16_softmax_rows_fwd(const float* s, void* p, int64_t rows, int cols, int64_t ld_s, int64_t ld_p, glf_stream_t stream);
+int glf_s16_softmax_rows_bwd(const float* s, const float* dp, void* ds, int64_t rows, int cols, int64_t ld_s, int64_t ld_dp,
+                             int64_t ld_ds, glf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Single-call fusion block, 16-bit storage (SURVEY 8b rows tpavi_proj + tpavi_attn_dot +
