@@ -1,6 +1,6 @@
 """Caller-side harness with the reference Trainer's surface (main.py:63-883) for the hot path:
 `Trainer(config)`, `.train(is_backbone, is_cycle)`, `.eval(net_path, is_fuse, raw_data)`,
-`_calculate_overlap_metrics`, `save()`.  The reference's data layer needs NIfTI files that are not
+`_calculate_overlap_metrics`, `save()`, `load()`.  The reference's data layer needs NIfTI files that are not
 shipped (absolute paths on the authors' machine), so loaders here produce synthetic clips with
 the reference's tensor contract: images [N,1,112,112] in [0,1], masks [N,5,112,112] in {0,1}
 (datasets/loader.py:298-330); the unlabelled "video" loader of the cycle term yields clips of `clip_length`
@@ -10,14 +10,16 @@ frames per view (main.py:213-218).  `is_cycle=True` adds the temporal cycle-cons
 from __future__ import annotations
 
 import functools
+import glob
 import os
+import warnings
 from typing import Dict, Iterator, Tuple
 
 import torch
 
 from . import ops
 from .ddp import GradAllReducer, all_reduce_counts
-from .optim import Adam
+from .optim import SGD, Adam
 from .models import Global_and_Local
 
 
@@ -177,10 +179,21 @@ class Trainer:
         self.fold_bn_s16 = bool(tr.get("fold_bn_s16", False))
         self.model = Global_and_Local(view_num=self.view_num).to(self.device)  # main.py:150
         opt = config["net"]["opt"]
-        if opt.get("opt_name", "Adam") != "Adam":
-            raise NotImplementedError("glfusion_amd: only the Adam branch of main.py:158-165 is built (the shipped config)")
-        self.optimizer = Adam(self.model.parameters(), lr=opt["lr"], weight_decay=opt["weight_decay"])    # main.py:162-165, fused
+        name = opt.get("opt_name", "Adam")
+        if name == "SGD":
+            # main.py:159-161 (plain SGD), fused; opt['momentum'] / opt['dampening'] / opt['nesterov'] have no reference counterpart, absent = off
+            self.optimizer = SGD(self.model.parameters(), lr=opt["lr"], weight_decay=opt["weight_decay"], momentum=opt.get("momentum", 0),
+                                 dampening=opt.get("dampening", 0), nesterov=bool(opt.get("nesterov", False)))
+        elif name == "Adam":
+            self.optimizer = Adam(self.model.parameters(), lr=opt["lr"], weight_decay=opt["weight_decay"])    # main.py:162-165, fused
+        else:
+            raise ValueError(f"glfusion_amd: config['net']['opt']['opt_name'] = {name!r}; main.py:158-165 has the branches 'SGD' and 'Adam'")
         self.scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.optimizer, T_max=tr["num_epochs"])   # main.py:168
+        # config['train']['save_optimizer'] (absent = False): save() also writes opt_%05d.pth, the file load() resumes the optimizer from
+        self.save_optimizer = bool(tr.get("save_optimizer", False))
+        self.latest_epoch = 0                                                   # first epoch train() runs; load() moves it
+        if tr.get("is_load", False):                                            # main.py:74, 153
+            self.load()
         self.reducer = GradAllReducer(self.model)
         self.reducer.broadcast_parameters(0)
         frames = tr["batch_size"] * tr.get("frames_per_clip", 1)
@@ -210,7 +223,9 @@ class Trainer:
 
     def _graph_step(self, imgs, masks):
         """The segmentation step (no cycle term) replayed from ONE hipGraph (StepGraph): the batch is copied into static input
-        buffers, the recorded forward + loss + backward (+ weight-image refresh) runs, Adam updates the parameters in place.
+        buffers, the recorded forward + loss + backward (+ weight-image refresh) runs, the optimizer updates the parameters in place.
+        The optimizer step is NOT part of the recorded work, so either optimizer (fused Adam or fused SGD) runs behind the same graph:
+        both write the parameters through their existing addresses, and their state lives outside the graph's memory pool.
         Recorded at the first call; the batch shape must not change afterwards."""
         if self._graph is None:
             self._static = ({v: torch.empty_like(t) for v, t in imgs.items()}, {v: torch.empty_like(t) for v, t in masks.items()})
@@ -240,7 +255,7 @@ class Trainer:
         return loss, self._graph_pred
 
     def train_step(self, imgs, masks, video=None) -> torch.Tensor:
-        """main.py:202-243: forward, sum_v BCE-sum (+ 1e-2 x cycle loss on `video`), backward, Adam step."""
+        """main.py:202-243: forward, sum_v BCE-sum (+ 1e-2 x cycle loss on `video`), backward, optimizer step."""
         if video is None and self.use_graph:
             return self._graph_step(imgs, masks)
         pred_frames, _, _, _ = self.model(imgs)
@@ -257,7 +272,7 @@ class Trainer:
         return loss.detach(), pred_frames
 
     def train(self, is_backbone: bool = False, is_cycle: bool = True):
-        for epoch in range(self.config["train"]["num_epochs"]):
+        for epoch in range(self.latest_epoch, self.config["train"]["num_epochs"]):
             self.model.train()
             for imgs, masks in self.loader:
                 video = self.video_loader.batch()[0] if is_cycle else None
@@ -401,11 +416,53 @@ class Trainer:
         return ops.overlap_metrics_from_counts(counts, eps)
 
     def save(self, epoch: int):
-        """main.py:857-872: {'network': state_dict} -> save_dir/net_%05d.pth + latest.ckpt."""
+        """main.py:857-872: {'network': state_dict} -> save_dir/net_%05d.pth + latest.ckpt; with config['train']['save_optimizer']
+        also {'epoch', 'optimizer': state_dict} -> opt_%05d.pth (the lines main.py:869-870 carries commented out; load() reads it)."""
         if not self.print_val:
             return
         d = self.config["train"]["save_dir"]
         os.makedirs(d, exist_ok=True)
         torch.save({"network": self.model.state_dict()}, os.path.join(d, "net_%05d.pth" % epoch))
+        if self.save_optimizer:
+            torch.save({"epoch": epoch, "optimizer": self.optimizer.state_dict()}, os.path.join(d, "opt_%05d.pth" % epoch))
         with open(os.path.join(d, "latest.ckpt"), "w") as f:
             f.write("%05d\n" % epoch)                              # main.py:869: `echo 00005 > latest.ckpt` (zero-padded, newline)
+
+    def load(self):
+        """main.py:823-855: resume from config['train']['save_dir'].  The latest epoch is the last line of latest.ckpt, else the
+        highest net_*.pth; net_%05d.pth is loaded with strict=True, opt_%05d.pth into the optimizer when it exists (a checkpoint
+        saved without config['train']['save_optimizer'] has none: one warning, the optimizer starts fresh).  train() then continues
+        at the epoch after it, with the learning rate an uninterrupted run would have there: the scheduler takes the same
+        `latest_epoch` steps from the base rate, so the recursion of CosineAnnealingLR yields the same bits.  Nothing found: one
+        warning, `latest_epoch` stays 0."""
+        d = self.config["train"]["save_dir"]
+        latest = None
+        if os.path.isfile(os.path.join(d, "latest.ckpt")):
+            with open(os.path.join(d, "latest.ckpt")) as f:
+                lines = f.read().split()
+            latest = int(lines[-1]) if lines else None
+        if latest is None:
+            found = [int(os.path.basename(q)[4:-4]) for q in glob.glob(os.path.join(d, "net_*.pth")) if os.path.basename(q)[4:-4].isdigit()]
+            latest = max(found) if found else None
+        if latest is None:
+            if self.print_val:
+                print(f"Warning: no trained model found in {d}. An initialized model will be used.")
+            self.latest_epoch = 0
+            return
+        net_path, opt_path = os.path.join(d, "net_%05d.pth" % latest), os.path.join(d, "opt_%05d.pth" % latest)
+        if self.print_val:
+            print(f"Loading model from {net_path}...")
+        self.model.load_state_dict(torch.load(net_path, map_location=self.device)["network"], strict=True)
+        if os.path.isfile(opt_path):
+            self.optimizer.load_state_dict(torch.load(opt_path, map_location=self.device)["optimizer"])
+        elif self.print_val:
+            print(f"Warning: {opt_path} not found (saved without config['train']['save_optimizer']); the optimizer starts fresh.")
+        ops.refresh_weights()                                      # load_state_dict copies in place: no stale weight image survives
+        self.latest_epoch = latest + 1
+        # the saved param_groups carry the rate of the moment of saving; the scheduler built in __init__ stands at step 0
+        for group, base in zip(self.optimizer.param_groups, self.scheduler.base_lrs):
+            group["lr"] = base
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)           # "lr_scheduler.step() before optimizer.step()": intended here
+            for _ in range(self.latest_epoch):
+                self.scheduler.step()

@@ -6,6 +6,10 @@ parameter -- optimizer checkpoints are interchangeable with torch.optim.Adam's),
 that has a gradient with ONE kernel launch per (param group, step count) (glf_adam_step) instead of ~1 500 small
 ATen kernels.  Parameters without a gradient are skipped and get no state, exactly as in torch (the dead
 `network.*` template and `align_channel` never receive one on this path).
+
+`SGD` is the other branch of main.py:158-161, built the same way: torch.optim.SGD's constructor, param_groups keys and
+state ('momentum_buffer' per parameter, only with momentum != 0), one glf_sgd_step launch per (param group, "has a
+momentum buffer" / "gets its first one").
 """
 from __future__ import annotations
 
@@ -69,7 +73,69 @@ class _Table:
         return self.dev
 
 
-class Adam(torch.optim.Optimizer):
+class _Fused(torch.optim.Optimizer):
+    """What the fused optimizers share: the checks on a parameter and its gradient, one pointer table and one launch per
+    (param group, class of parameters that take the same scalars), the version bump and the weight-image refresh.
+    A subclass says, per parameter, which class it falls into and which state tensors go into the table (`_classify`),
+    and launches its kernel over a class's table (`_launch`)."""
+    _NAME = ""
+    _SPARSE = ""
+
+    def _classify(self, group: dict, p: torch.Tensor):
+        """-> (class key, pointer for table column 2, pointer for column 3); creates / advances the parameter's state."""
+        raise NotImplementedError
+
+    def _launch(self, group: dict, key, table: torch.Tensor) -> None:
+        raise NotImplementedError
+
+    def _table_key(self, gi: int, key, n_classes: int) -> tuple:
+        return (gi, key)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for gi, group in enumerate(self.param_groups):
+            classes: Dict[object, List[tuple]] = {}
+            dev = None
+            updated = []
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if g.is_sparse:
+                    raise RuntimeError(self._SPARSE)
+                if not p.is_cuda or p.dtype != torch.float32 or g.dtype != torch.float32:
+                    raise RuntimeError(f"glfusion_amd.optim.{self._NAME}: parameters and gradients must be CUDA(HIP) float32 tensors "
+                                       "(the engine has no CPU fallback)")
+                if not p.is_contiguous():
+                    raise RuntimeError(f"glfusion_amd.optim.{self._NAME}: non-contiguous parameter")
+                if not g.is_contiguous():
+                    g = g.contiguous()
+                    p.grad = g
+                key, m_ptr, v_ptr = self._classify(group, p)
+                classes.setdefault(key, []).append((p.data_ptr(), g.data_ptr(), m_ptr, v_ptr, p.numel()))
+                dev = p.device
+                updated.append(p)
+            for key, entries in classes.items():
+                table = self._tables.setdefault(self._table_key(gi, key, len(classes)), _Table()).get(entries, dev)
+                self._launch(group, key, table)
+            if updated:
+                # the kernel writes through raw pointers: tell autograd (and every cache keyed on `_version`: the
+                # tap-major / transposed / pre-split weight layouts and the measured maxima in ops.py) that these changed
+                torch.autograd.graph.increment_version(updated)
+        # ... and rebuild every registered weight-derived image in four launches (instead of ~5 launches per conv when the
+        # next forward finds its caches stale)
+        refresh_weights()
+        return loss
+
+
+class Adam(_Fused):
+    _NAME = "Adam"
+    _SPARSE = "Adam does not support sparse gradients, please consider SparseAdam instead"
+
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  amsgrad: bool = False):
         if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0):
@@ -79,52 +145,57 @@ class Adam(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False))
         self._tables: Dict[tuple, _Table] = {}
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        for gi, group in enumerate(self.param_groups):
-            b1, b2 = group["betas"]
-            lr = group["lr"]
-            by_step: Dict[int, List[tuple]] = {}
-            dev = None
-            updated = []
-            for p in group["params"]:
-                g = p.grad
-                if g is None:
-                    continue
-                if g.is_sparse:
-                    raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead")
-                if not p.is_cuda or p.dtype != torch.float32 or g.dtype != torch.float32:
-                    raise RuntimeError("glfusion_amd.optim.Adam: parameters and gradients must be CUDA(HIP) float32 tensors "
-                                       "(the engine has no CPU fallback)")
-                if not p.is_contiguous():
-                    raise RuntimeError("glfusion_amd.optim.Adam: non-contiguous parameter")
-                if not g.is_contiguous():
-                    g = g.contiguous()
-                    p.grad = g
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                t = int(st["step"]) + 1
-                st["step"] = st["step"].new_tensor(float(t)) if isinstance(st["step"], torch.Tensor) else t
-                by_step.setdefault(t, []).append((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(),
-                                                  st["exp_avg_sq"].data_ptr(), p.numel()))
-                dev = p.device
-                updated.append(p)
-            for t, entries in by_step.items():
-                table = self._tables.setdefault((gi, len(by_step) > 1 and t), _Table()).get(entries, dev)
-                check(lib.glf_adam_step(_p(table), table.shape[0], float(lr), float(b1), float(b2), float(group["eps"]),
-                                        float(group["weight_decay"]), t, _stream()), "adam_step")
-            if updated:
-                # the kernel writes through raw pointers: tell autograd (and every cache keyed on `_version`: the
-                # tap-major / transposed / pre-split weight layouts and the measured maxima in ops.py) that these changed
-                torch.autograd.graph.increment_version(updated)
-        # ... and rebuild every registered weight-derived image in four launches (instead of ~5 launches per conv when the
-        # next forward finds its caches stale)
-        refresh_weights()
-        return loss
+    def _table_key(self, gi, t, n_classes):
+        return (gi, n_classes > 1 and t)               # t moves every step: the usual single class keeps ONE table
+
+    def _classify(self, group, p):
+        """Class = the step count t (torch keeps one per parameter; the bias corrections depend on it)."""
+        st = self.state[p]
+        if len(st) == 0:
+            st["step"] = 0
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        t = int(st["step"]) + 1
+        st["step"] = st["step"].new_tensor(float(t)) if isinstance(st["step"], torch.Tensor) else t
+        return t, st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+
+    def _launch(self, group, t, table):
+        b1, b2 = group["betas"]
+        check(lib.glf_adam_step(_p(table), table.shape[0], float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                                float(group["weight_decay"]), t, _stream()), "adam_step")
+
+
+class SGD(_Fused):
+    _NAME = "SGD"
+    _SPARSE = "glfusion_amd.optim.SGD: sparse gradients are not built"
+
+    def __init__(self, params, lr: float, momentum: float = 0, dampening: float = 0, weight_decay: float = 0,
+                 nesterov: bool = False):
+        # torch.optim.SGD's own checks (the same ValueErrors) and its own param_groups keys, whatever this torch version carries
+        # beyond the five that are built: a throw-away instance over one CPU scalar
+        twin = torch.optim.SGD([torch.zeros(1)], lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                               nesterov=nesterov)
+        super().__init__(params, dict(twin.defaults))
+        self._tables: Dict[tuple, _Table] = {}
+
+    def _classify(self, group, p):
+        """Class = "gets its first momentum buffer in this step" (the kernel writes it and never reads it) or not."""
+        if group["momentum"] == 0:
+            return False, 0, 0
+        st = self.state[p]
+        buf = st.get("momentum_buffer")
+        first = buf is None
+        if first:
+            buf = torch.empty_like(p, memory_format=torch.contiguous_format)
+        elif not buf.is_cuda or buf.dtype != torch.float32 or buf.numel() != p.numel():
+            raise RuntimeError("glfusion_amd.optim.SGD: a momentum buffer must be a CUDA(HIP) float32 tensor of its parameter's size")
+        elif not buf.is_contiguous():
+            buf = buf.contiguous()
+        st["momentum_buffer"] = buf
+        return first, buf.data_ptr(), 0
+
+    def _launch(self, group, first, table):
+        if group.get("maximize"):
+            raise NotImplementedError("glfusion_amd.optim.SGD: maximize is not used by the reference (main.py:159) and not built")
+        check(lib.glf_sgd_step(_p(table), table.shape[0], float(group["lr"]), float(group["momentum"]), float(group["dampening"]),
+                               float(group["weight_decay"]), int(bool(group["nesterov"])), int(first), _stream()), "sgd_step")

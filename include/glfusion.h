@@ -768,6 +768,19 @@ int glf_colsum(const float* dy, int lddy, float* db, int rows, int c, double* wo
  * ------------------------------------------------------------------------------------- */
 int glf_adam_step(const int64_t* table, int n_rows, double lr, double beta1, double beta2, double eps,
                   double weight_decay, int64_t step, glf_stream_t s);
+/* torch.optim.SGD (main.py:159-161; momentum, dampening and nesterov as torch defines them) over a table of the same
+ * n_rows x 5 int64 format, ONE launch: column 2 is the momentum buffer, column 3 is ignored (may be 0).  In torch's
+ * operation order, every operation individually rounded:
+ *   d = grad;  if weight_decay != 0: d += weight_decay * param
+ *   if momentum != 0: buf = first ? d : buf * momentum + (1 - dampening) * d;  d = nesterov ? d + momentum * buf : buf
+ *   param += (-lr) * d
+ * first != 0: the parameters of this call have no momentum buffer yet (the buffer is written, never read); parameters
+ * with and without one go into separate calls.  With momentum == 0 the buffer column is neither read nor written and
+ * may be 0 -- then and only then.  1 - dampening and -lr are formed in double on the host as torch does.
+ * Checked before any HIP runtime call: GLF_ERR_NULL (table), GLF_ERR_BAD_SHAPE (n_rows < 1, table not 8-byte aligned,
+ * momentum < 0, nesterov with momentum <= 0 or dampening != 0). */
+int glf_sgd_step(const int64_t* table, int n_rows, double lr, double momentum, double dampening, double weight_decay,
+                 int nesterov, int first, glf_stream_t s);
 
 /* ---------------------------------------------------------------------------------------
  * Temporal cycle-consistency loss: Trainer.seg_cycle and Trainer.dense_seg_cycle

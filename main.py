@@ -27,7 +27,16 @@ def main(rank, config):
                         help="evaluation with BatchNorm folded into the convolutions (config['train']['fold_bn']; f16x3 / f16 only)")
     parser.add_argument("--fold-bn-s16", action="store_true",
                         help="the same under 16-bit storage (config['train']['fold_bn_s16']; bf16 only)")
+    parser.add_argument("--opt", type=str, default=None, choices=("Adam", "SGD"),
+                        help="optimizer branch of main.py:158-165 (config['net']['opt']['opt_name']); default: the config's")
+    parser.add_argument("--resume", action="store_true",
+                        help="continue from the latest checkpoint in config['train']['save_dir'] (config['train']['is_load']); "
+                             "checkpoints then also hold the optimizer state (config['train']['save_optimizer'])")
     args = parser.parse_args()
+    if args.opt:
+        config["net"]["opt"]["opt_name"] = args.opt
+    if args.resume:
+        config["train"]["is_load"] = config["train"]["save_optimizer"] = True
     if args.precision:
         config["train"]["precision"] = args.precision
     if args.fold_bn:
