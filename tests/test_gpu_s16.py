@@ -372,7 +372,7 @@ def test_s16_tpavi_block_vs_oracle():
 @pytest.mark.parametrize("training", [True, False])
 def test_s16_tpavi_single_call_equals_composed_sequence(training, monkeypatch):
     """glf_s16_tpavi_fwd / _bwd (one C call per direction, include/glfusion.h) against the same block composed from the
-    individual entry points by ops16.Tpavi16Fn: the same launches, so every output, buffer update and gradient bit for bit."""
+    individual entry points by fusion16.Tpavi16Fn: the same launches, so every output, buffer update and gradient bit for bit."""
     from glfusion_amd import ops16
     from glfusion_amd.models.ours import TPAVIModule
     res = []

@@ -1,5 +1,5 @@
 """GPU: fused softmax attention under 16-bit storage (csrc/attn_s16.hip: glf_s16_attn_softmax_fwd / _bwd) and the fusion block's
-`embedded` mode under precision "bf16" (ops16.Tpavi16Fn).
+`embedded` mode under precision "bf16" (fusion16.Tpavi16Fn).
 
 Arithmetic contract checked here: S = theta phi^T on bf16 MFMA with fp32 accumulation, row max / sum / rescaling in fp32, P and dS
 rounded to bf16 only as MFMA operands, y and the gradients accumulated in fp32 and stored as bf16 once, lse fp32.  The kernel is

@@ -516,7 +516,7 @@ for _s in NT_NARROW.values():
 for _s in NT_PLAIN.values():
     assert nt_spec_variant(_s, True)["wide"] == nt_spec_variant(_s, False)["wide"] == (_s["N"] % 8 == 0)
 
-# the attention-gradient call shapes of ops16.Tpavi16Fn.backward (mode 'dot'), scaled down: n = 3 frames, L = 100, Ci = 64, C = 128
+# the attention-gradient call shapes of fusion16.Tpavi16Fn.backward (mode 'dot'), scaled down: n = 3 frames, L = 100, Ci = 64, C = 128
 _AL, _ACI, _AC, _AN = 100, 64, 128, 3
 _AC3 = 3 * _ACI
 NT_ATTN = {

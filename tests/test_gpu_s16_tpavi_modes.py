@@ -3,7 +3,7 @@
 concatenate: csrc/attn_pair_s16.hip (glf_s16_attn_pair_relu_* / _proj_*).  Contract checked here: s = (a_i + b_j) + c in fp32, the
 relu(s) tile rounded to bf16 only as an MFMA operand, y / dg accumulated in fp32, scaled by 1 / L in fp32 and stored as bf16 once;
 t = dY g^T from exact bf16 products with fp32 accumulation, so da / db / dc are held to the fp32 kernel's gate.
-gaussian: the frame-group route of ops16.Tpavi16Fn over glf_s16_softmax_rows_fwd / _bwd (fp32 scores in, bf16 operand out, zero pad
+gaussian: the frame-group route of fusion16.Tpavi16Fn over glf_s16_softmax_rows_fwd / _bwd (fp32 scores in, bf16 operand out, zero pad
 columns).  Kernels are gated against float64 on the SAME bf16 inputs with a bound derived from an emulation of exactly those roundings
 (the rule of test_gpu_s16_attn.py); the block and the model against the same module under precision "f32"."""
 import ctypes as C
@@ -324,6 +324,36 @@ def test_s16_tpavi_mode_block_vs_f32(mode):
     for k, b in bufs["f32"].items():
         assert l2(bufs["bf16"][k], b) <= 5e-2, k
     assert l2(evals["bf16"], evals["f32"]) <= 5e-2
+
+
+def test_s16_gaussian_frame_grouping_does_not_change_the_result():
+    """TPAVIModule(128, 'gaussian'), N = 3, L = 360 (rows padded to 384), train mode, under bf16: one group of three frames against
+    groups of two and one (a ragged last group).  No per-group quantity enters a frame's arithmetic: z, dx, every gradient and buffer
+    bit for bit."""
+    from glfusion_amd import fusion, fusion16
+    from glfusion_amd.models.ours import TPAVIModule
+    x = (0.5 * torch.randn(3, 3, 10, 12, 128, generator=torch.Generator().manual_seed(611))).to(DEV).to(BF)
+    res = {}
+    old_bytes = fusion.CHUNK_BYTES
+    try:
+        for frames, nbytes in ((3, old_bytes), (2, 2 * 360 * 384 * fusion16.GAUSS16_BYTES + 1024)):
+            fusion.CHUNK_BYTES = nbytes
+            assert fusion16.GAUSS16_BYTES == 12 and fusion16._gauss_frames16(3, 360, 384) == frames
+            mod = TPAVIModule(in_channels=128, mode="gaussian")
+            zero_mean_kinkfree_fill(mod, 61)
+            mod = mod.to(DEV).train()
+            z, dx, grads = _block_run(mod, x, 77)
+            out = {"z": z, "dx": dx}
+            out.update({"grad:" + k: v for k, v in grads.items()})
+            out.update({"buffer:" + k: b.detach().clone() for k, b in mod.named_buffers()})
+            res[frames] = out
+    finally:
+        fusion.CHUNK_BYTES = old_bytes
+    one, two = res[3], res[2]
+    assert set(one) == set(two)
+    print("  s16 gaussian, groups of 2 + 1 against one group of 3:", {k: f"{l2(two[k], v):.2e}" for k, v in one.items()})
+    for k, v in one.items():
+        assert torch.equal(two[k], v), k
 
 
 @pytest.mark.parametrize("mode", MODES)

@@ -78,6 +78,106 @@ def test_tpavi_modes_vs_golden(golden_dir, mode, precision):
     assert ok_z and ok_dx and ok_rs and ok_ze and not bad, (ok_z, ok_dx, ok_rs, ok_ze, bad)
 
 
+def _odd_width_float64(golden_dir, mode, state):
+    """z, dx, running mean / var and every parameter gradient of TPAVIModule(48, mode) in float64 on the +-1 input.  'embedded': the
+    oracle's module, evaluated here; 'gaussian' (which the oracle does not restate): the reference's own class, evaluated in float64
+    by tests/golden/make_golden_tpavi_modes.py."""
+    if mode == "gaussian":
+        g = np.load(os.path.join(golden_dir, "tpavi_gaussian_w48_f64.npz"))
+        return {"z": g["z"], "dx": g["dx"], "rm": g["rm"], "rv": g["rv"]}, {k: g["g:" + k] for k in g["grad_names"].tolist()}
+    ref = orc.TPAVIModule(48, mode=mode)
+    ref.load_state_dict(state, strict=True)
+    ref = ref.double().train()
+    x = orc.closed_form_tensor((2, 48, 3, 6, 5), 101, -1.0, 1.0).double().requires_grad_(True)
+    z, _ = ref(x)
+    (z * orc.closed_form_tensor(tuple(z.shape), 102, -1.0, 1.0).double()).sum().backward()
+    out = {"z": z.detach(), "dx": x.grad, "rm": ref.W_z[1].running_mean, "rv": ref.W_z[1].running_var}
+    return out, {k: p.grad for k, p in ref.named_parameters() if p.grad is not None}
+
+
+@pytest.mark.parametrize("mode", ["gaussian", "embedded"])
+def test_tpavi_materialised_odd_width_vs_float64(golden_dir, mode):
+    """TPAVIModule(48, mode) (Ci = 24: no fused kernel, no frame groups -- the scores are materialised) at L = 90 under f32, against
+    float64, at test_gpu_model.test_tpavi_vs_golden's gates: z 2e-5, dx 5e-5, running statistics 1e-6, gradient norms and elements
+    1e-4, the W_z.0.bias rule."""
+    from glfusion_amd import fusion, ops
+    from glfusion_amd.models import TPAVIModule
+    ops.set_precision("f32")
+    if mode == "embedded":
+        assert not fusion.fused_softmax_ok(24) and not fusion.chunked_softmax_ok(24, 90)
+    else:
+        assert not fusion.gaussian_chunked_ok(24)
+    m = TPAVIModule(48, mode=mode)
+    orc.closed_form_fill(m, salt=3)
+    want, want_g = _odd_width_float64(golden_dir, mode, m.state_dict())
+    m = m.to(DEV).train()
+    x = orc.closed_form_tensor((2, 48, 3, 6, 5), 101, -1.0, 1.0).to(DEV).requires_grad_(True)
+    z, _ = m(x)
+    (z * orc.closed_form_tensor(tuple(z.shape), 102, -1.0, 1.0).to(DEV)).sum().backward()
+    print(f"  {mode}: z"); ok = close(z, want["z"], 2e-5)
+    print("  dx"); ok = close(x.grad, want["dx"], 5e-5) and ok
+    print("  running mean / var"); ok = close(m.W_z[1].running_mean, want["rm"], 1e-6) and close(m.W_z[1].running_var, want["rv"], 1e-6) and ok
+    bad = []
+    for name, p in m.named_parameters():
+        if name not in want_g:
+            assert p.grad is None, name
+            continue
+        ref_g = torch.as_tensor(want_g[name]).double()
+        gn, rn = float(p.grad.double().norm()), float(ref_g.norm())
+        print(f"  grad {name}: norm {gn:.6e} (float64 {rn:.6e})")
+        if name == "W_z.0.bias":          # exactly-zero true gradient (feeds a train-mode BN): rounding noise only
+            if not gn <= 1e-4 * float(torch.as_tensor(want_g["W_z.0.weight"]).double().norm()):
+                bad.append(name)
+            continue
+        if not abs(gn - rn) <= 1e-4 * max(1.0, rn) or not close(p.grad, ref_g, 1e-4):
+            bad.append(name)
+    assert ok and not bad, (ok, bad)
+
+
+@pytest.mark.parametrize("prec", ["f32", "f16x3"])
+def test_gaussian_frame_grouping_does_not_change_the_result(prec):
+    """TPAVIModule(128, 'gaussian'), N = 3, L = 3 * 10 * 12 = 360 (rows padded to 384), train mode: one group of three frames against
+    groups of two and one (a ragged last group).  No per-group quantity enters a frame's arithmetic under f32: bit for bit.  Under
+    f16x3 the bound on |dP| that scales the split of dS is taken per group: output within 5e-5, dx, gradients and running statistics
+    within 2e-4 relative L2 (the gates of test_chunked_split_fp16_softmax_attention_matches_fused_kernel)."""
+    from glfusion_amd import fusion, ops
+    from glfusion_amd.models import TPAVIModule
+    res = {}
+    old_bytes = fusion.CHUNK_BYTES
+    ops.set_precision(prec)
+    try:
+        for frames, nbytes in ((3, old_bytes), (2, 2 * 360 * 384 * 4 + 1024)):
+            fusion.CHUNK_BYTES = nbytes
+            assert fusion.gaussian_chunked_ok(64) and fusion._frames_per_chunk(3, 360) == frames
+            mod = TPAVIModule(128, mode="gaussian")
+            _fill(mod, 61)
+            mod = mod.to(DEV).train()
+            x = (0.5 * torch.randn(3, 3, 10, 12, 128, generator=torch.Generator().manual_seed(611))).to(DEV).requires_grad_(True)
+            z = mod.forward_nvhwc(x)
+            z.backward(torch.randn(z.shape, generator=torch.Generator().manual_seed(77)).to(DEV))
+            torch.cuda.synchronize()
+            out = {"z": z.detach(), "dx": x.grad}
+            out.update({"grad:" + k: p.grad for k, p in mod.named_parameters() if p.grad is not None})
+            out.update({"buffer:" + k: b.detach().clone() for k, b in mod.named_buffers()})
+            res[frames] = out
+    finally:
+        fusion.CHUNK_BYTES = old_bytes
+        ops.set_precision("f32")
+    one, two = res[3], res[2]
+    assert set(one) == set(two)
+    errs = {k: l2(two[k].double().cpu().numpy(), v.double().cpu().numpy()) for k, v in one.items()}
+    print(f"  gaussian, groups of 2 + 1 against one group of 3 ({prec}):", {k: f"{e:.2e}" for k, e in errs.items()})
+    if prec == "f32":
+        for k, v in one.items():
+            assert torch.equal(two[k], v), (k, errs[k])
+        return
+    top = max(float(v.norm()) for k, v in one.items() if k.startswith("grad:"))
+    for k, v in one.items():
+        if k.startswith("grad:") and not float(v.norm()) > 1e-5 * top:
+            continue
+        assert errs[k] <= (5e-5 if k == "z" else 2e-4), (k, errs[k])
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # 2. parameters and buffers per mode are the reference's
 # ---------------------------------------------------------------------------------------------------------------------------
