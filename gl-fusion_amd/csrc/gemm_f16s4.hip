@@ -93,7 +93,7 @@ __global__ __launch_bounds__(NT4, 2) void gemm_rows_f16s4_kernel(const GemmArgs 
             unsigned rm;
             region_of(p_gather, r, g_dil, g_hd, g_wd, y0, y1, x0, x1, rm);
             const int mt = g_nimg * (y1 - y0) * (x1 - x0);
-            const int tiles = (mt + BM4 - 1) / BM4;
+            const int tiles = (rm & p_tap_mask) ? (mt + BM4 - 1) / BM4 : 0;      // a region none of whose taps is kept gets no tiles
             if (!found) {
                 if (tm < tiles) { found = true; mask = rm & p_tap_mask; pMe = mt; r_y0 = y0; r_x0 = x0; r_h = y1 - y0; r_w = x1 - x0; }
                 else tm -= tiles;
@@ -554,8 +554,9 @@ int launch_rows_f16s4(const GemmArgs& a0, dim3 grid, bool gather, int nprod, hip
             int y0, y1, x0, x1;
             unsigned rm;
             region_of(a.gather, r, a.g.dil, a.g.hd, a.g.wd, y0, y1, x0, x1, rm);
-            tiles_m += ((long long)a.g.n_img * (y1 - y0) * (x1 - x0) + BM4 - 1) / BM4;
+            if (rm & a.tap_mask) tiles_m += ((long long)a.g.n_img * (y1 - y0) * (x1 - x0) + BM4 - 1) / BM4;      // as the kernel's region walk
         }
+        if (tiles_m == 0) return GLF_OK;             // every region's tap set is empty under this mask: nothing to add
     } else if (a.rect) {
         tiles_m = 0;
         for (unsigned mm = a.tap_mask; mm; mm &= mm - 1) {

@@ -392,7 +392,8 @@ __global__ __launch_bounds__(256) void sum_finalize(const double* __restrict__ p
 // fp16 headroom above the bound anyway)
 __global__ __launch_bounds__(256) void bnbwd_finalize(const double* __restrict__ partial, const float* __restrict__ pmax, int slices, int c,
                                                       const float* __restrict__ gamma, const float* __restrict__ invstd, float inv_n,
-                                                      int training, float* out_a, float* out_b, float* __restrict__ bound) {
+                                                      int training, float* out_a, float* out_b, float* __restrict__ bound,
+                                                      float* __restrict__ keep) {
     __shared__ double sh[512];
     __shared__ float shm[512];
     const int cx = threadIdx.x % FIN_CH, lane = threadIdx.x / FIN_CH;
@@ -421,6 +422,7 @@ __global__ __launch_bounds__(256) void bnbwd_finalize(const double* __restrict__
     for (int l = 1; l < FIN_LANES; ++l) { mg = fmaxf(mg, shm[threadIdx.x + l * FIN_CH]); mx = fmaxf(mx, shm[256 + threadIdx.x + l * FIN_CH]); }
     if (out_a) out_a[ch] = (float)s;
     if (out_b) out_b[ch] = (float)q;
+    if (keep) { keep[ch] = (float)s; keep[c + ch] = (float)q; }       // the caller's own copy for a later apply pass (packed_dx = 2)
     const float k = fabsf(gamma[ch] * invstd[ch]);
     const float b = 1.0001f * k * (training ? mg + inv_n * (fabsf((float)s) + mx * fabsf((float)q)) : mg);
     if (b > 0.f && b < 3.0e38f) atomicMax(reinterpret_cast<unsigned*>(bound), __float_as_uint(b));
@@ -857,7 +859,17 @@ extern "C" int glf_bn_bwd(const float* dy, int lddy, const float* x, int ldx, co
     if (dy2) { REQ_AL(dy2, "dy2"); REQ_LD(lddy2, "lddy2"); }
     const OpBnBwd op{dy, lddy, x, ldx, y, ldy, mean, invstd, gamma, beta, relu, relu_mask, c / 4, dy2, lddy2};
     const long long total4f = (long long)rows * (c / 4);
-    if (fused_sums && c <= APPLY_MAX_C) {
+    // packed_dx = 2 / 3: the two halves of the packed three-launch form for SEVERAL layers whose images share one scale (column
+    // slices of one buffer): 2 = reduction + finalize only (dgamma / dbeta final, the bound raised into *amax_out by atomic max),
+    // 3 = the apply pass only, scaled by *amax_out -- the caller runs every layer's half 2 before the first half 3.  Half 3 reads
+    // the sums from `fused_sums` (here 2 c floats the CALLER owns, written by half 2), never from dgamma / dbeta: those are handed
+    // on after half 2 and may be summed over ranks or accumulated into before half 3 runs
+    const int phase = packed_dx >= 2 ? packed_dx : 0;
+    GLF_REQUIRE(packed_dx >= 0 && packed_dx <= 3, GLF_ERR_BAD_SHAPE, "bn_bwd: packed_dx must be 0 .. 3");
+    GLF_REQUIRE(!phase || (workspace && fused_sums), GLF_ERR_NULL, "bn_bwd: packed_dx = 2 / 3 needs the workspace and fused_sums (2 c floats kept from half 2 to half 3)");
+    GLF_REQUIRE(phase != 2 || (dgamma && dbeta), GLF_ERR_NULL, "bn_bwd: packed_dx = 2 needs dgamma and dbeta");
+    float* keep = phase ? reinterpret_cast<float*>(fused_sums) : (float*)nullptr;
+    if (!phase && fused_sums && c <= APPLY_MAX_C) {
         // two launches: reduction with atomics into the caller's ZERO-FILLED buffer (2 c doubles, then 2 c floats of maxima), apply
         float* fmax = reinterpret_cast<float*>(fused_sums + (size_t)2 * c);
         const int fs = fused_slices(rows, c);
@@ -881,18 +893,21 @@ extern "C" int glf_bn_bwd(const float* dy, int lddy, const float* x, int ldx, co
     float* sums = reinterpret_cast<float*>(workspace + (size_t)2 * slices * c);
     float* s_dy = dbeta ? dbeta : sums;
     float* s_dyx = dgamma ? dgamma : sums + c;
-    if (packed_dx) {
+    if (phase == 3) {
+        s_dy = keep; s_dyx = keep + c;      // the sums are where half 2 kept them, the bound in *amax_out
+    } else if (packed_dx) {
         float* pmax = reinterpret_cast<float*>(workspace + (size_t)2 * slices * c + (size_t)2 * c);
         const int c4 = c / 4, tpr = c4 < RT ? c4 : RT;
         hipLaunchKernelGGL(bnbwd_reduce_kernel, dim3(slices, (c4 + tpr - 1) / tpr), dim3(RT), 0, glf::S(s), op, rows, c, slices, workspace, pmax);
         if (int rc = glf::check_launch("bn_bwd_reduce")) return rc;
         hipLaunchKernelGGL(bnbwd_finalize, dim3((c + FIN_CH - 1) / FIN_CH), dim3(256), 0, glf::S(s), workspace, pmax, slices, c, gamma, invstd,
-                           1.0f / (float)rows, training, s_dy, s_dyx, amax_out);
+                           1.0f / (float)rows, training, s_dy, s_dyx, amax_out, keep);
     } else {
         if (int rc = launch_colreduce(op, rows, c, workspace, glf::S(s))) return rc;
         hipLaunchKernelGGL(sum_finalize, dim3((c + FIN_CH - 1) / FIN_CH), dim3(256), 0, glf::S(s), workspace, slices, c, s_dy, s_dyx);
     }
     if (int rc = glf::check_launch("bn_bwd_finalize")) return rc;
+    if (phase == 2) return GLF_OK;
     const long long total4 = (long long)rows * (c / 4);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(stream_grid(total4, 256)), dim3(256), 0, glf::S(s), dy, lddy, x, ldx, y, ldy,
                        Coef{mean, invstd, gamma, beta}, s_dy, s_dyx, dx, lddx, dres, lddres, total4, c / 4, relu, training,

@@ -376,6 +376,19 @@ __global__ __launch_bounds__(256) void bcast_rows_kernel(const TX* __restrict__ 
     }
 }
 
+// y[row][:] += scale * x[row / p][:]: the accumulating form (fp32, C % 4 == 0) -- the gradient of a per-frame average (the ASPP
+// pooled branch) added into the input gradient the conv branches already wrote, instead of a tensor of its own plus a sum pass
+__global__ __launch_bounds__(256) void bcast_rows_add_kernel(const float* __restrict__ x, float* __restrict__ y, int ld, float scale, int p, int c4, long long total) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int cc = (int)(i % c4); const long long row = i / c4;
+        const float4 a = *reinterpret_cast<const float4*>(x + ((row / p) * c4 + cc) * 4);
+        float4* dst = reinterpret_cast<float4*>(y + row * ld + cc * 4);
+        float4 v = *dst;
+        v.x = fmaf(scale, a.x, v.x); v.y = fmaf(scale, a.y, v.y); v.z = fmaf(scale, a.z, v.z); v.w = fmaf(scale, a.w, v.w);
+        *dst = v;
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // dropout (counter-based; same mask recomputed in backward from the seed)
 // ---------------------------------------------------------------------------------------
@@ -1030,6 +1043,15 @@ extern "C" int glf_bcast_rows_scaled(const float* x, float* y, int ldy, float sc
     GLF_REQUIRE(n > 0 && p > 0 && c > 0 && ldy >= c, GLF_ERR_BAD_SHAPE, "bcast_rows: bad shape");
     if (c % 4 == 0 && ldy % 4 == 0 && al16(x) && al16(y)) return launch_bcast_rows<float, float, 4>(x, y, ldy, scale, n, p, c, glf::S(s), "bcast_rows");
     return launch_bcast_rows<float, float, 1>(x, y, ldy, scale, n, p, c, glf::S(s), "bcast_rows");
+}
+extern "C" int glf_bcast_rows_add(const float* x, float* y, int ldy, float scale, int n, int p, int c, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(x && y, GLF_ERR_NULL, "bcast_rows_add: null argument");
+    GLF_REQUIRE(n > 0 && p > 0 && c > 0 && ldy >= c, GLF_ERR_BAD_SHAPE, "bcast_rows_add: bad shape");
+    GLF_REQUIRE(c % 4 == 0 && ldy % 4 == 0 && al16(x) && al16(y), GLF_ERR_UNSUPPORTED, "bcast_rows_add: c and ldy must be multiples of 4 and both tensors 16-byte aligned");
+    const long long total = (long long)n * p * (c / 4);
+    hipLaunchKernelGGL(bcast_rows_add_kernel, dim3(stream_grid(total, 256)), dim3(256), 0, glf::S(s), x, y, ldy, scale, p, c / 4, total);
+    return glf::check_launch("bcast_rows_add");
 }
 extern "C" int glf_s16_bcast_rows(const void* x, int x_dtype, void* y, int ldy, float scale, int n, int p, int c, glf_stream_t s) {
     if (int rc = glf::ensure_init()) return rc;

@@ -19,7 +19,9 @@ constexpr int ELEMS_PER_WG = 4096;      // elements of the destination one workg
 __device__ __forceinline__ void job_copy(const glf_weight_job& j, long long wg) {
     const long long n = j.d0, base = wg * ELEMS_PER_WG;
     const long long hi = base + ELEMS_PER_WG < n ? base + ELEMS_PER_WG : n;
-    if ((n & 3) == 0 && ((reinterpret_cast<uintptr_t>(j.src) | reinterpret_cast<uintptr_t>(j.dst)) & 15u) == 0) {
+    if (j.d1 > 0) {        // strided gather dst[i] = src[i * d1 + d2]: the centre tap of an OIHW k x k weight as a dense [Cout][Cin] matrix
+        for (long long i = base + threadIdx.x; i < hi; i += WB) j.dst[i] = j.src[i * j.d1 + j.d2];
+    } else if ((n & 3) == 0 && ((reinterpret_cast<uintptr_t>(j.src) | reinterpret_cast<uintptr_t>(j.dst)) & 15u) == 0) {
         for (long long i = base + 4 * threadIdx.x; i < hi; i += 4 * WB)
             *reinterpret_cast<float4*>(j.dst + i) = *reinterpret_cast<const float4*>(j.src + i);
     } else {
@@ -253,6 +255,7 @@ extern "C" int glf_weights_plan(glf_weight_job* jobs_host, int n_jobs, int* pass
         GLF_REQUIRE(j.d0 > 0 && (j.kind == GLF_WJ_COPY || j.kind == GLF_WJ_AMAX || j.kind == GLF_WJ_PACK || j.kind == GLF_WJ_ZERO || j.kind == GLF_WJ_CVT_BF16 || j.d1 > 0), GLF_ERR_BAD_SHAPE,
                     "weights_plan: job %d: bad extents", i);
         if (j.kind == GLF_WJ_AMAX || j.kind == GLF_WJ_PACK) GLF_REQUIRE(j.amax, GLF_ERR_NULL, "weights_plan: job %d needs an amax scalar", i);
+        if (j.kind == GLF_WJ_COPY) GLF_REQUIRE(j.d1 >= 0 && j.d2 >= 0 && (j.d1 > 0 || j.d2 == 0), GLF_ERR_BAD_SHAPE, "weights_plan: job %d: bad gather stride / offset", i);
         if (j.kind == GLF_WJ_PACK)
             GLF_REQUIRE((j.d0 & 3) == 0 && ((reinterpret_cast<uintptr_t>(j.src) | reinterpret_cast<uintptr_t>(j.dst)) & 15u) == 0, GLF_ERR_BAD_SHAPE,
                         "weights_plan: job %d: packed images need 16-byte aligned tensors of 4n elements", i);

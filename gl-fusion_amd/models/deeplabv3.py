@@ -4,7 +4,8 @@ ASPP specifics of this build: the five branch outputs are never concatenated -- 
 projection is evaluated as five accumulated K=256 contractions (ops.conv1x1_cat); dilated
 taps that fall into the zero padding for a whole tile are skipped inside the conv kernel
 (rate 36 on a 28x28 map reduces to its centre tap); the pooled branch is a per-frame row
-broadcast."""
+broadcast; under the split-fp16 precisions the 1x1 branch and the centre taps of the dilated
+branches run as one stacked contraction forward and in dgrad (ops.AsppCentreFn)."""
 from __future__ import annotations
 
 from typing import List
@@ -41,9 +42,9 @@ class ASPPPooling(nn.Sequential):
         super().__init__(AdaptiveAvgPool2d(1), Conv2d(in_channels, out_channels, 1, bias=False),
                          BatchNorm2d(out_channels), ReLU())
 
-    def forward_nhwc(self, x):
+    def forward_nhwc(self, x, lazy_grad: bool = False):
         h, w = x.shape[1], x.shape[2]
-        p = ops.global_avgpool(x)                               # [N,1,1,C]
+        p = ops.global_avgpool(x, lazy_grad)                    # [N,1,1,C]
         p = conv_bn_act(p, self[1], self[2], relu=True)         # BN statistics over the N frames
         return ops.broadcast_hw(p, h, w)                        # bilinear from 1x1 == broadcast (deeplabv3.py:135)
 
@@ -73,7 +74,15 @@ class ASPP(nn.Module):
 
     def trunk_nhwc(self, x):
         """Everything up to (not including) the Dropout: branches, projection, BN, ReLU."""
-        xs = ops.fan_out(x, len(self.convs))              # one-pass gradient fan-in over the five branches
+        # split-fp16 precisions: the 1x1 branch and the centre taps of the dilated branches as one contraction (ops.AsppCentreFn)
+        group = [conv[0] for conv in self.convs[:-1]]
+        centre = (not ops.fold_bn() and not ops.fold_bn_s16() and isinstance(self.convs[0], _Branch1x1)
+                  and all(isinstance(conv, ASPPConv) for conv in self.convs[1:-1]) and isinstance(self.convs[-1], ASPPPooling)
+                  and ops.aspp_centre_ok(x, group))
+        if centre:
+            xg, xpool = ops.fan_out(x, 2)                 # the pooled branch's gradient is added into the group's in place
+        else:
+            xs = ops.fan_out(x, len(self.convs))          # one-pass gradient fan-in over the five branches
         # every branch's last kernel (BatchNorm apply / broadcast) writes its 256 columns of ONE [N,h,w,1280] buffer, so
         # the 1280 -> 256 projection is a single K = 1280 contraction (and one dgrad, one wgrad) -- still no concat copy
         n, h, w = x.shape[0], x.shape[1], x.shape[2]
@@ -81,10 +90,22 @@ class ASPP(nn.Module):
         cat = torch.empty(n, h, w, sum(widths), dtype=x.dtype, device=x.device)
         slot = ops.amax_slot(x.device)
         branches, off = [], 0
-        for conv, xi, ck in zip(self.convs, xs, widths):
-            with ops.output_into(cat[..., off:off + ck], slot):
-                branches.append(conv.forward_nhwc(xi))
-            off += ck
+        if centre:
+            bns = [conv[1] for conv in self.convs[:-1]]
+            train = [bn.training or bn.running_mean is None for bn in bns]
+            us, sums = ops.aspp_centre_convs(xg, group, stats=any(train))
+            for conv, bn, u, sm, tr, ck in zip(group, bns, us, sums, train, widths):
+                pg = torch.is_grad_enabled() and ops.takes_packed_grad(conv.weight)
+                with ops.output_into(cat[..., off:off + ck], slot):
+                    branches.append(bn.forward_nhwc(u, relu=True, sums=sm if tr else None, packed_grad=pg))
+                off += ck
+            with ops.output_into(cat[..., off:off + widths[-1]], slot):
+                branches.append(self.convs[-1].forward_nhwc(xpool, lazy_grad=True))
+        else:
+            for conv, xi, ck in zip(self.convs, xs, widths):
+                with ops.output_into(cat[..., off:off + ck], slot):
+                    branches.append(conv.forward_nhwc(xi))
+                off += ck
         pbn = self.project[1]
         if ops.s16() and (pbn.training or pbn.running_mean is None):
             # 16-bit storage: the projection's BatchNorm statistics come out of its own epilogue

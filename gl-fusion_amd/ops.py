@@ -913,6 +913,36 @@ def _conv_out(h: int, k: int, stride: int, pad: int, dil: int) -> int:
     return (h + 2 * pad - dil * (k - 1) - 1) // stride + 1
 
 
+def _conv_wgrad(weight, wshape, x, x_packed, da, lda: int, pa: bool, am_dy, cfg, mask: int):
+    """The weight gradient of a convolution (Conv2dFn's cfg) from its output gradient `da` (row stride lda; pa: a packed pre-split
+    image scaled by am_dy) over the taps of `mask`: the parameter-shaped gradient (in its all-reduce bucket slot where one is
+    registered).  Taps outside `mask` receive zeros."""
+    n, h, w, cin, cout, kh, kw, ho, wo, stride, pad, dil, plain = cfg[:13]
+    taps, rows_o = kh * kw, n * ho * wo
+    ntap = bin(mask).count("1")
+    rect = (not plain and taps > 1 and stride == 1 and ntap > 1
+            and rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) < _rect_thr("wgrad"))
+    frac = rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) if rect else 1.0
+    split = wgrad_split(rows_o, frac, cout, cin, ntap, rect)
+    full = mask == (1 << taps) - 1
+    if taps == 1 and full:
+        dwt = grad_out(weight, (1, cout, cin), x.device)       # a 1x1 weight's gradient is the contraction's output
+    else:
+        dwt = (torch.empty if full else zeros)(taps, cout, cin, dtype=torch.float32, device=x.device)
+    ok = tn_presplit_ok(cout, cin, lda, cin)
+    am_x = x_packed[1] if x_packed is not None else amax_of(x)
+    xb, pb = pick(x, x_packed[0] if x_packed is not None else None, ok)        # x: the image the forward made, if any
+    gemm("tn", da, xb, dwt, M=cout, N=cin, K=rows_o, lda=lda, ldb=cin, ldc=cin, taps=taps, mask=mask,
+         tap_stride_b=cout * cin, gather=0 if plain else 1,
+         geo=None if plain else (n, h, w, ho, wo, kh, kw, stride, pad, dil), split=split, rect=rect,
+         amax_a=am_dy, amax_b=am_x, a_packed=pa, b_packed=pb)
+    if taps == 1:
+        return dwt.view(wshape)
+    dw = grad_out(weight, wshape, x.device)
+    check(lib.glf_tap_major_to_oihw(_p(dwt), _p(dw), cout, cin, taps, _stream()), "tap_major_to_oihw")
+    return dw
+
+
 class Conv2dFn(Function):
     """F.conv2d on [N,H,W,Cin] with torch-layout weights [Cout,Cin,kh,kw] (groups = 1)."""
 
@@ -1007,35 +1037,12 @@ class Conv2dFn(Function):
             return dx
 
         def wgrad():
-            dw = None
-            if ctx.needs_input_grad[1]:
-                mask = 1 if plain else tap_mask(1, ho, wo, h, w, kh, kw, stride, pad, dil)
-                ntap = bin(mask).count("1")
-                rect = (not plain and taps > 1 and stride == 1 and ntap > 1
-                        and rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) < _rect_thr("wgrad"))
-                frac = rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) if rect else 1.0
-                split = wgrad_split(rows_o, frac, cout, cin, ntap, rect)
-                full = mask == (1 << taps) - 1
-                if taps == 1 and full:
-                    dwt = grad_out(ctx.weight_ref, (1, cout, cin), x.device)       # a 1x1 weight's gradient is the contraction's output
-                else:
-                    dwt = (torch.empty if full else zeros)(taps, cout, cin, dtype=torch.float32, device=x.device)
-                ok = tn_presplit_ok(cout, cin, cout, cin)
-                am_x = ctx.x_packed[1] if ctx.x_packed is not None else amax_of(x)
-                # dy: the image dgrad made (or one worth making for this kernel alone); x: the image the forward made, if any
-                ok_dy = ok and (packed_hit(dy, am_dy) is not None or cin * ntap >= PRESPLIT_MIN_COLS)
-                da, pa = (dy, True) if dy_pk else pick(dy, act_packed(dy, am_dy, True) if ok_dy else None, ok_dy)
-                xb, pb = pick(x, ctx.x_packed[0] if ctx.x_packed is not None else None, ok)
-                gemm("tn", da, xb, dwt, M=cout, N=cin, K=rows_o, lda=cout, ldb=cin, ldc=cin, taps=taps, mask=mask,
-                     tap_stride_b=cout * cin, gather=0 if plain else 1,
-                     geo=None if plain else (n, h, w, ho, wo, kh, kw, stride, pad, dil), split=split, rect=rect,
-                     amax_a=am_dy, amax_b=am_x, a_packed=pa, b_packed=pb)
-                if taps == 1:
-                    dw = dwt.view(wshape)
-                else:
-                    dw = grad_out(ctx.weight_ref, wshape, x.device)
-                    check(lib.glf_tap_major_to_oihw(_p(dwt), _p(dw), cout, cin, taps, _stream()), "tap_major_to_oihw")
-            return dw
+            ok = tn_presplit_ok(cout, cin, cout, cin)
+            mask = 1 if plain else tap_mask(1, ho, wo, h, w, kh, kw, stride, pad, dil)
+            # dy: the image dgrad made (or one worth making for this kernel alone)
+            ok_dy = ok and (packed_hit(dy, am_dy) is not None or cin * bin(mask).count("1") >= PRESPLIT_MIN_COLS)
+            da, pa = (dy, True) if dy_pk else pick(dy, act_packed(dy, am_dy, True) if ok_dy else None, ok_dy)
+            return _conv_wgrad(ctx.weight_ref, wshape, x, ctx.x_packed, da, cout, pa, am_dy, ctx.cfg, mask)
 
         if ctx.needs_input_grad[0]:
             dx = dgrad()
@@ -1073,6 +1080,234 @@ def conv_stats_fusable(weight, stride: int, pad: int, dil: int, h: int, w: int, 
     rect = (taps > 1 and stride == 1 and bin(mask).count("1") > 1
             and rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) < _rect_thr("fwd"))
     return not rect
+
+
+# ----------------------------------------------------------------------------------------
+# ASPP conv branches: the centre taps as ONE contraction (split-fp16 precisions)
+# ----------------------------------------------------------------------------------------
+# The 1x1 branch and the centre taps of the 3x3 "same" branches (pad == dil: the centre tap is in range for every pixel) are
+# full-map products over the same input.  Stacked, they are one plain launch with N = k Cout forward and one with K = k Cout in
+# dgrad, at the shapes the big projections run at; the off-centre taps of a branch keep the launch they use today and ADD
+# into what the stacked launch stored.  The four BatchNorm backward passes write their gradients as column slices of one
+# packed image under one scale (_GradGroup), and the head's input gradient is one tensor where there were four plus a sum.
+ASPP_CENTRE = os.environ.get("GLF_ASPP_CENTRE", "1") != "0"
+CENTRE_TAP = 1 << 4                    # of a 3x3 kernel
+_centre_cache = {}
+
+
+def aspp_centre_weights(weights) -> torch.Tensor:
+    """Wc [k Cout][Cin]: the 1x1 weight and the centre taps of the 3x3 weights stacked by rows, bit-identical to slicing the
+    parameters.  Like fusion._qkv_weights: the buffer lives as long as the first weight, every row block is a registered weight
+    image of its parameter (GLF_WJ_COPY, for a 3x3 weight its strided-gather form), and Wc carries the combined version stamp of its sources for the
+    images derived from IT (maximum, transpose, packed forms)."""
+    w0 = weights[0]
+    cout, cin, k = w0.shape[0], w0.shape[1], len(weights)
+    key = id(w0)
+    hit = _centre_cache.get(key)
+    if (hit is None or hit[0]() is not w0 or hit[1].device != w0.device or tuple(hit[1].shape) != (k * cout, cin)
+            or any(r() is not t for r, t in zip(hit[1]._glf_sources, weights))):
+        Wc = torch.empty(k * cout, cin, dtype=torch.float32, device=w0.device)
+        refs = [weakref.ref(t) for t in weights]
+        Wc._glf_version_fn = lambda refs=refs: tuple((r()._version, r().data_ptr()) if r() is not None else None for r in refs)
+        Wc._glf_sources = refs
+        hit = _centre_cache[key] = (weakref.ref(w0, lambda _r, k_=key: _centre_cache.pop(k_, None)), Wc)
+    Wc = hit[1]
+    for i, t in enumerate(weights):
+        taps = t.shape[2] * t.shape[3]
+        src, dst = _contig(t.detach()), Wc[i * cout:(i + 1) * cout]
+        kind, dims = WJ_COPY, (cout * cin, 0, 0) if taps == 1 else (cout * cin, taps, taps // 2)
+        im, fresh = _wimage(t, "centre", kind, src, dims, lambda dst=dst: dst)
+        if im.dst.data_ptr() != dst.data_ptr():       # the stacked buffer was re-created: re-register
+            _registry(t.device).drop(im.key)
+            im, fresh = _wimage(t, "centre", kind, src, dims, lambda dst=dst: dst)
+        if fresh:
+            one = src if taps == 1 else tap_major(t)[taps // 2]       # the centre slab [Cout][Cin] of the tap-major image
+            check(lib.glf_copy_frames(_p(one), cout * cin, _p(im.dst), cout * cin, 1, cout * cin, _stream()), "aspp_centre_weights")
+    return Wc
+
+
+def aspp_centre_ok(x: torch.Tensor, convs) -> bool:
+    """True when AsppCentreFn takes the conv branches `convs` (modules with .weight/.bias/.stride/.padding/.dilation) of an
+    ASPP over x: a split-fp16 precision with pre-split operands and packed gradients, one 1x1 conv followed by 3x3 stride-1
+    pad == dil convs of equal Cin / Cout, no biases, Cin % 32 == 0 and Cout % 32 == 0.  Cout % 32 and not % 4: the gradient
+    image G exists in packed form only, and the off-centre dgrad launches contract over K = Cout of one column slice of it on
+    the aligned NT kernel, whose K step is 32 (nt_presplit_ok; the same bound takes_packed_grad sets for a single conv)."""
+    if not ASPP_CENTRE or _PREC[0] < 2 or _S16[0] or _is16(x) or packed_only(x) or x.dim() != 4 or len(convs) < 2:
+        return False
+    w0 = convs[0].weight
+    cout, cin = w0.shape[0], w0.shape[1]
+    if cin != x.shape[-1] or cin % 32 != 0 or cout % 32 != 0 or not takes_packed_grad(w0) or not nt_presplit_ok(len(convs) * cout, 4, 4):
+        return False
+    for i, cv in enumerate(convs):
+        k, d = (1, 1) if i == 0 else (3, int(cv.dilation[0]))
+        pad = 0 if i == 0 else d
+        if (tuple(cv.weight.shape) != (cout, cin, k, k) or cv.bias is not None or tuple(cv.stride) != (1, 1) or cv.groups != 1
+                or tuple(cv.padding) != (pad, pad) or tuple(cv.dilation) != (d, d) or not cv.weight.is_contiguous()):
+            return False
+    return True
+
+
+class _GradGroup:
+    """The packed image G [rows][k Cout] that the BatchNorm layers behind AsppCentreFn's k outputs write their input gradients
+    into, column slice by column slice, under ONE power-of-two scale: every layer's reduction raises its bound of max|dx| into
+    the shared slot (glf_bn_bwd packed_dx = 2) and keeps its apply pass (packed_dx = 3) back until the last layer's bound is in.
+    The channel sums an apply pass needs stay in `sums`, which the group owns: dgamma / dbeta are handed to autograd as soon as
+    a layer's reduction is enqueued, and a gradient all-reduce may sum them over ranks before the held-back pass runs."""
+
+    def __init__(self, k: int, cout: int):
+        self.k, self.cout = k, cout
+        self.G = self.amax = self.sums = None
+        self.pending, self.seen = [], 0
+
+    def bn_backward(self, i, dy, lddy, dy2, lddy2, x, ldx, y, ldy, mean, invstd, gamma, beta, dgamma, dbeta, rows, c, relu, training, has_mask):
+        if not (PACKED_GRADS and _PREC[0] >= 2 and c == self.cout):
+            raise RuntimeError("glfusion_amd: the stacked ASPP gradient image needs packed gradients under a split-fp16 precision")
+        dev = dy.device
+        if self.G is None:
+            self.G = torch.empty(rows, self.k * c, dtype=torch.float32, device=dev)
+            self.sums = torch.empty(self.k, 2 * c, dtype=torch.float32, device=dev)
+        if self.seen == 0:
+            self.amax = amax_slot(dev)           # a round of its own for every backward pass (retain_graph): the bound starts at zero
+        ld = self.k * c
+        keep = self.sums[i]
+        dx = self.G.view(tuple(x.shape[:-1]) + (ld,))[..., i * c:(i + 1) * c]
+        ws = _ws(rows, c, dev)
+
+        def call(phase: int, dg=None, db=None):      # (the held-back pass keeps no reference to dgamma / dbeta: autograd adopts them)
+            check(lib.glf_bn_bwd(_p(dy), lddy, _p(x), ldx, None if has_mask else _p(y), ldy, _p(mean), _p(invstd), _p(gamma), _p(beta),
+                                 _p(dx), ld, None, c, _p(dg), _p(db), rows, c, int(relu), int(training), _p(ws), _p(self.amax), phase,
+                                 _p(y) if has_mask else None, _p(dy2), lddy2, _p(keep), _stream()), "bn_bwd")
+
+        call(2, dgamma, dbeta)
+        self.pending.append(call)
+        self.seen += 1
+        if self.seen == self.k:
+            self.flush()
+        set_amax(dx, self.amax)
+        dx._glf_packed_only = True
+        dx._glf_grad_group = (self, i)
+        return dx
+
+    def flush(self) -> None:
+        for call in self.pending:
+            call(3)
+        self.pending, self.seen = [], 0
+
+
+class AsppCentreFn(Function):
+    """The conv branches of an ASPP head (a 1x1 conv and 3x3 stride-1 pad == dil convs over one input) up to their BatchNorm
+    inputs: k outputs, column slices of one [N,H,W,k Cout] buffer, plus the per-branch column statistics [k][2][Cout] (final
+    for the 1x1 branch and for every 3x3 branch whose kept taps are the centre alone)."""
+
+    @staticmethod
+    def forward(ctx, x, dils, stats: bool, *weights):
+        x = _contig(_chk(x, "conv input"))
+        n, h, w, cin = x.shape
+        k, cout = len(weights), weights[0].shape[0]
+        rows, ldu, dev = n * h * w, k * cout, x.device
+        Wc = aspp_centre_weights(weights)
+        am_x, am_wc = amax_of(x), amax_of(Wc)
+        ok = nt_presplit_ok(cin, cin, cin)
+        ok_x = ok and (ldu >= PRESPLIT_MIN_COLS or packed_hit(x, am_x) is not None)
+        xa, pa = pick(x, act_packed(x, am_x) if ok_x else None, ok_x)
+        wb, pb = pick(Wc, weight_packed(Wc, Wc, "w", am_wc) if ok else None, ok)
+        U = torch.empty(n, h, w, ldu, dtype=torch.float32, device=dev)
+        sums = stats_slot(ldu, dev) if stats else None
+        gemm("nt", xa, wb, U, M=rows, N=ldu, K=cin, lda=cin, ldb=cin, ldc=ldu, amax_a=am_x, amax_b=am_wc, colstats=sums,
+             a_packed=pa, b_packed=pb)
+        for i in range(1, k):
+            d = dils[i - 1]
+            mask = tap_mask(1, h, w, h, w, 3, 3, 1, d, d)
+            off = mask & ~CENTRE_TAP
+            if not off:
+                continue
+            # the launch this conv uses today (per-tap rectangles with atomics, or dense), minus the centre tap: it adds into
+            # its column slice of U, which needs no zero fill
+            rect = bin(mask).count("1") > 1 and rect_fraction(1, h, w, h, w, 3, 3, d, d, mask) < _rect_thr("fwd")
+            wt, am_w = tap_major(weights[i]), amax_of(weights[i])
+            ok_xi = ok and (cout * bin(off).count("1") >= PRESPLIT_MIN_COLS or packed_hit(x, am_x) is not None)
+            xi, pi = pick(x, act_packed(x, am_x) if ok_xi else None, ok_xi)
+            wi, pbi = pick(wt, weight_packed(wt, weights[i], "w", am_w) if ok else None, ok)
+            gemm("nt", xi, wi, U[..., i * cout:(i + 1) * cout], M=rows, N=cout, K=cin, lda=cin, ldb=cin, ldc=ldu, taps=9, mask=off,
+                 tap_stride_b=cout * cin, gather=1, geo=(n, h, w, h, w, 3, 3, 1, d, d), rect=rect, accumulate=not rect,
+                 amax_a=am_x, amax_b=am_w, a_packed=pi, b_packed=pbi)
+        # [2][k Cout] -> [k][2][Cout]: the layout a BatchNorm reads its own sums in (a 16 KB copy)
+        s4 = sums.view(2, k, cout).permute(1, 0, 2).contiguous() if stats else torch.empty(0, dtype=torch.float64, device=dev)
+        ctx.mark_non_differentiable(s4)
+        ctx.save_for_backward(x)
+        ctx.x_packed = (xa, am_x) if (pa and packed_hit(x, am_x) is not None) else None
+        ctx.weights, ctx.dils = weights, dils
+        ctx.group = grp = _GradGroup(k, cout)
+        outs = tuple(U[..., i * cout:(i + 1) * cout] for i in range(k))
+        for i, t in enumerate(outs):
+            t._glf_grad_group = (grp, i)
+        return outs + (s4,)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *dys):
+        x, = ctx.saved_tensors
+        weights, dils, grp = ctx.weights, ctx.dils, ctx.group
+        n, h, w, cin = x.shape
+        k, cout = len(weights), weights[0].shape[0]
+        rows, ldu, dev = n * h * w, k * cout, x.device
+        grp.flush()
+        G, am_g = grp.G, grp.amax
+        for i in range(k):
+            if G is None or getattr(dys[i], "_glf_grad_group", None) != (grp, i) or dys[i].data_ptr() != G.data_ptr() + 4 * i * cout:
+                raise RuntimeError("glfusion_amd: AsppCentreFn needs every branch's gradient from the BatchNorm that follows it")
+        Wc = aspp_centre_weights(weights)
+        am_wc = amax_of(Wc)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            WcT = weight_T(Wc, Wc)
+            wb, pb = pick(WcT, weight_packed(WcT, Wc, "wT", am_wc), True)
+            dx = torch.empty_like(x)
+            slot = amax_slot(dev)
+            gemm("nt", G, wb, dx, M=rows, N=cin, K=ldu, lda=ldu, ldb=ldu, ldc=cin, amax_a=am_g, amax_b=am_wc, amax_c=slot,
+                 a_packed=True, b_packed=pb)
+            for i in range(1, k):
+                d = dils[i - 1]
+                mask = tap_mask(2, h, w, h, w, 3, 3, 1, d, d)
+                off = mask & ~CENTRE_TAP
+                if not off:
+                    continue
+                frac = rect_fraction(2, h, w, h, w, 3, 3, d, d, mask)
+                if bin(mask).count("1") > 1 and region_mode(9, 3, 1, d, d, h, w, h, w, cout, frac):
+                    rect = 2                     # a region whose taps are all masked out gets no tiles: its pixels are not touched
+                else:
+                    rect = int(bin(mask).count("1") > 1 and frac < _rect_thr("dgrad"))
+                wT, am_w = tap_major_T(weights[i]), amax_of(weights[i])
+                wi, pbi = pick(wT, weight_packed(wT, weights[i], "wT", am_w), True)
+                gemm("nt", dys[i], wi, dx, M=rows, N=cin, K=cout, lda=ldu, ldb=cout, ldc=cin, taps=9, mask=off, tap_stride_b=cout * cin,
+                     gather=2, geo=(n, h, w, h, w, 3, 3, 1, d, d), rect=rect, accumulate=rect != 1, amax_a=am_g, amax_b=am_w,
+                     amax_c=slot if rect != 1 else None, a_packed=True, b_packed=pbi)
+                if rect == 1:
+                    slot = None                  # atomics report no maximum: dx is measured on first use
+            set_amax(dx, slot)
+            dx._glf_owned = True                 # fresh and handed to ONE consumer: a fan_out node may add into it
+        dws = []
+        for i in range(k):
+            if not ctx.needs_input_grad[3 + i]:
+                dws.append(None)
+                continue
+            kk, d = (1, 1) if i == 0 else (3, dils[i - 1])
+            cfg = (n, h, w, cin, cout, kk, kk, h, w, 1, 0 if i == 0 else d, d, i == 0)
+            mask = 1 if i == 0 else tap_mask(1, h, w, h, w, 3, 3, 1, d, d)
+            dws.append(_conv_wgrad(weights[i], tuple(weights[i].shape), x, ctx.x_packed, dys[i], ldu, True, am_g, cfg, mask))
+        return (dx, None, None) + tuple(dws)
+
+
+def aspp_centre_convs(x, convs, stats: bool):
+    """The conv outputs of the ASPP conv branches `convs` (see aspp_centre_ok) and, with stats, their column statistics:
+    ([u_0 .. u_{k-1}], [sums_i or None]) -- sums_i is None where branch i kept off-centre taps (its BatchNorm reduces its
+    own statistics, as it does today)."""
+    n, h, w = x.shape[0], x.shape[1], x.shape[2]
+    dils = tuple(int(cv.dilation[0]) for cv in convs[1:])
+    out = AsppCentreFn.apply(x, dils, bool(stats), *[cv.weight for cv in convs])
+    us, s4 = out[:-1], out[-1]
+    final = [True] + [(tap_mask(1, h, w, h, w, 3, 3, 1, d, d) & ~CENTRE_TAP) == 0 for d in dils]
+    return list(us), [s4[i] if (stats and f) else None for i, f in enumerate(final)]
 
 
 class ConvCatFn(Function):
@@ -1315,7 +1550,8 @@ class BatchNormActFn(Function):
     def forward(ctx, x, gamma, beta, residual, running_mean, running_var, nbt, training: bool,
                 momentum: float, eps: float, relu: bool, sums=None, packed_grad: bool = False, packed_out: bool = False):
         _chk(x, "bn input"); _chk(gamma, "bn weight"); _chk(beta, "bn bias")
-        x = _contig(x)
+        ctx.grad_group = getattr(x, "_glf_grad_group", None)      # AsppCentreFn: dx goes into a column slice of a shared packed image
+        x, ldx = _rows_view(x)                   # may be a column slice of the stacked centre-tap conv output
         c = x.shape[-1]
         rows = x.numel() // c
         dev = x.device
@@ -1328,7 +1564,7 @@ class BatchNormActFn(Function):
             check(lib.glf_bn_stats_from_sums(_p(sums), rows, c, eps, momentum, _p(mean), _p(invstd), _p(running_mean),
                                              _p(running_var), _p(nbt), _stream()), "bn_stats_from_sums")
         elif training:
-            check(lib.glf_bn_stats(_p(x), c, rows, c, eps, momentum, _p(mean), _p(invstd), _p(running_mean), _p(running_var),
+            check(lib.glf_bn_stats(_p(x), ldx, rows, c, eps, momentum, _p(mean), _p(invstd), _p(running_mean), _p(running_var),
                                    _p(nbt), _p(_ws(rows, c, dev)), _stream()), "bn_stats")
         else:
             if running_mean is None or running_var is None:
@@ -1350,11 +1586,11 @@ class BatchNormActFn(Function):
         need_mask = relu and residual is not None and any(ctx.needs_input_grad[:4])
         mask = torch.empty(rows * (c // 4), dtype=torch.uint8, device=dev) if need_mask else None
         if fused_stats:
-            check(lib.glf_bn_apply_from_sums(_p(x), c, _p(residual), c, _p(y), ldy, _p(sums), rows, c, eps, momentum, _p(gamma), _p(beta),
+            check(lib.glf_bn_apply_from_sums(_p(x), ldx, _p(residual), c, _p(y), ldy, _p(sums), rows, c, eps, momentum, _p(gamma), _p(beta),
                                              _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(nbt), int(relu), _p(am),
                                              _p(mask), _p(colmax) if packed else None, _stream()), "bn_apply_from_sums")
         else:
-            check(lib.glf_bn_apply(_p(x), c, _p(residual), c, _p(y), ldy, _p(mean), _p(invstd), _p(gamma), _p(beta), rows, c,
+            check(lib.glf_bn_apply(_p(x), ldx, _p(residual), c, _p(y), ldy, _p(mean), _p(invstd), _p(gamma), _p(beta), rows, c,
                                    int(relu), _p(am), _p(mask), _stream()), "bn_apply")
         set_amax(y, am)
         if packed:
@@ -1362,7 +1598,7 @@ class BatchNormActFn(Function):
         # without a residual the ReLU mask is recomputed from x in backward (sign of the same expression): y is not kept
         ctx.save_for_backward(x, mask if need_mask else (y if (relu and residual is not None) else None), mean, invstd, gamma, beta if relu else None)
         ctx.has_mask = need_mask
-        ctx.cfg = (rows, c, relu, training, residual is not None, ldy)
+        ctx.cfg = (rows, c, relu, training, residual is not None, ldy, ldx)
         ctx.packed_grad = bool(packed_grad) and _PREC[0] >= 2
         ctx.param_refs = (gamma, beta)
         _last_bn[0] = (mean, invstd, rows)
@@ -1372,7 +1608,7 @@ class BatchNormActFn(Function):
     @once_differentiable
     def backward(ctx, dy):
         x, y, mean, invstd, gamma, beta = ctx.saved_tensors
-        rows, c, relu, training, has_res, ldy = ctx.cfg
+        rows, c, relu, training, has_res, ldy, ldx = ctx.cfg
         dy2 = getattr(dy, "_glf_addend", None)    # fan_out(lazy=True): the two gradients of a block input arrive unsummed
         lddy2 = 0
         dy, lddy = _rows_view(dy)                 # may be a column slice of the concat-free projection's gradient
@@ -1381,10 +1617,13 @@ class BatchNormActFn(Function):
                 raise RuntimeError("glfusion_amd: the two addends of a lazy fan-in gradient differ in shape")
             dy2, lddy2 = _rows_view(dy2)
         dev = dy.device
-        dx = torch.empty_like(x)
-        dres = torch.empty_like(x) if (has_res and ctx.needs_input_grad[3]) else None
+        dres = torch.empty(x.shape, dtype=torch.float32, device=dev) if (has_res and ctx.needs_input_grad[3]) else None
         dgamma = grad_out(ctx.param_refs[0], (c,), dev)
         dbeta = grad_out(ctx.param_refs[1], (c,), dev)
+        if ctx.grad_group is not None:
+            return (ctx.grad_group[0].bn_backward(ctx.grad_group[1], dy, lddy, dy2, lddy2, x, ldx, y, ldy, mean, invstd, gamma, beta, dgamma, dbeta,
+                                                  rows, c, relu, training, ctx.has_mask), dgamma, dbeta) + (None,) * 11
+        dx = torch.empty(x.shape, dtype=torch.float32, device=dev)
         am = amax_slot(dev)
         # packed: the producing conv reads this gradient only through its dgrad / wgrad contractions -- write it ONCE, as the
         # packed pre-split image they want (scaled by a bound of its maximum the reduction pass provides), instead of fp32
@@ -1392,7 +1631,7 @@ class BatchNormActFn(Function):
         packed = ctx.packed_grad and _PREC[0] >= 2 and am is not None and PACKED_GRADS
         mask = y if ctx.has_mask else None
         fused = bnbwd_slot(c, dev) if c <= 4096 else None      # two launches (atomics) instead of three
-        check(lib.glf_bn_bwd(_p(dy), lddy, _p(x), c, None if ctx.has_mask else _p(y), ldy, _p(mean), _p(invstd), _p(gamma), _p(beta),
+        check(lib.glf_bn_bwd(_p(dy), lddy, _p(x), ldx, None if ctx.has_mask else _p(y), ldy, _p(mean), _p(invstd), _p(gamma), _p(beta),
                              _p(dx), c, _p(dres), c, _p(dgamma), _p(dbeta), rows, c, int(relu), int(training),
                              None if fused is not None else _p(_ws(rows, c, dev)), _p(am), int(packed), _p(mask), _p(dy2), lddy2, _p(fused), _stream()), "bn_bwd")
         set_amax(dx, am)
@@ -1723,12 +1962,15 @@ class AvgPoolFn(Function):
     fp32 up to its broadcast -- its BatchNorm normalises over the N per-frame averages, which differ by less than a few bf16 steps."""
 
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, lazy_grad: bool = False):
         x = _contig(_chk(x, "avgpool input", None))
         n, h, w, c = x.shape
         y = torch.empty(n, 1, 1, c, dtype=torch.float32, device=x.device)
         _launch("avgpool_fwd", x, x, y, n, h * w, c)
         ctx.cfg = (n, h, w, c, x.dtype)
+        # lazy_grad: the caller guarantees that the gradient goes straight to a fan_out node, which adds the broadcast into the
+        # other branch's gradient in place (glf_bcast_rows_add) -- it is handed over as a stride-0 view, never materialised
+        ctx.lazy = bool(lazy_grad) and x.dtype == torch.float32 and c % 4 == 0
         return y
 
     @staticmethod
@@ -1736,13 +1978,21 @@ class AvgPoolFn(Function):
     def backward(ctx, dy):
         n, h, w, c, xdt = ctx.cfg
         dy = _contig(dy)
+        if ctx.lazy:
+            # the 1 / (h w) factor goes into the data ([N][C], one tiny launch): a consumer that does not see the tag below
+            # materialises the stride-0 view and still gets the right gradient, at the price of the pass the tag saves
+            ds = torch.empty(n, 1, 1, c, dtype=torch.float32, device=dy.device)
+            _launch("bcast_rows_scaled", ds, dy, ds, c, 1.0 / (h * w), n, 1, c)
+            dx = ds.expand(n, h, w, c)
+            dx._glf_bcast = (ds, 1.0, n, h * w, c)
+            return dx, None
         dx = torch.empty(n, h, w, c, dtype=xdt, device=dy.device)
         _launch("bcast_rows_scaled", dx, dy, dx, c, 1.0 / (h * w), n, h * w, c)
-        return dx
+        return dx, None
 
 
-def global_avgpool(x):
-    return AvgPoolFn.apply(x)
+def global_avgpool(x, lazy_grad: bool = False):
+    return AvgPoolFn.apply(x, lazy_grad)
 
 
 class BroadcastFn(Function):
@@ -1797,6 +2047,22 @@ class FanOutFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, *dys):
+        lazy = [d for d in dys if d is not None and getattr(d, "_glf_bcast", None) is not None]
+        if lazy:
+            # a per-frame row broadcast (AvgPoolFn, lazy_grad): added in place into the one dense gradient when this node owns it
+            # (AsppCentreFn's fresh input gradient), written out as a tensor of its own otherwise
+            dense = [d for d in dys if d is not None and getattr(d, "_glf_bcast", None) is None]
+            own = len(dense) == 1 and getattr(dense[0], "_glf_owned", False) and dense[0].is_contiguous() and not _is16(dense[0])
+            mat = []
+            for d in lazy:
+                src, scale, n, p, c = d._glf_bcast
+                out = dense[0] if own else torch.empty(d.shape, dtype=torch.float32, device=src.device)
+                check((lib.glf_bcast_rows_add if own else lib.glf_bcast_rows_scaled)(_p(src), _p(out), c, scale, n, p, c, _stream()), "bcast_rows")
+                mat.append(out)
+            if own:
+                dense[0]._glf_amax = None        # the maximum the contractions reported no longer bounds it
+                return dense[0], None, None
+            dys = tuple(dense) + tuple(mat)
         live = [_contig(d) for d in dys if d is not None]
         if not live:
             return None, None, None

@@ -428,7 +428,9 @@ int glf_transpose2d_strided(const float* src, int64_t ld_src, int64_t batch_stri
  * per-tensor entry points.
  * ------------------------------------------------------------------------------------- */
 enum {
-    GLF_WJ_COPY = 0,        /* dst[i] = src[i], d0 elements                                   (pass 0) */
+    GLF_WJ_COPY = 0,        /* dst[i] = src[i], d0 elements; with d1 > 0 a strided gather dst[i] = src[i * d1 + d2] (d1 = taps, d2 = taps / 2:
+                               the centre tap of an OIHW weight as a dense [Cout][Cin] row block of the stacked centre-tap operand of an
+                               ASPP head, whose maximum, transpose and packed forms are ordinary jobs on the stacked buffer)  (pass 0) */
     GLF_WJ_AMAX = 1,        /* *amax = max(*amax, max|src|), d0 elements; dst unused           (pass 1) */
     GLF_WJ_TAP_MAJOR = 2,   /* src OIHW [d0=Cout][d1=Cin][d2=taps] -> dst [taps][Cout][Cin]     (pass 2) */
     GLF_WJ_TAP_MAJOR_T = 3, /* ... -> dst [taps][Cin][Cout]                                     (pass 2) */
@@ -651,6 +653,12 @@ int glf_bn_apply_from_sums(const float* x, int ldx, const float* residual, int l
  * of the tensor) is gone.  The image's power-of-two scale must be known before the first element is written: the reduction
  * pass also takes max|dy'| and max|xhat| per channel, and *amax_out (required, zeroed by the caller) receives the upper
  * bound of max|dx| derived from them (typically within 2x of the true maximum); pass the same scalar as amax_a.
+ * packed_dx = 2 / 3 split that form in two for layers whose packed gradients are column slices of ONE image under ONE scale
+ * (the conv branches of an ASPP head): 2 = reduction only (needs workspace, dgamma, dbeta, which are final afterwards; the
+ * bound is raised into *amax_out by an atomic maximum), 3 = the apply pass only (same amax_out).  Run every layer's half 2
+ * with the same amax_out before the first half 3.  In both halves fused_sums is required and means something else: 2 c floats
+ * (no zero fill) that the caller keeps per layer from half 2, which stores the channel sums there as well, to half 3, which
+ * reads them there and never touches dgamma / dbeta (which it takes as NULL) -- those may be reduced over ranks or accumulated into in between.
  * dy2 (may be NULL; row stride lddy2): a second addend of the incoming gradient -- the node sees dy + dy2.  The input of a
  * residual block feeds its shortcut and its first conv (models/resnet.py:59-79), so the gradient that reaches the previous
  * block's last BatchNorm is a sum of two tensors: both passes add them while reading instead of a separate add kernel
@@ -682,6 +690,9 @@ int glf_bcast_rows_fwd(const float* x, float* y, int ldy, int n, int p, int c, g
  * and, with scale = 1/p on a dense dy, nothing else; avgpool backward is bcast with scale 1/p. */
 int glf_sum_rows_fwd(const float* dy, int lddy, float* dx, float scale, int n, int p, int c, glf_stream_t s);
 int glf_bcast_rows_scaled(const float* x, float* y, int ldy, float scale, int n, int p, int c, glf_stream_t s);
+/* y[r][:] += scale * x[r / p][:] for the n p rows of y (c and ldy multiples of 4, 16-byte aligned): glf_bcast_rows_scaled adding
+ * into y instead of overwriting it. */
+int glf_bcast_rows_add(const float* x, float* y, int ldy, float scale, int n, int p, int c, glf_stream_t s);
 /* Stand-alone nn.ReLU (the fused paths apply it inside glf_bn_apply). */
 int glf_relu_fwd(const float* x, float* y, int64_t numel, glf_stream_t s);
 int glf_relu_bwd(const float* dy, const float* y, float* dx, int64_t numel, glf_stream_t s);
