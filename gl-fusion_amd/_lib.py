@@ -37,7 +37,11 @@ class GemmParams(C.Structure):
         ("precision", C.c_int32),
         ("colmax", C.c_void_p),
         ("c_dtype", C.c_int32), ("reserved0", C.c_int32),
+        ("c_oihw", C.c_int32), ("foreign_tap", C.c_int32), ("foreign_src", C.c_void_p), ("foreign_ld", C.c_int64),
     ]
+
+
+TN_OIHW_MAX_TAPS = 9          # GLF_TN_OIHW_MAX_TAPS
 
 
 class GemmEpilogue(C.Structure):

@@ -708,6 +708,122 @@ __global__ __launch_bounds__(256) void tn_reduce_lanes_kernel(const float* __res
     }
 }
 
+// slices of `tap` that ran (the others returned early): cut from the FULL reduction length, as in the kernels
+__device__ __forceinline__ int tn_valid_slices(int tap, int K, int split, int rect, const Geo& g) {
+    int pKe = K;
+    if (rect) {
+        int y0, y1, x0, x1;
+        tap_rect(1, tap, g.kw, g.pad, g.dil, g.hs, g.ws, g.hd, g.wd, y0, y1, x0, x1);
+        pKe = g.n_img * (y1 - y0) * (x1 - x0);
+    }
+    int chunk = (K + split - 1) / split;
+    chunk = ((chunk + BK - 1) / BK) * BK;
+    return chunk > 0 ? min(split, (pKe + chunk - 1) / chunk) : 0;
+}
+
+// The second stage storing the PARAMETER layout (glf_gemm_params.c_oihw): out[m][n][tap], the taps of an output element side by
+// side, so that a k x k weight's gradient needs neither the tap-major intermediate nor the pass that re-lays it out.  A workgroup
+// owns 4 * OG consecutive elements of the [M][N] plane (OG = 256 / SL float4 groups, SL slice lanes per group) for ALL taps.  It
+// sums tap after tap with the expressions of the two kernels above -- SL = 1: tn_reduce_kernel's walk, SL = 4 / 16: the lane walk
+// of tn_reduce_lanes_kernel, the stored bits are the same -- into an LDS tile laid out as the destination is, and stores the
+// tile's 4 * OG * taps floats as one contiguous run of float4 (144 B per float4 group of a 3x3 kernel; a tap per blockIdx.y would
+// write 4-byte pieces 36 B apart).  Taps outside tap_mask store 0 (the caller fills nothing), tap `ftap` is copied from fsrc
+// [M][fld] when that is given; accumulate adds to what the destination holds.  partial may be null when tap_mask is empty.
+template <int SL>
+__global__ __launch_bounds__(256) void tn_reduce_oihw_kernel(const float* __restrict__ partial, float* __restrict__ C, int M, int N, int taps, int split,
+                                                             unsigned tap_mask, int accumulate, int K, int rect, Geo g,
+                                                             const float* __restrict__ fsrc, long long fld, int ftap, float* __restrict__ amax_c) {
+    constexpr int OG = 256 / SL;
+    extern __shared__ __attribute__((aligned(16))) float tile[];          // [4 * OG][taps]
+    __shared__ double sh[SL > 1 ? 4 : 1][SL > 1 ? 256 : 1];
+    const long long mn = (long long)M * N, slice_stride = (long long)__popc(tap_mask) * mn;
+    const int n4 = N >> 2;
+    const long long total = (long long)M * n4;
+    const int ol = threadIdx.x % OG, sl = threadIdx.x / OG;
+    const long long g0 = (long long)blockIdx.x * OG;                      // first float4 group of this workgroup
+    const int ngrp = (int)min((long long)OG, total - g0);
+    const int nfl = ngrp * 4 * taps;                                      // floats of the tile: a multiple of 4, 16-byte aligned in C
+    float* __restrict__ dst = C + g0 * 4 * taps;
+    if (accumulate) {
+        for (int i = 4 * threadIdx.x; i < nfl; i += 1024) *reinterpret_cast<float4*>(tile + i) = *reinterpret_cast<const float4*>(dst + i);
+        __syncthreads();
+    }
+    const bool live = ol < ngrp;
+    const long long row = live ? (g0 + ol) / n4 : 0;
+    const int c4 = live ? (int)(g0 + ol - row * n4) * 4 : 0;
+    float* to = tile + 4 * ol * taps;                                     // element j of the group, tap t: to[j * taps + t]
+    int ord = 0;                                                          // ordinal of tap t among the kept ones (its slab)
+    for (int t = 0; t < taps; ++t) {
+        if ((tap_mask >> t) & 1u) {
+            const int nvalid = tn_valid_slices(t, K, split, rect, g);
+            const float* sp = partial + (long long)ord * mn + row * N + c4;
+            ++ord;
+            double ax = 0, ay = 0, az = 0, aw = 0;
+            if (SL == 1) {
+                if (live) {
+                    if (accumulate) { ax = to[t]; ay = to[taps + t]; az = to[2 * taps + t]; aw = to[3 * taps + t]; }
+                    int s_ = 0;
+                    for (; s_ + 4 <= nvalid; s_ += 4) {                   // four loads in flight, added in slice order
+                        const float4 v0 = *reinterpret_cast<const float4*>(sp + (long long)s_ * slice_stride);
+                        const float4 v1 = *reinterpret_cast<const float4*>(sp + (long long)(s_ + 1) * slice_stride);
+                        const float4 v2 = *reinterpret_cast<const float4*>(sp + (long long)(s_ + 2) * slice_stride);
+                        const float4 v3 = *reinterpret_cast<const float4*>(sp + (long long)(s_ + 3) * slice_stride);
+                        ax += v0.x; ay += v0.y; az += v0.z; aw += v0.w;
+                        ax += v1.x; ay += v1.y; az += v1.z; aw += v1.w;
+                        ax += v2.x; ay += v2.y; az += v2.z; aw += v2.w;
+                        ax += v3.x; ay += v3.y; az += v3.z; aw += v3.w;
+                    }
+                    for (; s_ < nvalid; ++s_) {
+                        const float4 v = *reinterpret_cast<const float4*>(sp + (long long)s_ * slice_stride);
+                        ax += v.x; ay += v.y; az += v.z; aw += v.w;
+                    }
+                    to[t] = (float)ax; to[taps + t] = (float)ay; to[2 * taps + t] = (float)az; to[3 * taps + t] = (float)aw;
+                }
+            } else {
+                if (live) {
+                    int s_ = sl;
+                    for (; s_ + SL < nvalid; s_ += 2 * SL) {
+                        const float4 v0 = *reinterpret_cast<const float4*>(sp + (long long)s_ * slice_stride);
+                        const float4 v1 = *reinterpret_cast<const float4*>(sp + (long long)(s_ + SL) * slice_stride);
+                        ax += (double)v0.x + (double)v1.x; ay += (double)v0.y + (double)v1.y;
+                        az += (double)v0.z + (double)v1.z; aw += (double)v0.w + (double)v1.w;
+                    }
+                    for (; s_ < nvalid; s_ += SL) {
+                        const float4 v = *reinterpret_cast<const float4*>(sp + (long long)s_ * slice_stride);
+                        ax += v.x; ay += v.y; az += v.z; aw += v.w;
+                    }
+                }
+                sh[0][threadIdx.x] = ax; sh[1][threadIdx.x] = ay; sh[2][threadIdx.x] = az; sh[3][threadIdx.x] = aw;
+                __syncthreads();
+                if (sl == 0 && live) {
+#pragma unroll
+                    for (int l = 1; l < SL; ++l) { ax += sh[0][l * OG + ol]; ay += sh[1][l * OG + ol]; az += sh[2][l * OG + ol]; aw += sh[3][l * OG + ol]; }
+                    if (accumulate) { ax += to[t]; ay += to[taps + t]; az += to[2 * taps + t]; aw += to[3 * taps + t]; }
+                    to[t] = (float)ax; to[taps + t] = (float)ay; to[2 * taps + t] = (float)az; to[3 * taps + t] = (float)aw;
+                }
+                __syncthreads();
+            }
+        } else if (sl == 0 && live) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (fsrc && t == ftap) v = *reinterpret_cast<const float4*>(fsrc + row * fld + c4);
+            if (accumulate) { v.x += to[t]; v.y += to[taps + t]; v.z += to[2 * taps + t]; v.w += to[3 * taps + t]; }
+            to[t] = v.x; to[taps + t] = v.y; to[2 * taps + t] = v.z; to[3 * taps + t] = v.w;
+        }
+    }
+    __syncthreads();
+    float cmax = 0.f;
+    for (int i = 4 * threadIdx.x; i < nfl; i += 1024) {
+        const float4 v = *reinterpret_cast<const float4*>(tile + i);
+        *reinterpret_cast<float4*>(dst + i) = v;
+        cmax = fmaxf(fmaxf(cmax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+    }
+    if (amax_c) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cmax = fmaxf(cmax, __shfl_xor(cmax, o, 64));
+        if ((threadIdx.x & 63) == 0 && cmax > 0.f) atomicMax(reinterpret_cast<unsigned*>(amax_c), __float_as_uint(cmax));
+    }
+}
+
 constexpr size_t SMEM_ROWS_NT = (2 * BK * LD_T + 2 * BK * LD_T) * sizeof(float) + 16;
 constexpr size_t SMEM_ROWS_NN = (2 * BK * LD_T + 2 * BK * LD_V) * sizeof(float) + 16;
 constexpr size_t SMEM_TN = (4 * BK * LD_V) * sizeof(float) + 2 * 32 * sizeof(int);
@@ -966,7 +1082,30 @@ extern "C" int glf_gemm_tn(const float* A, const float* B, float* C,
                                "gemm_tn: K (%d rows) != n_img*hd*wd", p->K);
     GemmArgs a = make_args(A, B, nullptr, C, p);
     const int ntap = __builtin_popcount(p->tap_mask);
-    if (ntap == 0) return GLF_OK;       // every tap in the padding: dW stays as the caller left it
+    const bool oihw = p->c_oihw != 0;
+    if (oihw) {
+        GLF_REQUIRE(p->batch == 1 && p->N % 4 == 0 && aligned16(C) && p->taps <= GLF_TN_OIHW_MAX_TAPS, GLF_ERR_UNSUPPORTED,
+                    "gemm_tn: c_oihw needs batch 1, N %% 4 == 0, a 16-byte aligned C and taps <= %d", GLF_TN_OIHW_MAX_TAPS);
+        GLF_REQUIRE(ntap == 0 || p->workspace != nullptr, GLF_ERR_UNSUPPORTED, "gemm_tn: c_oihw stores through the workspace (two-stage reduction)");
+        if (p->foreign_src)
+            GLF_REQUIRE(p->foreign_tap >= 0 && p->foreign_tap < p->taps && !((p->tap_mask >> p->foreign_tap) & 1u) && p->foreign_ld >= p->N &&
+                        p->foreign_ld % 4 == 0 && aligned16(p->foreign_src), GLF_ERR_BAD_SHAPE,
+                        "gemm_tn: the foreign tap must be a tap outside tap_mask, its source 16-byte aligned with a row stride %% 4 == 0 and >= N");
+    } else {
+        GLF_REQUIRE(!p->foreign_src, GLF_ERR_UNSUPPORTED, "gemm_tn: a foreign tap needs c_oihw");
+    }
+    auto store_oihw = [&](int lanes) {
+        const long long work = (long long)p->M * (p->N / 4);
+        const size_t lds = (size_t)(1024 / lanes) * p->taps * sizeof(float);
+        const dim3 gr((unsigned)((work * lanes + 255) / 256));
+#define GLF_OIHW(SL_)                                                                                                                          \
+        hipLaunchKernelGGL((tn_reduce_oihw_kernel<SL_>), gr, dim3(256), lds, glf::S(stream), a.partial, C, p->M, p->N, p->taps, a.split, p->tap_mask, \
+                           p->accumulate, p->K, a.rect, a.g, p->foreign_src, (long long)p->foreign_ld, p->foreign_tap, p->amax_c);
+        if (lanes == 16) { GLF_OIHW(16) } else if (lanes == 4) { GLF_OIHW(4) } else { GLF_OIHW(1) }
+#undef GLF_OIHW
+        return glf::check_launch("gemm_tn(reduce, oihw)");
+    };
+    if (ntap == 0) return oihw ? store_oihw(1) : GLF_OK;       // every tap in the padding: dW stays as the caller left it (c_oihw: zeros + the foreign tap)
     GLF_REQUIRE((long long)p->batch * a.split <= 65535, GLF_ERR_BAD_SHAPE, "gemm_tn: batch*split too large");
     a.vec_a = aligned16(A) && (p->lda % 4 == 0) && (p->batch_stride_a % 4 == 0);
     a.vec_b = aligned16(B) && (p->ldb % 4 == 0) && (p->batch_stride_b % 4 == 0);
@@ -977,7 +1116,7 @@ extern "C" int glf_gemm_tn(const float* A, const float* B, float* C,
     }
     dim3 grid(a.tiles_m * a.tiles_n, ntap, p->batch * a.split);
     const int prec = call_precision(p);
-    const bool two_stage = a.split > 1 && p->workspace != nullptr;
+    const bool two_stage = (a.split > 1 || oihw) && p->workspace != nullptr;
     if (two_stage) {
         GLF_REQUIRE(p->workspace_bytes >= (int64_t)glf_gemm_tn_workspace_bytes(p), GLF_ERR_WORKSPACE,
                     "gemm_tn: workspace of %lld bytes, glf_gemm_tn_workspace_bytes() asks for %zu", (long long)p->workspace_bytes,
@@ -1008,6 +1147,7 @@ extern "C" int glf_gemm_tn(const float* A, const float* B, float* C,
     if (bx > 2048) bx = 2048;
     int lanes = 1;
     while (vec && lanes < 16 && lanes * 4 <= a.split && work * lanes < 65536) lanes *= 4;
+    if (oihw) return store_oihw(lanes);          // (vec holds: N % 4 == 0 and the alignment of C were required above)
     if (lanes > 1) {
         long long bl = (work * lanes + 255) / 256;
         if (bl > 4096) bl = 4096;
@@ -1026,8 +1166,8 @@ extern "C" int glf_gemm_tn(const float* A, const float* B, float* C,
 }
 
 extern "C" size_t glf_gemm_tn_workspace_bytes(const glf_gemm_params* p) {
-    if (!p || p->split <= 1) return 0;
+    if (!p || (p->split <= 1 && !p->c_oihw)) return 0;
     const size_t ntap = (size_t)__builtin_popcount(p->tap_mask);
-    return (size_t)p->batch * (size_t)p->split * ntap * (size_t)p->M * (size_t)p->N * sizeof(float);
+    return (size_t)p->batch * (size_t)(p->split < 1 ? 1 : p->split) * ntap * (size_t)p->M * (size_t)p->N * sizeof(float);
 }
 

@@ -1071,6 +1071,7 @@ extern "C" int glf_s16_gemm_tn(const void* A, const void* B, void* C, const glf_
     if (int rc = validate16(p, A, B, C, "s16_gemm_tn")) return rc;
     GLF_REQUIRE(p->gather != 2, GLF_ERR_UNSUPPORTED, "s16_gemm_tn: transposed gather is not defined for the reduction form");
     GLF_REQUIRE(!p->colstats && !p->accumulate, GLF_ERR_UNSUPPORTED, "s16_gemm_tn: colstats / accumulate are not built");
+    GLF_REQUIRE(!p->c_oihw && !p->foreign_src, GLF_ERR_UNSUPPORTED, "s16_gemm_tn: the parameter-layout store (c_oihw) exists in glf_gemm_tn only");
     GLF_REQUIRE(p->rect == 0 || (p->rect == 1 && p->gather == 1 && p->split > 1 && p->batch == 1), GLF_ERR_UNSUPPORTED,
                 "s16_gemm_tn: rect = 1 (per-tap rectangles) needs a forward gather, batch 1 and split > 1 (only the slabs of slices that run are kept)");
     GLF_REQUIRE(p->M % 8 == 0 && p->N % 8 == 0, GLF_ERR_UNSUPPORTED, "s16_gemm_tn: M and N must be multiples of 8 (got %d, %d)", p->M, p->N);

@@ -19,7 +19,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ._lib import GemmEpilogue, GemmParams, WeightJob, WJ_AMAX, WJ_COPY, WJ_PACK, WJ_PASSES, WJ_PASS_OF, WJ_TAP_MAJOR, WJ_TAP_MAJOR_T, WJ_TRANSPOSE, WJ_ZERO, check, lib
+from ._lib import GemmEpilogue, GemmParams, TN_OIHW_MAX_TAPS, WeightJob, WJ_AMAX, WJ_COPY, WJ_PACK, WJ_PASSES, WJ_PASS_OF, WJ_TAP_MAJOR, WJ_TAP_MAJOR_T, WJ_TRANSPOSE, WJ_ZERO, check, lib
 
 
 # ----------------------------------------------------------------------------------------
@@ -185,14 +185,17 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
          split: int = 1, rect: bool = False, amax_a: Optional[torch.Tensor] = None,
          amax_b: Optional[torch.Tensor] = None, amax_c: Optional[torch.Tensor] = None,
          colstats: Optional[torch.Tensor] = None, a_packed: bool = False, b_packed: bool = False,
-         colmax: Optional[torch.Tensor] = None, epilogue=None) -> None:
+         colmax: Optional[torch.Tensor] = None, epilogue=None, oihw: bool = False, foreign=None) -> None:
     """mode in {'nt','nn','tn'}; geo = (n_img, hs, ws, hd, wd, kh, kw, stride, pad, dil).
     epilogue ('nt' only): (residual or None, its row stride, relu) -- the call goes to glf_gemm_nt_epilogue, which stores
     act(alpha * acc + bias[n] + residual[m][n]) once (bias is then required: the folded BatchNorm shift).
     amax_a / amax_b: device scalars bounding max|A| / max|B| (f16x3 precision only; None = measured by the library);
     amax_c: a slot from amax_slot() that receives max|C written| (ignored by rect / split > 1 / non-f16x3 calls -- pass
     it only to calls that store C directly).
-    a_packed / b_packed: A / B is the packed pre-split image packed_of() made with the same amax_a / amax_b."""
+    a_packed / b_packed: A / B is the packed pre-split image packed_of() made with the same amax_a / amax_b.
+    oihw ('tn' only, see tn_oihw_ok): Cm is the parameter-shaped [M][N][taps] gradient -- the second stage of the reduction
+    stores every tap of an element side by side, zeros for the taps outside `mask` (which may then be empty: nothing is
+    contracted); foreign = (tap, src, row stride): that tap's [M][N] values are copied from src."""
     p = GemmParams()
     p.M, p.N, p.K, p.lda, p.ldb, p.ldc = M, N, K, lda, ldb, ldc
     p.taps, p.tap_mask, p.tap_stride_b, p.gather = taps, mask, tap_stride_b, gather
@@ -207,14 +210,20 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
     p.colmax = _p(colmax)                      # zero-filled float32 [N]: column maxima of |C| (with colstats)
     p.precision = _PREC[0] + 1
     p.a_presplit, p.b_presplit = int(a_packed), int(b_packed)
+    if oihw:
+        if mode != "tn":
+            raise ValueError("gemm: the parameter-layout store exists for mode 'tn' only")
+        p.c_oihw = 1
+        if foreign is not None:
+            p.foreign_tap, p.foreign_src, p.foreign_ld = int(foreign[0]), _p(foreign[1]), int(foreign[2])
     ws = None
-    if mode == "tn" and split > 1:
+    if mode == "tn" and (split > 1 or oihw) and mask:
         # two-stage reduction: the slices store partial sums, a second kernel adds them in a fixed order -- no atomics, no
         # zero-filled C, bitwise reproducible gradients
         nbytes = int(lib.glf_gemm_tn_workspace_bytes(C.byref(p)))
         ws = torch.empty(nbytes // 4, dtype=torch.float32, device=Cm.device)
         p.workspace, p.workspace_bytes = _p(ws), nbytes
-    prof = PROFILER
+    prof = PROFILER if mask else None          # (an empty mask contracts nothing: the store-only form of the TN second stage)
     if prof is not None:
         ev0 = torch.cuda.Event(enable_timing=True)
         ev0.record()
@@ -913,32 +922,50 @@ def _conv_out(h: int, k: int, stride: int, pad: int, dil: int) -> int:
     return (h + 2 * pad - dil * (k - 1) - 1) // stride + 1
 
 
-def _conv_wgrad(weight, wshape, x, x_packed, da, lda: int, pa: bool, am_dy, cfg, mask: int):
+def tn_oihw_ok(cin: int, taps: int, dw: torch.Tensor) -> bool:
+    """True when glf_gemm_tn's second stage can store the parameter-shaped gradient `dw` itself (glf_gemm_params.c_oihw): a
+    multi-tap kernel of at most TN_OIHW_MAX_TAPS taps, Cin % 4 == 0 and a 16-byte aligned destination (a bucket slot may start
+    at any float)."""
+    return 1 < taps <= TN_OIHW_MAX_TAPS and cin % 4 == 0 and dw.data_ptr() % 16 == 0 and dw.is_contiguous()
+
+
+def _conv_wgrad(weight, wshape, x, x_packed, da, lda: int, pa: bool, am_dy, cfg, mask: int, foreign=None, out=None):
     """The weight gradient of a convolution (Conv2dFn's cfg) from its output gradient `da` (row stride lda; pa: a packed pre-split
     image scaled by am_dy) over the taps of `mask`: the parameter-shaped gradient (in its all-reduce bucket slot where one is
-    registered).  Taps outside `mask` receive zeros."""
+    registered).  Taps outside `mask` receive zeros, except foreign = (tap, src [Cout][Cin], row stride): that tap, not in
+    `mask`, is copied from src.  A multi-tap gradient is stored in parameter layout by the reduction itself (tn_oihw_ok): no
+    tap-major intermediate, no zero fill, no re-layout pass; an empty `mask` then launches that store alone.
+    out: the destination the caller already took with grad_out()."""
     n, h, w, cin, cout, kh, kw, ho, wo, stride, pad, dil, plain = cfg[:13]
     taps, rows_o = kh * kw, n * ho * wo
     ntap = bin(mask).count("1")
     rect = (not plain and taps > 1 and stride == 1 and ntap > 1
             and rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) < _rect_thr("wgrad"))
     frac = rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) if rect else 1.0
-    split = wgrad_split(rows_o, frac, cout, cin, ntap, rect)
+    split = wgrad_split(rows_o, frac, cout, cin, ntap, rect) if ntap else 1
     full = mask == (1 << taps) - 1
-    if taps == 1 and full:
-        dwt = grad_out(weight, (1, cout, cin), x.device)       # a 1x1 weight's gradient is the contraction's output
+    dw = (out if out is not None else grad_out(weight, wshape, x.device)) if taps > 1 else None
+    fused = taps > 1 and tn_oihw_ok(cin, taps, dw)
+    if fused:
+        dwt = dw
+    elif taps == 1 and full:                                   # a 1x1 weight's gradient is the contraction's output
+        dwt = out.view(1, cout, cin) if out is not None else grad_out(weight, (1, cout, cin), x.device)
     else:
         dwt = (torch.empty if full else zeros)(taps, cout, cin, dtype=torch.float32, device=x.device)
     ok = tn_presplit_ok(cout, cin, lda, cin)
     am_x = x_packed[1] if x_packed is not None else amax_of(x)
     xb, pb = pick(x, x_packed[0] if x_packed is not None else None, ok)        # x: the image the forward made, if any
-    gemm("tn", da, xb, dwt, M=cout, N=cin, K=rows_o, lda=lda, ldb=cin, ldc=cin, taps=taps, mask=mask,
-         tap_stride_b=cout * cin, gather=0 if plain else 1,
-         geo=None if plain else (n, h, w, ho, wo, kh, kw, stride, pad, dil), split=split, rect=rect,
-         amax_a=am_dy, amax_b=am_x, a_packed=pa, b_packed=pb)
+    if ntap or fused:
+        gemm("tn", da, xb, dwt, M=cout, N=cin, K=rows_o, lda=lda, ldb=cin, ldc=cin, taps=taps, mask=mask,
+             tap_stride_b=cout * cin, gather=0 if plain else 1,
+             geo=None if plain else (n, h, w, ho, wo, kh, kw, stride, pad, dil), split=split, rect=rect,
+             amax_a=am_dy, amax_b=am_x, a_packed=pa, b_packed=pb, oihw=fused, foreign=foreign if fused else None)
+    if fused:
+        return dw
     if taps == 1:
         return dwt.view(wshape)
-    dw = grad_out(weight, wshape, x.device)
+    if foreign is not None:                # (a destination the fused store cannot take: the tap joins the tap-major image)
+        check(lib.glf_copy_frames(_p(foreign[1]), foreign[2], _p(dwt[foreign[0]]), cin, cout, cin, _stream()), "conv_wgrad(foreign tap)")
     check(lib.glf_tap_major_to_oihw(_p(dwt), _p(dw), cout, cin, taps, _stream()), "tap_major_to_oihw")
     return dw
 
@@ -1091,6 +1118,8 @@ def conv_stats_fusable(weight, stride: int, pad: int, dil: int, h: int, w: int, 
 # into what the stacked launch stored.  The four BatchNorm backward passes write their gradients as column slices of one
 # packed image under one scale (_GradGroup), and the head's input gradient is one tensor where there were four plus a sum.
 ASPP_CENTRE = os.environ.get("GLF_ASPP_CENTRE", "1") != "0"
+# the centre taps' WEIGHT gradients as one stacked contraction too (0: one contraction per branch, centre tap included)
+ASPP_CENTRE_WGRAD = os.environ.get("GLF_ASPP_CENTRE_WGRAD", "1") != "0"
 CENTRE_TAP = 1 << 4                    # of a 3x3 kernel
 _centre_cache = {}
 
@@ -1287,6 +1316,15 @@ class AsppCentreFn(Function):
             set_amax(dx, slot)
             dx._glf_owned = True                 # fresh and handed to ONE consumer: a fan_out node may add into it
         dws = []
+        # every centre weight wanted: their gradients are ONE plain reduction dWc [k Cout][Cin] = G^T x over the full map (the 1x1
+        # weight's is row block 0; row block i is the centre tap of branch i, which the store of that branch's gradient picks up)
+        stacked = ASPP_CENTRE_WGRAD and all(ctx.needs_input_grad[3:3 + k])
+        if stacked:
+            dWc = torch.empty(ldu, cin, dtype=torch.float32, device=dev)
+            am_x = ctx.x_packed[1] if ctx.x_packed is not None else amax_of(x)
+            xb, pb = pick(x, ctx.x_packed[0] if ctx.x_packed is not None else None, tn_presplit_ok(ldu, cin, ldu, cin))
+            gemm("tn", G, xb, dWc, M=ldu, N=cin, K=rows, lda=ldu, ldb=cin, ldc=cin, split=wgrad_split(rows, 1.0, ldu, cin, 1, False),
+                 amax_a=am_g, amax_b=am_x, a_packed=True, b_packed=pb)
         for i in range(k):
             if not ctx.needs_input_grad[3 + i]:
                 dws.append(None)
@@ -1294,7 +1332,20 @@ class AsppCentreFn(Function):
             kk, d = (1, 1) if i == 0 else (3, dils[i - 1])
             cfg = (n, h, w, cin, cout, kk, kk, h, w, 1, 0 if i == 0 else d, d, i == 0)
             mask = 1 if i == 0 else tap_mask(1, h, w, h, w, 3, 3, 1, d, d)
-            dws.append(_conv_wgrad(weights[i], tuple(weights[i].shape), x, ctx.x_packed, dys[i], ldu, True, am_g, cfg, mask))
+            if stacked and i == 0:
+                # a copy of 4 Cout Cin bytes (2 MB at 2048 -> 256) into the parameter's slot; the alternative, a reduce that sends
+                # one row block elsewhere, would put a second destination into every TN second stage for this one caller
+                dw = grad_out(weights[0], tuple(weights[0].shape), dev)
+                if dw.data_ptr() % 16 == 0:
+                    check(lib.glf_copy_frames(_p(dWc), cout * cin, _p(dw), cout * cin, 1, cout * cin, _stream()), "aspp_centre(dw 1x1)")
+                else:                      # (a bucket slot that starts off a 16-byte boundary: the branch's own reduction stores there)
+                    _conv_wgrad(weights[0], tuple(weights[0].shape), x, ctx.x_packed, dys[0], ldu, True, am_g, cfg, mask, out=dw)
+                dws.append(dw)
+            elif stacked:
+                dws.append(_conv_wgrad(weights[i], tuple(weights[i].shape), x, ctx.x_packed, dys[i], ldu, True, am_g, cfg, mask & ~CENTRE_TAP,
+                                       foreign=(4, dWc[i * cout:(i + 1) * cout], cin)))
+            else:
+                dws.append(_conv_wgrad(weights[i], tuple(weights[i].shape), x, ctx.x_packed, dys[i], ldu, True, am_g, cfg, mask))
         return (dx, None, None) + tuple(dws)
 
 

@@ -148,7 +148,19 @@ typedef struct {
                                 /* packed_y: the activation written once, as the packed image its consumer reads)           */
     int32_t c_dtype;            /* glf_s16_gemm_nt / _tn only: element type of C (GLF_DT_F32 or GLF_DT_BF16); the fp32-storage    */
     int32_t reserved0;          /* entry points ignore it (C is fp32).  reserved0: padding, leave 0.                              */
+    int32_t c_oihw;             /* glf_gemm_tn only: 1 = C is the PARAMETER-SHAPED gradient [M][N][taps] (torch's OIHW), dense:   */
+                                /* ldc / tap_stride_b are not used.  The slices always go through the workspace (required, also   */
+                                /* with split == 1: glf_gemm_tn_workspace_bytes sizes it) and the second stage stores every tap   */
+                                /* of an output element side by side: kept taps = the sum of their slices (the bits the tap-major */
+                                /* store + glf_tap_major_to_oihw give), taps outside tap_mask = 0 -- no zero fill by the caller.  */
+                                /* An EMPTY tap_mask is allowed here: no contraction runs, only the store (zeros and the foreign  */
+                                /* tap).  accumulate adds to what C holds.  Needs batch == 1, N % 4 == 0, a 16-byte aligned C and */
+                                /* taps <= GLF_TN_OIHW_MAX_TAPS; anything else is GLF_ERR_UNSUPPORTED.                            */
+    int32_t foreign_tap;        /* with c_oihw and foreign_src: the tap (not in tap_mask) whose [M][N] values are copied from     */
+    const float* foreign_src;   /* foreign_src (row stride foreign_ld floats, % 4 == 0, 16-byte aligned) -- a result another      */
+    int64_t foreign_ld;         /* contraction produced (the ASPP centre taps, stacked).  NULL: no such tap.                      */
 } glf_gemm_params;
+#define GLF_TN_OIHW_MAX_TAPS 9
 
 /* *out = max |x| over the [rows, cols] view with row stride ld (elements); out is a device float. */
 int glf_amax(const float* x, int64_t rows, int cols, int64_t ld, float* out, glf_stream_t stream);
