@@ -38,10 +38,12 @@ class GemmParams(C.Structure):
         ("colmax", C.c_void_p),
         ("c_dtype", C.c_int32), ("reserved0", C.c_int32),
         ("c_oihw", C.c_int32), ("foreign_tap", C.c_int32), ("foreign_src", C.c_void_p), ("foreign_ld", C.c_int64),
+        ("nseg", C.c_int32), ("seg_kx", C.c_int32), ("seg", C.c_void_p),
     ]
 
 
 TN_OIHW_MAX_TAPS = 9          # GLF_TN_OIHW_MAX_TAPS
+SEG_MAX, SEG_MAX_REGIONS, SEG_ROW_TILE = 28, 49, 256          # GLF_SEG_MAX, GLF_SEG_MAX_REGIONS, GLF_SEG_ROW_TILE
 
 
 class GemmEpilogue(C.Structure):

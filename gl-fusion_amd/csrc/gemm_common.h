@@ -31,7 +31,19 @@ struct GemmArgs {
     int epi;                                    // 1 = launch the epilogue instantiation
     const float* res; long long ld_res;         // residual rows indexed like C's (null = none), its row stride in floats
     int relu;                                   // act: 0 = identity, 1 = max(., 0)
+    // segmented region mode (glf_gemm_params.nseg > 0; 8-wave split-fp16 rows kernel, SEG instantiations only)
+    const int* seg_tab;                         // device plan table (SegTab layout below); null = not a segmented launch
+    int seg_kx;                                 // K extent of one extra segment
 };
+
+// Device image of a segmented-region plan, in ints: [0, 64) first row tile of region r (INT_MAX beyond the last region);
+// then SEG_REGION_INTS per region: y0, x0, height, width, segment mask, rows (= n_img * height * width); then, 8-byte aligned,
+// one long long per segment: its element offset into A, (oy * wd + ox) * lda + acol.
+constexpr int SEG_MAX = 28, SEG_MAX_BANDS = 7, SEG_MAX_REGIONS = SEG_MAX_BANDS * SEG_MAX_BANDS;
+constexpr int SEG_REGION_INTS = 8;
+constexpr int SEG_TAB_REGIONS = 64, SEG_TAB_OFFS = SEG_TAB_REGIONS + SEG_REGION_INTS * SEG_MAX_REGIONS;
+constexpr int SEG_TAB_INTS = SEG_TAB_OFFS + 2 * SEG_MAX;
+static_assert(SEG_TAB_OFFS % 2 == 0, "segment offsets are 8-byte aligned");
 constexpr int ZERO_PAGE_FLOATS = 1 << 18;
 
 
@@ -53,6 +65,7 @@ float* amax_scratch(int n, hipStream_t s);     // n consecutive device floats fr
 const float* zero_page();                      // ZERO_PAGE_FLOATS zeros on the device (glf_api.hip)
 bool f16s_rows_ok(const GemmArgs& a);
 bool f16s_tn_ok(const GemmArgs& a);
+int launch_rows_f16s_seg(const GemmArgs& a, const glf_gemm_params* p, int nprod, hipStream_t s);   // gemm_f16s.hip: segmented region mode
 }  // namespace glf
 
 namespace {
@@ -193,6 +206,7 @@ GemmArgs make_args(const float* A, const float* B, const float* bias, float* C, 
     a.vec_a = 0; a.vec_b = 0; a.rect = 0;
     a.amax_a = p->amax_a; a.amax_b = p->amax_b; a.zeros = nullptr; a.amax_c = p->amax_c; a.colstats = p->colstats; a.colmax = p->colstats ? p->colmax : nullptr; a.partial = nullptr; a.flags = 0; a.stamps = nullptr; a.a_presplit = p->a_presplit; a.b_presplit = p->b_presplit;
     a.epi = 0; a.res = nullptr; a.ld_res = 0; a.relu = 0;
+    a.seg_tab = nullptr; a.seg_kx = 0;
     return a;
 }
 

@@ -21,8 +21,12 @@
 #include "gemm_common.h"
 #include "split_f16.h"
 #include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <vector>
 
 namespace {
+using glf::SEG_TAB_REGIONS; using glf::SEG_REGION_INTS; using glf::SEG_TAB_OFFS;
 
 #define GLF_MFMA_F16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
 // one A tile-row against both B tile-cols for one 16-deep k-step: main products into c, mixed products into m
@@ -68,7 +72,14 @@ constexpr size_t SMEM_ROWS_H8 = 3 * BUF8 + 16;
 // (after the region mapping) with its own row stride, act = identity or ReLU; amax_c then is the maximum of the value stored.
 // Only for launches that store every output element exactly once (no rect = 1, accumulate, colstats: refused by the entry point).
 // EPI = false compiles to the code it was before the parameter existed.
-template <bool GATHER, int NP, bool BP, bool PA = false, bool EPI = false>
+// SEG: segmented region mode (glf_gemm_params.nseg; instantiated for GATHER = false, PA = BP = true, EPI = false only).  A plain NT
+// contraction over K whose rows are the pixels of an n_img x hd x wd map, extended by extra segments: segment s adds
+// sum_j A[pixel + (oy_s, ox_s)][acol_s + j] * B[n][K + s * kx + j] where the shifted pixel is inside the map.  The map is cut into
+// rectangles inside each of which the set of in-range segments is constant (glf_gemm_nt_seg_plan; the plan reaches the kernel as a
+// small device table, args.seg_tab); a row tile enumerates (frame, pixel of its rectangle) as region mode does, walks the K columns
+// and then its rectangle's segments by ascending s -- a segment change is a new A row offset and a new B column offset, nothing
+// else -- and stores through the region-mode epilogue: every output element once.  SEG = false compiles to the code it was before.
+template <bool GATHER, int NP, bool BP, bool PA = false, bool EPI = false, bool SEG = false>
 __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs args) {
     const int pM = args.M, pN = args.N, pK = args.K, p_lda = args.lda, p_ldb = args.ldb, p_ldc = args.ldc;
     const int p_taps = args.taps, p_gather = args.gather, p_accumulate = args.accumulate;
@@ -80,7 +91,9 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
     const float* __restrict__ p_zero = args.zeros;
     const int g_hs = args.g.hs, g_ws = args.g.ws, g_hd = args.g.hd, g_wd = args.g.wd, g_kw = args.g.kw;
     const int g_stride = args.g.stride, g_pad = args.g.pad, g_dil = args.g.dil;
-    const int g_nimg = args.g.n_img, p_rect = GATHER ? args.rect : 0;
+    const int g_nimg = args.g.n_img, p_rect = SEG ? 2 : (GATHER ? args.rect : 0);
+    const int* __restrict__ p_seg = args.seg_tab;
+    const int p_kx = args.seg_kx;
     float sc_a, sc_b, inv_a, inv_b;
     pow2_scale(args.amax_a, sc_a, inv_a);
     pow2_scale(args.amax_b, sc_b, inv_b);
@@ -118,6 +131,15 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
     int pMe = pM;
     int r_y0 = 0, r_x0 = 0, r_h = g_hd, r_w = g_wd;
     unsigned mask = p_tap_mask;
+    unsigned seg_mask = 0;
+    if constexpr (SEG) {
+        // the plan's regions: lane r holds the first row tile of region r (INT_MAX beyond the last), one ballot finds this tile's
+        const int start = p_seg[lane];
+        const int r = __builtin_amdgcn_readfirstlane(__popcll(__ballot(tm >= start)) - 1);
+        const int* __restrict__ reg = p_seg + SEG_TAB_REGIONS + SEG_REGION_INTS * r;
+        tm -= p_seg[r];
+        r_y0 = reg[0]; r_x0 = reg[1]; r_h = reg[2]; r_w = reg[3]; seg_mask = (unsigned)reg[4]; pMe = reg[5];
+    } else
     if (p_rect == 2) {                              // region mode: tiles laid out region after region (see region_of)
         bool found = false;
 #pragma unroll
@@ -156,7 +178,7 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
     {
         // pixel coordinates of the thread's first row by division, of the other three (64 rows further each) by carrying
         int cn = 0, cy = 0, cx = 0;
-        if (GATHER) {
+        if (GATHER || SEG) {
             const int m0 = tm * BM8 + ar, hw = r_h * r_w;
             cn = m0 / hw;
             const int rem = m0 - cn * hw;
@@ -165,6 +187,15 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int m = tm * BM8 + ar + 64 * j;
+            if constexpr (SEG) {                    // the row's own pixel; a segment adds one uniform offset (advance)
+                a_n[j] = 0; a_y[j] = 0; a_x[j] = 0;
+                a_off[j] = (m < pMe) ? (long long)((cn * g_hd + r_y0 + cy) * g_wd + r_x0 + cx) * p_lda : -1;
+                if (j < 3 && m + 64 < pMe) {
+                    cx += 64;
+                    while (cx >= r_w) { cx -= r_w; ++cy; }
+                    while (cy >= r_h) { cy -= r_h; ++cn; }
+                }
+            } else
             if (GATHER) {
                 if (m < pMe) { a_n[j] = cn; a_y[j] = r_y0 + cy; a_x[j] = r_x0 + cx; }
                 else { a_n[j] = -1; a_y[j] = 0; a_x[j] = 0; }
@@ -232,16 +263,54 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
     }
 
     const int nkc = pK / BK;
-    const int ntiles = __popc(mask) * nkc;
+    const int ntiles = SEG ? nkc + __popc(seg_mask) * (p_kx / BK) : __popc(mask) * nkc;
     f32x16 c00 = {0}, c01 = {0}, c10 = {0}, c11 = {0};      // main products
     f32x16 m00 = {0}, m01 = {0}, m10 = {0}, m11 = {0};      // mixed products (x 2^11)
     float4 ra[4], rb[2];
-    unsigned rem_mask = mask;
+    unsigned rem_mask = SEG ? seg_mask : mask;
     int tap = -1, kc = nkc;
+    int nk_cur = nkc;                   // SEG: K-iterations of the slice being walked (the K columns, then one segment at a time),
+    long long ao_cur = 0;               // and that slice's element offsets into A's rows and B's rows
+    int bo_cur = 0;
     const float* pa[4];
     const float* pb[2];
 
     auto advance = [&]() __attribute__((always_inline)) {
+        if constexpr (SEG) {
+            if (++kc >= nk_cur) {
+                kc = 0;
+                if (tap == -1) {
+                    tap = 0;                        // the K columns of the plain contraction come first
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) pa[j] = (a_off[j] >= 0 ? A + a_off[j] : p_zero) + 4 * ac;      // overhang rows read the zero page
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const int n = tn * BN + ar + 64 * j;
+                        pb[j] = (n < pN ? B + (long long)n * p_ldb : p_zero) + 4 * ac;
+                    }
+                } else {
+                    // next segment of the region: ONE uniform step takes every row pointer from the end of the slice it walked to the
+                    // start of the segment's (a new pixel offset and column block of A, a new column block of B); the rows that read
+                    // the zero page just walk on through it (the launcher bounds the whole chain by the page)
+                    const int sg = __builtin_amdgcn_readfirstlane(__ffs(rem_mask) - 1);
+                    rem_mask &= rem_mask - 1;
+                    const long long ao = reinterpret_cast<const long long*>(p_seg + SEG_TAB_OFFS)[sg];
+                    const int bo = pK + sg * p_kx;
+                    const long long back = (long long)(nk_cur - 1) * BK;
+                    const long long da = ao - ao_cur - back, db = (long long)(bo - bo_cur) - back;
+                    ao_cur = ao; bo_cur = bo; nk_cur = p_kx / BK;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) pa[j] += (tm * BM8 + ar + 64 * j < pMe) ? da : (long long)BK;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) pb[j] += (tn * BN + ar + 64 * j < pN) ? db : (long long)BK;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) pa[j] += BK;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) pb[j] += BK;
+            }
+        } else
         if (++kc >= nkc) {
             kc = 0;
             tap = __ffs(rem_mask) - 1;
@@ -1396,6 +1465,8 @@ int init_gemm_f16s_attrs() {
 #define SET_ALL(G, NP_) SET_ROWS(G, NP_, false, false) SET_ROWS(G, NP_, true, false) SET_ROWS(G, NP_, false, true) SET_ROWS(G, NP_, true, true) \
                         SET_TN(G, NP_, false, false) SET_TN(G, NP_, true, false) SET_TN(G, NP_, false, true) SET_TN(G, NP_, true, true)
     SET_ALL(false, 3) SET_ALL(true, 3) SET_ALL(false, 1) SET_ALL(true, 1)
+    SET_ATTR((gemm_rows_f16s8_kernel<false, 3, true, true, false, true>), SMEM_ROWS_H8)
+    SET_ATTR((gemm_rows_f16s8_kernel<false, 1, true, true, false, true>), SMEM_ROWS_H8)
 #undef SET_ALL
 #undef SET_TN
 #undef SET_ROWS
@@ -1469,6 +1540,131 @@ int launch_rows_f16s(const GemmArgs& a0, dim3 grid, bool gather, int nprod, hipS
     return check_launch("gemm_nt(f16x3, 256x128)");
 }
 
+// ---- segmented region mode (glf_gemm_params.nseg) ----------------------------------------------------------------------
+// Host plan: per axis the band edges are the union of {min(d, H - d), max(d, H - d)} over the distinct |offset| values d, so the
+// in-range test of every segment is constant inside a band; a region is a product of bands, its segment mask the AND of the two
+// axis masks.  Returns the number of regions (dispatch order: descending segment count, stable), or -1 for too many bands.
+struct SegRegion { int y0, y1, x0, x1; unsigned mask; long long tiles; };
+
+static int seg_axis_bands(int len, int nseg, const int32_t* seg, int axis, int* lo, int* hi, unsigned* masks) {
+    int edges[2 * SEG_MAX + 2], ne = 0;
+    edges[ne++] = 0; edges[ne++] = len;
+    for (int s = 0; s < nseg; ++s) {
+        const int o = seg[3 * s + axis], d = o < 0 ? -o : o;
+        if (d == 0) continue;
+        const int e[2] = {d < len - d ? d : len - d, d < len - d ? len - d : d};
+        for (int i = 0; i < 2; ++i) {
+            const int v = e[i] < 0 ? 0 : (e[i] > len ? len : e[i]);
+            bool seen = false;
+            for (int k = 0; k < ne; ++k) seen |= edges[k] == v;
+            if (!seen) edges[ne++] = v;
+        }
+    }
+    for (int i = 1; i < ne; ++i)                    // insertion sort: at most 58 values
+        for (int k = i; k > 0 && edges[k - 1] > edges[k]; --k) { const int t = edges[k]; edges[k] = edges[k - 1]; edges[k - 1] = t; }
+    const int nb = ne - 1;
+    if (nb > SEG_MAX_BANDS) return -1;
+    for (int b = 0; b < nb; ++b) {
+        lo[b] = edges[b]; hi[b] = edges[b + 1];
+        unsigned m = 0;
+        for (int s = 0; s < nseg; ++s) {
+            const int o = seg[3 * s + axis];
+            if (lo[b] + o >= 0 && hi[b] - 1 + o < len) m |= 1u << s;
+        }
+        masks[b] = m;
+    }
+    return nb;
+}
+
+static int seg_plan(int n_img, int h, int w, int nseg, const int32_t* seg, SegRegion* out, long long* row_tiles) {
+    int ylo[SEG_MAX_BANDS], yhi[SEG_MAX_BANDS], xlo[SEG_MAX_BANDS], xhi[SEG_MAX_BANDS];
+    unsigned ym[SEG_MAX_BANDS], xm[SEG_MAX_BANDS];
+    const int nby = seg_axis_bands(h, nseg, seg, 0, ylo, yhi, ym), nbx = seg_axis_bands(w, nseg, seg, 1, xlo, xhi, xm);
+    if (nby < 0 || nbx < 0) return -1;
+    int nreg = 0;
+    long long total = 0;
+    for (int cnt = nseg; cnt >= 0; --cnt)           // descending segment count, row-major inside a count
+        for (int by = 0; by < nby; ++by)
+            for (int bx = 0; bx < nbx; ++bx) {
+                const unsigned m = ym[by] & xm[bx];
+                if (__builtin_popcount(m) != cnt) continue;
+                SegRegion& r = out[nreg++];
+                r.y0 = ylo[by]; r.y1 = yhi[by]; r.x0 = xlo[bx]; r.x1 = xhi[bx]; r.mask = m;
+                r.tiles = ((long long)n_img * (r.y1 - r.y0) * (r.x1 - r.x0) + BM8 - 1) / BM8;
+                total += r.tiles;
+            }
+    *row_tiles = total;
+    return nreg;
+}
+
+static int seg_check(int n_img, int h, int w, int nseg, const int32_t* seg, const char* who) {
+    GLF_REQUIRE(seg != nullptr, GLF_ERR_NULL, "%s: null segment list", who);
+    GLF_REQUIRE(nseg >= 1 && nseg <= SEG_MAX, GLF_ERR_UNSUPPORTED, "%s: nseg must be in [1, %d] (got %d)", who, SEG_MAX, nseg);
+    GLF_REQUIRE(n_img > 0 && h > 0 && w > 0 && (long long)n_img * h * w < 2147483647LL, GLF_ERR_BAD_SHAPE, "%s: bad map geometry", who);
+    return GLF_OK;
+}
+
+// device tables of the plans used so far: made once per (device, geometry, lda, segment list), never freed
+struct SegPlanDev { int dev, n_img, h, w, lda, nseg; int32_t seg[3 * SEG_MAX]; int* tab; long long row_tiles; };
+static std::mutex g_seg_mu;
+static std::vector<SegPlanDev> g_seg_plans;
+
+int launch_rows_f16s_seg(const GemmArgs& a0, const glf_gemm_params* p, int nprod, hipStream_t s) {
+    GemmArgs a = a0;
+    a.zeros = zero_page();
+    const int n_img = p->n_img, h = p->hd, w = p->wd, nseg = p->nseg;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return fail(GLF_ERR_LAUNCH, "gemm_nt(seg): hipGetDevice failed");
+    const int* tab = nullptr;
+    long long row_tiles = 0;
+    {
+        std::lock_guard<std::mutex> lk(g_seg_mu);
+        for (const SegPlanDev& q : g_seg_plans)
+            if (q.dev == dev && q.n_img == n_img && q.h == h && q.w == w && q.lda == p->lda && q.nseg == nseg &&
+                memcmp(q.seg, p->seg, sizeof(int32_t) * 3 * nseg) == 0) { tab = q.tab; row_tiles = q.row_tiles; break; }
+        if (!tab) {
+            SegRegion regs[SEG_MAX_REGIONS];
+            const int nreg = seg_plan(n_img, h, w, nseg, p->seg, regs, &row_tiles);
+            if (nreg < 0) return fail(GLF_ERR_UNSUPPORTED, "gemm_nt(seg): more than %d bands on an axis", SEG_MAX_BANDS);
+            if (row_tiles * a.tiles_n >= 2147483647LL) return fail(GLF_ERR_BAD_SHAPE, "gemm_nt(seg): grid out of range");
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
+                return fail(GLF_ERR_UNSUPPORTED, "gemm_nt(seg): the first launch of a plan allocates its table -- run it once before capturing");
+            std::vector<int> host(SEG_TAB_INTS, 0);
+            long long first = 0;
+            for (int r = 0; r < SEG_TAB_REGIONS; ++r) {
+                host[r] = r < nreg ? (int)first : 2147483647;
+                if (r < nreg) {
+                    int* e = host.data() + SEG_TAB_REGIONS + SEG_REGION_INTS * r;
+                    e[0] = regs[r].y0; e[1] = regs[r].x0; e[2] = regs[r].y1 - regs[r].y0; e[3] = regs[r].x1 - regs[r].x0;
+                    e[4] = (int)regs[r].mask; e[5] = n_img * e[2] * e[3];
+                    first += regs[r].tiles;
+                }
+            }
+            long long offs[SEG_MAX] = {0};
+            for (int i = 0; i < nseg; ++i) offs[i] = ((long long)p->seg[3 * i] * w + p->seg[3 * i + 1]) * p->lda + p->seg[3 * i + 2];
+            memcpy(host.data() + SEG_TAB_OFFS, offs, sizeof(offs));
+            int* d = nullptr;
+            hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), SEG_TAB_INTS * sizeof(int));
+            if (e == hipSuccess) e = hipMemcpy(d, host.data(), SEG_TAB_INTS * sizeof(int), hipMemcpyHostToDevice);
+            if (e != hipSuccess) return fail(GLF_ERR_WORKSPACE, "gemm_nt(seg): plan table: %s", hipGetErrorString(e));
+            SegPlanDev q;
+            q.dev = dev; q.n_img = n_img; q.h = h; q.w = w; q.lda = p->lda; q.nseg = nseg; q.tab = d; q.row_tiles = row_tiles;
+            memset(q.seg, 0, sizeof(q.seg));
+            memcpy(q.seg, p->seg, sizeof(int32_t) * 3 * nseg);
+            g_seg_plans.push_back(q);
+            tab = d;
+        }
+    }
+    a.seg_tab = tab; a.seg_kx = p->seg_kx; a.rect = 0; a.accumulate = 0;
+    a.tiles_m = (int)row_tiles;
+    dim3 g2((unsigned)(row_tiles * a.tiles_n), 1, 1);
+    a.flags = ((a.tiles_n >= 8 ? 4 : 0) & 0xff) << 8;          // grouped tile order, as the plain launch
+    if (nprod == 3) hipLaunchKernelGGL((gemm_rows_f16s8_kernel<false, 3, true, true, false, true>), g2, dim3(NT8), SMEM_ROWS_H8, s, a);
+    else hipLaunchKernelGGL((gemm_rows_f16s8_kernel<false, 1, true, true, false, true>), g2, dim3(NT8), SMEM_ROWS_H8, s, a);
+    return check_launch("gemm_nt(f16x3, 256x128, segmented)");
+}
+
 int launch_tn_f16s(const GemmArgs& a0, dim3 grid, bool gather, int nprod, hipStream_t s) {
     GemmArgs a = a0;
     a.zeros = zero_page();
@@ -1512,3 +1708,21 @@ int launch_amax(const float* x, long long rows, int cols, long long ld, int vec,
 }
 
 }  // namespace glf
+
+extern "C" int glf_gemm_nt_seg_plan(int32_t n_img, int32_t h, int32_t w, int32_t nseg, const int32_t* seg, int32_t* regions,
+                                    int32_t* n_regions, int64_t* row_tiles) {
+    using namespace glf;
+    GLF_REQUIRE(regions && n_regions && row_tiles, GLF_ERR_NULL, "gemm_nt_seg_plan: null argument");
+    if (int rc = seg_check(n_img, h, w, nseg, seg, "gemm_nt_seg_plan")) return rc;
+    SegRegion regs[SEG_MAX_REGIONS];
+    long long total = 0;
+    const int nreg = seg_plan(n_img, h, w, nseg, seg, regs, &total);
+    GLF_REQUIRE(nreg >= 0, GLF_ERR_UNSUPPORTED, "gemm_nt_seg_plan: more than %d bands on an axis", SEG_MAX_BANDS);
+    for (int r = 0; r < nreg; ++r) {
+        int32_t* e = regions + 6 * r;
+        e[0] = regs[r].y0; e[1] = regs[r].y1; e[2] = regs[r].x0; e[3] = regs[r].x1; e[4] = (int32_t)regs[r].mask; e[5] = (int32_t)regs[r].tiles;
+    }
+    *n_regions = nreg;
+    *row_tiles = total;
+    return GLF_OK;
+}

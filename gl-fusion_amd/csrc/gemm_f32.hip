@@ -974,6 +974,23 @@ extern "C" int glf_gemm_nt(const float* A, const float* B, const float* bias, fl
     a.vec_a = aligned16(A) && (p->lda % 4 == 0) && (p->batch_stride_a % 4 == 0);
     a.vec_b = aligned16(B) && (p->ldb % 4 == 0) && (p->batch_stride_b % 4 == 0) && (p->tap_stride_b % 4 == 0);
     dim3 grid(a.tiles_m * a.tiles_n, 1, p->batch);
+    if (p->nseg != 0) {                 // segmented region mode: the SEG instantiations of the 8-wave split-fp16 kernel only
+        GLF_REQUIRE(p->nseg >= 1 && p->nseg <= GLF_SEG_MAX && p->seg != nullptr, GLF_ERR_UNSUPPORTED, "glf_gemm_nt: nseg must be in [1, %d] with a segment list", GLF_SEG_MAX);
+        GLF_REQUIRE(prec >= 2 && glf::f16s_rows_ok(a) && p->a_presplit && p->b_presplit && p->amax_a && p->amax_b, GLF_ERR_UNSUPPORTED,
+                    "glf_gemm_nt: segments need precision 3 / 4, the aligned fast path and both operands pre-split with their amax");
+        GLF_REQUIRE(!p->gather && p->taps == 1 && !p->rect && !p->accumulate && !p->colstats && !p->colmax && p->batch == 1, GLF_ERR_UNSUPPORTED,
+                    "glf_gemm_nt: segments extend a plain NT launch (no gather, rect, accumulate, colstats or batch)");
+        GLF_REQUIRE(p->n_img > 0 && p->hd > 0 && p->wd > 0 && (long long)p->n_img * p->hd * p->wd == p->M && p->K <= p->lda && p->N <= p->ldc,
+                    GLF_ERR_BAD_SHAPE, "glf_gemm_nt: segments need M (%d) == n_img*hd*wd, K <= lda and N <= ldc", p->M);
+        // (overhang rows walk the zero page from end to end of the chain, 16 bytes per lane of a 32-float row: it must hold all of it)
+        GLF_REQUIRE(p->seg_kx >= BK && p->seg_kx % BK == 0 && (long long)p->K + (long long)p->nseg * p->seg_kx <= p->ldb &&
+                    (long long)p->K + (long long)p->nseg * p->seg_kx + BK <= glf::ZERO_PAGE_FLOATS, GLF_ERR_UNSUPPORTED,
+                    "glf_gemm_nt: segments need seg_kx %% 32 == 0 and K + nseg * seg_kx <= ldb, < 2^18");
+        for (int i = 0; i < p->nseg; ++i)
+            GLF_REQUIRE(p->seg[3 * i + 2] >= 0 && p->seg[3 * i + 2] % 4 == 0 && p->seg[3 * i + 2] + p->seg_kx <= p->lda, GLF_ERR_UNSUPPORTED,
+                        "glf_gemm_nt: segment %d: acol must be a multiple of 4 with acol + seg_kx <= lda", i);
+        return glf::launch_rows_f16s_seg(a, p, prec == 2 ? 3 : 1, glf::S(stream));
+    }
     if (p->M <= 64 && !p->gather && p->taps == 1 && p->batch == 1 && !p->rect && !p->colstats && !p->a_presplit && !p->b_presplit && a.vec_a &&
         a.vec_b && p->K % 16 == 0 && p->N >= 64) {
         hipLaunchKernelGGL(gemm_skinny_nt_kernel, dim3((p->N + SK_COLS - 1) / SK_COLS), dim3(256), 0, glf::S(stream), A, B, bias, C, p->M, p->N, p->K,

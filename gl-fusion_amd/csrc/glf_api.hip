@@ -34,6 +34,7 @@ int precision() { return g_precision.load(std::memory_order_relaxed); }
 //   * one ring of RING floats per (device, stream) for operand maxima the library measures itself (f16x3 with
 //     amax_a / amax_b == NULL).  A slot is written (memset + amax kernel) and read (GEMM) on that one stream, in
 //     order, so reuse after the ring wraps is ordered by the stream itself.
+//   * one 2 KB plan table per (device, geometry, segment list) of a segmented NT launch (gemm_f16s.hip launch_rows_f16s_seg).
 // Both are created lazily on first use on a device / stream and live until the process exits.
 constexpr unsigned RING = 1u << 12;
 struct StreamRing { float* base = nullptr; unsigned pos = 0; };

@@ -19,7 +19,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ._lib import GemmEpilogue, GemmParams, TN_OIHW_MAX_TAPS, WeightJob, WJ_AMAX, WJ_COPY, WJ_PACK, WJ_PASSES, WJ_PASS_OF, WJ_TAP_MAJOR, WJ_TAP_MAJOR_T, WJ_TRANSPOSE, WJ_ZERO, check, lib
+from ._lib import GemmEpilogue, GemmParams, SEG_MAX, TN_OIHW_MAX_TAPS, WeightJob, WJ_AMAX, WJ_COPY, WJ_PACK, WJ_PASSES, WJ_PASS_OF, WJ_TAP_MAJOR, WJ_TAP_MAJOR_T, WJ_TRANSPOSE, WJ_ZERO, check, lib
 
 
 # ----------------------------------------------------------------------------------------
@@ -185,7 +185,7 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
          split: int = 1, rect: bool = False, amax_a: Optional[torch.Tensor] = None,
          amax_b: Optional[torch.Tensor] = None, amax_c: Optional[torch.Tensor] = None,
          colstats: Optional[torch.Tensor] = None, a_packed: bool = False, b_packed: bool = False,
-         colmax: Optional[torch.Tensor] = None, epilogue=None, oihw: bool = False, foreign=None) -> None:
+         colmax: Optional[torch.Tensor] = None, epilogue=None, oihw: bool = False, foreign=None, seg=None) -> bool:
     """mode in {'nt','nn','tn'}; geo = (n_img, hs, ws, hd, wd, kh, kw, stride, pad, dil).
     epilogue ('nt' only): (residual or None, its row stride, relu) -- the call goes to glf_gemm_nt_epilogue, which stores
     act(alpha * acc + bias[n] + residual[m][n]) once (bias is then required: the folded BatchNorm shift).
@@ -195,7 +195,11 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
     a_packed / b_packed: A / B is the packed pre-split image packed_of() made with the same amax_a / amax_b.
     oihw ('tn' only, see tn_oihw_ok): Cm is the parameter-shaped [M][N][taps] gradient -- the second stage of the reduction
     stores every tap of an element side by side, zeros for the taps outside `mask` (which may then be empty: nothing is
-    contracted); foreign = (tap, src, row stride): that tap's [M][N] values are copied from src."""
+    contracted); foreign = (tap, src, row stride): that tap's [M][N] values are copied from src.
+    seg ('nt' only, glf_gemm_params.nseg): (kx, [(oy, ox, acol), ...], dense FLOPs, executed FLOPs) -- the segmented region
+    mode over the geo = (n_img, h, w, h, w, 1, 1, 1, 0, 1) map; the two FLOP counts are what the profiler record carries.  A
+    launch the library refuses as unsupported returns False (nothing ran: the caller takes its other route); every other
+    call returns True."""
     p = GemmParams()
     p.M, p.N, p.K, p.lda, p.ldb, p.ldc = M, N, K, lda, ldb, ldc
     p.taps, p.tap_mask, p.tap_stride_b, p.gather = taps, mask, tap_stride_b, gather
@@ -216,6 +220,11 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
         p.c_oihw = 1
         if foreign is not None:
             p.foreign_tap, p.foreign_src, p.foreign_ld = int(foreign[0]), _p(foreign[1]), int(foreign[2])
+    if seg is not None:
+        if mode != "nt":
+            raise ValueError("gemm: segments exist for mode 'nt' only")
+        seg_arr = (C.c_int32 * (3 * len(seg[1])))(*[v for t in seg[1] for v in t])
+        p.nseg, p.seg_kx, p.seg = len(seg[1]), int(seg[0]), C.cast(seg_arr, C.c_void_p)
     ws = None
     if mode == "tn" and (split > 1 or oihw) and mask:
         # two-stage reduction: the slices store partial sums, a second kernel adds them in a fixed order -- no atomics, no
@@ -234,7 +243,10 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
     elif epilogue is not None:
         raise ValueError("gemm: the fused epilogue exists for mode 'nt' only")
     elif mode == "nt":
-        check(lib.glf_gemm_nt(_p(A), _p(B), _p(bias), _p(Cm), C.byref(p), _stream()), "gemm_nt")
+        rc = lib.glf_gemm_nt(_p(A), _p(B), _p(bias), _p(Cm), C.byref(p), _stream())
+        if seg is not None and rc == -2:          # GLF_ERR_UNSUPPORTED
+            return False
+        check(rc, "gemm_nt")
     elif mode == "nn":
         check(lib.glf_gemm_nn(_p(A), _p(B), _p(bias), _p(Cm), C.byref(p), _stream()), "gemm_nn")
     elif mode == "tn":
@@ -256,8 +268,13 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
             abytes = 4.0 * batch * (K * M + (src_rows if src_rows else K) * N + M * N * kept_taps)
         else:
             abytes = 4.0 * batch * ((src_rows if src_rows else M) * K + N * K * kept_taps + M * N * (2 if accumulate else 1))
-        prof.append((KERNEL_NAMES[(mode, gather != 0)], dense, dense * kept_taps / taps * in_range, ev0, ev1,
+        executed = dense * kept_taps / taps * in_range
+        if seg is not None:
+            dense, executed = float(seg[2]), float(seg[3])
+            abytes = 4.0 * (M * lda + N * (K + len(seg[1]) * seg[0]) + M * N)
+        prof.append((KERNEL_NAMES[(mode, gather != 0)], dense, executed, ev0, ev1,
                      (M, N, K, taps, kept_taps, batch, split, geo[8] if geo else 0, geo[9] if geo else 0), abytes))
+    return True
 
 
 # ----------------------------------------------------------------------------------------
@@ -1155,6 +1172,85 @@ def aspp_centre_weights(weights) -> torch.Tensor:
     return Wc
 
 
+# The head's input gradient as ONE launch (glf_gemm_params.nseg): the stacked centre contraction G Wc^T extended by one extra
+# segment per kept off-centre tap of the dilated branches -- every element of dx stored once, where the off-centre taps used
+# to be region-mode launches that read dx back and added to it.  0: those launches.
+ASPP_DGRAD_ONE = os.environ.get("GLF_ASPP_DGRAD_ONE", "1") != "0"
+_dgrad_cache = {}
+
+
+def aspp_dgrad_segments(dils, h: int, w: int, cout: int):
+    """[(branch, tap, oy, ox, acol)] of the kept off-centre taps of the dilated branches on an h x w map, branch by branch in tap
+    order: the tap reads the gradient pixel (y + oy, x + ox) of column block acol of the stacked gradient image."""
+    segs = []
+    for i, d in enumerate(dils, start=1):
+        off = tap_mask(2, h, w, h, w, 3, 3, 1, d, d) & ~CENTRE_TAP
+        for t in range(9):
+            if (off >> t) & 1:
+                ky, kx = divmod(t, 3)
+                segs.append((i, t, (1 - ky) * d, (1 - kx) * d, i * cout))
+    return segs
+
+
+def aspp_dgrad_weights(weights, segs) -> torch.Tensor:
+    """Wd [(k + nseg) Cout][Cin]: the rows of aspp_centre_weights (Wc), then the tap slab [Cout][Cin] of every segment in
+    aspp_dgrad_segments order.  Built and cached like Wc (GLF_WJ_COPY jobs of the multi-tensor refresh, the combined version stamp
+    of its sources for the images derived from it); one buffer per set of kept taps, which depends on the map's size."""
+    w0 = weights[0]
+    cout, cin, k = w0.shape[0], w0.shape[1], len(weights)
+    blocks = [(i, 4 if weights[i].shape[2] * weights[i].shape[3] == 9 else 0) for i in range(k)] + [(i, t) for i, t, _, _, _ in segs]
+    sk = ",".join("%d.%d" % b for b in blocks[k:])
+    per = _dgrad_cache.get(id(w0))
+    if per is None or per[0]() is not w0:
+        per = _dgrad_cache[id(w0)] = (weakref.ref(w0, lambda _r, k_=id(w0): _dgrad_cache.pop(k_, None)), {})
+    Wd = per[1].get(sk)
+    if (Wd is None or Wd.device != w0.device or tuple(Wd.shape) != (len(blocks) * cout, cin)
+            or any(r() is not t for r, t in zip(Wd._glf_sources, weights))):
+        Wd = torch.empty(len(blocks) * cout, cin, dtype=torch.float32, device=w0.device)
+        refs = [weakref.ref(t) for t in weights]
+        Wd._glf_version_fn = lambda refs=refs: tuple((r()._version, r().data_ptr()) if r() is not None else None for r in refs)
+        Wd._glf_sources = refs
+        per[1][sk] = Wd
+    for b, (i, tap) in enumerate(blocks):
+        t = weights[i]
+        taps = t.shape[2] * t.shape[3]
+        src, dst = _contig(t.detach()), Wd[b * cout:(b + 1) * cout]
+        kind, dims = WJ_COPY, (cout * cin, 0, 0) if taps == 1 else (cout * cin, taps, tap)
+        tag = "dgrad1:%s:%d" % (sk, b)
+        im, fresh = _wimage(t, tag, kind, src, dims, lambda dst=dst: dst)
+        if im.dst.data_ptr() != dst.data_ptr():       # the stacked buffer was re-created: re-register
+            _registry(t.device).drop(im.key)
+            im, fresh = _wimage(t, tag, kind, src, dims, lambda dst=dst: dst)
+        if fresh:
+            one = src if taps == 1 else tap_major(t)[tap]
+            check(lib.glf_copy_frames(_p(one), cout * cin, _p(im.dst), cout * cin, 1, cout * cin, _stream()), "aspp_dgrad_weights")
+    return Wd
+
+
+def _aspp_dgrad_one(G, am_g, weights, dils, dx, slot, n: int, h: int, w: int, cin: int, cout: int) -> bool:
+    """dx = G Wd^T in one segmented launch; False when this head does not take that route (the caller runs today's launches)."""
+    k = len(weights)
+    ldu = k * cout
+    segs = aspp_dgrad_segments(dils, h, w, cout)
+    if not ASPP_DGRAD_ONE or _PREC[0] not in (2, 3) or not segs or len(segs) > SEG_MAX or cout % 32 != 0 or ldu % 32 != 0:
+        return False
+    Wd = aspp_dgrad_weights(weights, segs)
+    am_wd = amax_of(Wd)
+    WdT = weight_T(Wd, Wd)
+    wb = weight_packed(WdT, Wd, "wT", am_wd)
+    if wb is None:
+        return False
+    rows, ldb = n * h * w, Wd.shape[0]
+    # executed work: the centre slices of every pixel plus the (pixel, in-range segment) pairs; dense: what the stacked launch
+    # and the off-centre launches it replaces reported together (every tap of those branches, padding included)
+    pairs = sum(max(0, h - abs(oy)) * max(0, w - abs(ox)) for _, _, oy, ox, _ in segs)
+    executed = 2.0 * cin * cout * (rows * k + n * pairs)
+    dense = 2.0 * rows * cin * (ldu + 9 * cout * len({i for i, _, _, _, _ in segs}))
+    return gemm("nt", G, wb, dx, M=rows, N=cin, K=ldu, lda=ldu, ldb=ldb, ldc=cin, geo=(n, h, w, h, w, 1, 1, 1, 0, 1),
+                amax_a=am_g, amax_b=am_wd, amax_c=slot, a_packed=True, b_packed=True,
+                seg=(cout, [(oy, ox, acol) for _, _, oy, ox, acol in segs], dense, executed))
+
+
 def aspp_centre_ok(x: torch.Tensor, convs) -> bool:
     """True when AsppCentreFn takes the conv branches `convs` (modules with .weight/.bias/.stride/.padding/.dilation) of an
     ASPP over x: a split-fp16 precision with pre-split operands and packed gradients, one 1x1 conv followed by 3x3 stride-1
@@ -1289,13 +1385,17 @@ class AsppCentreFn(Function):
         am_wc = amax_of(Wc)
         dx = None
         if ctx.needs_input_grad[0]:
-            WcT = weight_T(Wc, Wc)
-            wb, pb = pick(WcT, weight_packed(WcT, Wc, "wT", am_wc), True)
             dx = torch.empty_like(x)
             slot = amax_slot(dev)
-            gemm("nt", G, wb, dx, M=rows, N=cin, K=ldu, lda=ldu, ldb=ldu, ldc=cin, amax_a=am_g, amax_b=am_wc, amax_c=slot,
-                 a_packed=True, b_packed=pb)
-            for i in range(1, k):
+            # one segmented launch stores dx; where it does not apply: the stacked centre launch, then one accumulating launch per
+            # branch that keeps off-centre taps
+            one = _aspp_dgrad_one(G, am_g, weights, dils, dx, slot, n, h, w, cin, cout)
+            if not one:
+                WcT = weight_T(Wc, Wc)
+                wb, pb = pick(WcT, weight_packed(WcT, Wc, "wT", am_wc), True)
+                gemm("nt", G, wb, dx, M=rows, N=cin, K=ldu, lda=ldu, ldb=ldu, ldc=cin, amax_a=am_g, amax_b=am_wc, amax_c=slot,
+                     a_packed=True, b_packed=pb)
+            for i in range(1, 1 if one else k):
                 d = dils[i - 1]
                 mask = tap_mask(2, h, w, h, w, 3, 3, 1, d, d)
                 off = mask & ~CENTRE_TAP

@@ -10,12 +10,15 @@
  * Conventions
  *   - plain pointers and sizes only; every tensor and workspace buffer is CALLER-OWNED (inputs,
  *     outputs, workspace, saved-for-backward) and no caller pointer is kept after return.  The
- *     library owns exactly two kinds of small device allocations, made lazily and kept until the
+ *     library owns exactly three kinds of small device allocations, made lazily and kept until the
  *     process exits: a 1 MiB page of zeros per device (the split-fp16 kernels load conv-padding
- *     and tile-overhang rows from it) and a 16 KiB ring of floats per (device, stream) that is
+ *     and tile-overhang rows from it), a 16 KiB ring of floats per (device, stream) that is
  *     used only when a precision-3 contraction is called with amax_a / amax_b == NULL (the
- *     library then measures the operand maxima itself, on that stream).
- *   - every function only ENQUEUES work on `stream` and returns; no host synchronisation.
+ *     library then measures the operand maxima itself, on that stream), and a 2 KiB plan table per
+ *     distinct (device, geometry, segment list) of a segmented glf_gemm_nt launch (nseg > 0).
+ *   - every function only ENQUEUES work on `stream` and returns; no host synchronisation (one
+ *     exception: the FIRST segmented launch of a plan copies its table with a blocking hipMemcpy
+ *     and therefore refuses to run on a capturing stream; later launches of that plan do neither).
  *   - return 0 on success, a negative glf_status otherwise; text via glf_last_error()
  *     (thread-local).  No exception crosses this boundary.
  *   - activations are channels-last: a tensor [N,H,W,C] is the row-major matrix
@@ -159,8 +162,32 @@ typedef struct {
     int32_t foreign_tap;        /* with c_oihw and foreign_src: the tap (not in tap_mask) whose [M][N] values are copied from     */
     const float* foreign_src;   /* foreign_src (row stride foreign_ld floats, % 4 == 0, 16-byte aligned) -- a result another      */
     int64_t foreign_ld;         /* contraction produced (the ASPP centre taps, stacked).  NULL: no such tap.                      */
+    int32_t nseg;               /* glf_gemm_nt only, segmented region mode (0 = off): a plain NT contraction (gather 0, taps 1,   */
+    int32_t seg_kx;             /* rect 0) over the n_img x hd x wd pixel rows of A, extended by nseg <= GLF_SEG_MAX extra        */
+    int32_t* seg;               /* segments.  seg is a HOST array [nseg][3] = (oy, ox, acol), only read; segment s adds to the    */
+                                /* output row of pixel (n, y, x)   sum_{j < seg_kx} A[(n, y+oy, x+ox)][acol + j] * B[c][K + s*seg_kx + j] */
+                                /* wherever (y+oy, x+ox) lies inside the map (ldb >= K + nseg*seg_kx, acol + seg_kx <= lda).  The  */
+                                /* map is cut into the rectangles of glf_gemm_nt_seg_plan, inside each of which the set of        */
+                                /* in-range segments is constant: a row tile walks the K columns, then its rectangle's segments   */
+                                /* by ascending s, and every output element is stored ONCE (no accumulate, no zero fill, no       */
+                                /* atomics; bitwise reproducible; amax_c reported).  Precision 3 / 4 with BOTH operands pre-split, */
+                                /* K and seg_kx multiples of 32, acol a multiple of 4, batch 1, no colstats; anything else is     */
+                                /* GLF_ERR_UNSUPPORTED.  The plan's small device table is made on the first launch of a given     */
+                                /* (geometry, segment list) and kept: later launches allocate and copy nothing (graph-capturable). */
 } glf_gemm_params;
 #define GLF_TN_OIHW_MAX_TAPS 9
+#define GLF_SEG_MAX 28
+#define GLF_SEG_MAX_REGIONS 49
+#define GLF_SEG_ROW_TILE 256
+
+/* Host-only plan of a segmented-region glf_gemm_nt launch (glf_gemm_params.nseg): the rectangles of the h x w map in DISPATCH
+ * order (descending number of in-range segments).  seg = [nseg][3] (oy, ox, acol; acol is not used here).  Per axis the band
+ * edges are the union of {min(d, H-d), max(d, H-d)} (clamped to [0, H]) over the distinct |offset| values d > 0 present; more
+ * than 7 bands on an axis is GLF_ERR_UNSUPPORTED.  regions receives [*n_regions][6] = (y0, y1, x0, x1, segment mask, row tiles)
+ * with room for GLF_SEG_MAX_REGIONS entries; a row tile is GLF_SEG_ROW_TILE of the n_img * (y1-y0) * (x1-x0) rows of its
+ * rectangle (the last one ragged).  *row_tiles = their sum: the launch's grid is that times ceil(N / 128). */
+int glf_gemm_nt_seg_plan(int32_t n_img, int32_t h, int32_t w, int32_t nseg, const int32_t* seg, int32_t* regions,
+                         int32_t* n_regions, int64_t* row_tiles);
 
 /* *out = max |x| over the [rows, cols] view with row stride ld (elements); out is a device float. */
 int glf_amax(const float* x, int64_t rows, int cols, int64_t ld, float* out, glf_stream_t stream);
