@@ -188,6 +188,12 @@ class Trainer:
             self.optimizer = Adam(self.model.parameters(), lr=opt["lr"], weight_decay=opt["weight_decay"])    # main.py:162-165, fused
         else:
             raise ValueError(f"glfusion_amd: config['net']['opt']['opt_name'] = {name!r}; main.py:158-165 has the branches 'SGD' and 'Adam'")
+        # config['train']['clip_grad_norm'] (absent = off): every step clips by this global gradient norm and skips itself when the
+        # norm is not finite, all on the device (optim._Fused.set_grad_clip).  The optimizer step is outside a recorded graph and
+        # behind reducer.finalize(), so the eager, cycle and graph-replayed steps and every rank see the same (reduced) norm.
+        self.clip_grad_norm = tr.get("clip_grad_norm")
+        if self.clip_grad_norm is not None:
+            self.optimizer.set_grad_clip(float(self.clip_grad_norm))
         self.scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.optimizer, T_max=tr["num_epochs"])   # main.py:168
         # config['train']['save_optimizer'] (absent = False): save() also writes opt_%05d.pth, the file load() resumes the optimizer from
         self.save_optimizer = bool(tr.get("save_optimizer", False))
@@ -281,7 +287,10 @@ class Trainer:
             # the epoch's Dice sums its counters over ranks: a collective, so EVERY rank computes it (only rank 0 prints)
             dice = {v: self._calculate_overlap_metrics(masks[v], pred[v].detach())[1] for v in self.test_view}
             if self.print_val:
-                print(f"epoch {epoch}: loss {float(loss):.2f} dice {dice}")
+                clip = ""
+                if self.clip_grad_norm is not None:      # the epoch's one read of the device values, beside float(loss)
+                    clip = f" grad-norm {float(self.optimizer.grad_norm):.4g} skipped-steps {int(self.optimizer.skipped_steps)}"
+                print(f"epoch {epoch}: loss {float(loss):.2f}{clip} dice {dice}")
                 if self.config["train"].get("validate_every_epoch", True):
                     # main.py:259-274: validation runs on the printing rank alone, over every clip of the splits, with NO collective
                     # (the other ranks have already moved on to the next epoch's gradient all-reduces and wait there)
@@ -372,6 +381,11 @@ class Trainer:
                         img, mask, _ = per_view[v][i]                          # [1,112,112,T], [5,112,112,T]
                         imgs[v] = img.permute(3, 0, 1, 2).contiguous()         # main.py:361-365: frames become the batch
                         masks[v] = mask.permute(3, 0, 1, 2).contiguous()
+                    # every view draws its own clip window (loader.py:429-458), and one that runs past the end of its volume comes
+                    # back short: the views keep their common leading frames (the model stacks the views frame by frame)
+                    frames = min(t.shape[0] for t in imgs.values())
+                    imgs = {v: t[:frames] for v, t in imgs.items()}
+                    masks = {v: t[:frames] for v, t in masks.items()}
                     out = self.model(imgs)
                     pred = out[0] if is_fuse else out[1]
                     for v in self.test_view:

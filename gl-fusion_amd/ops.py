@@ -2476,6 +2476,9 @@ class StackViewsFn(Function):
         xs = [_contig(_chk(t, "view feature", dt)) for t in xs]
         n, h, w, c = xs[0].shape
         v = len(xs)
+        if any(t.shape != xs[0].shape for t in xs):      # the copies below take every view at the first one's extents
+            raise RuntimeError(f"glfusion_amd: the views of one batch must have one shape, got {[tuple(t.shape) for t in xs]} "
+                               "(the same number of frames in every view)")
         out = torch.empty(n, v, h, w, c, dtype=xs[0].dtype, device=xs[0].device)
         inner = h * w * c
         amax_bound(out, xs)                  # known BEFORE the copy: the largest of the views' maxima (fp32 storage only)

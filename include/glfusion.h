@@ -831,6 +831,33 @@ int glf_adam_step(const int64_t* table, int n_rows, double lr, double beta1, dou
  * momentum < 0, nesterov with momentum <= 0 or dampening != 0). */
 int glf_sgd_step(const int64_t* table, int n_rows, double lr, double momentum, double dampening, double weight_decay,
                  int nesterov, int first, glf_stream_t s);
+/* Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) with a non-finite guard, on the device
+ * throughout: nothing here reads a value back or blocks the host.  All tables have the format above, the gradient in column 1.
+ * glf_grad_sumsq: partials[row] (DEVICE double[n_rows]) = sum of grad^2 over the row, accumulated in double in a fixed order,
+ * no atomics: the same bits on every run.  Only column 1 and column 4 (n) of the table are read.
+ * glf_grad_clip_coef: adds partials[0..n) in index order in double and writes record (DEVICE float[4]):
+ *   record[0] = norm = (float)sqrt(sum)
+ *   record[1] = coef = min(1.0f, (float)max_norm / (norm + 1e-6f)) in float, every operation individually rounded (what
+ *               clip_grad_norm_ evaluates on a float32 norm); 0.0f when the sum is not finite
+ *   record[2] = ok = 1.0f when the sum is finite, 0.0f otherwise;  record[3] = 0.0f
+ * and adds 1 to *skipped (DEVICE int64) when the sum is not finite.  max_norm = +inf is legal: coef is then 1 and only the
+ * guard is active.  Partials of several glf_grad_sumsq calls may be laid end to end into one glf_grad_clip_coef.
+ * glf_adam_step_clipped / glf_sgd_step_clipped: their unclipped twins with every gradient element replaced by
+ * grad * record[1] (individually rounded, before the weight decay; the stored gradient is NOT rewritten); with
+ * record[2] == 0 nothing is read or written beyond the record -- not param, exp_avg, exp_avg_sq or the momentum buffer, the
+ * `first` call that was to write a new buffer included.  Because the host cannot know that such a call was skipped,
+ * glf_sgd_step_clipped also takes a row whose momentum buffer still begins with the bit pattern 0x7fc0dead (a quiet NaN no
+ * arithmetic produces; the caller fills a new buffer with it) as `first`, whatever the argument says.
+ * glf_grad_scale: grad *= record[1] in place over the table; writes nothing when record[2] == 0 or record[1] == 1.
+ * Checked before any HIP runtime call: GLF_ERR_NULL (any pointer), then GLF_ERR_BAD_SHAPE (n_rows < 1, n < 1, table or
+ * partials not 8-byte aligned, max_norm negative or NaN, and what the unclipped twin refuses). */
+int glf_grad_sumsq(const int64_t* table, int n_rows, double* partials, glf_stream_t s);
+int glf_grad_clip_coef(const double* partials, int n, double max_norm, float* record, int64_t* skipped, glf_stream_t s);
+int glf_adam_step_clipped(const int64_t* table, int n_rows, double lr, double beta1, double beta2, double eps,
+                          double weight_decay, int64_t step, const float* record, glf_stream_t s);
+int glf_sgd_step_clipped(const int64_t* table, int n_rows, double lr, double momentum, double dampening, double weight_decay,
+                         int nesterov, int first, const float* record, glf_stream_t s);
+int glf_grad_scale(const int64_t* table, int n_rows, const float* record, glf_stream_t s);
 
 /* ---------------------------------------------------------------------------------------
  * Temporal cycle-consistency loss: Trainer.seg_cycle and Trainer.dense_seg_cycle

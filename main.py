@@ -32,9 +32,14 @@ def main(rank, config):
     parser.add_argument("--resume", action="store_true",
                         help="continue from the latest checkpoint in config['train']['save_dir'] (config['train']['is_load']); "
                              "checkpoints then also hold the optimizer state (config['train']['save_optimizer'])")
+    parser.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                        help="clip every step by the global gradient norm X and skip steps with a non-finite one, on the device "
+                             "(config['train']['clip_grad_norm']; inf = the guard alone); default: off")
     args = parser.parse_args()
     if args.opt:
         config["net"]["opt"]["opt_name"] = args.opt
+    if args.clip_grad_norm is not None:
+        config["train"]["clip_grad_norm"] = args.clip_grad_norm
     if args.resume:
         config["train"]["is_load"] = config["train"]["save_optimizer"] = True
     if args.precision:
