@@ -666,8 +666,9 @@ int glf_bn_apply(const float* x, int ldx, const float* residual, int ldr, float*
                  const float* mean, const float* invstd, const float* gamma, const float* beta,
                  int rows, int c, int relu, float* amax_out, uint8_t* relu_mask, glf_stream_t s);
 /* glf_bn_stats_from_sums + glf_bn_apply in ONE launch (train mode, statistics from a contraction's colstats): every
- * workgroup finishes mean / invstd for all channels in LDS, workgroup 0 writes them to mean / invstd (for the backward pass)
- * and updates running_mean / running_var / num_batches_tracked (all three may be NULL).  Bit-identical to the two calls.
+ * workgroup finishes mean / invstd for the channels of its own column block in LDS, the workgroups of the first row slice
+ * write them to mean / invstd (for the backward pass) and update running_mean / running_var / num_batches_tracked (all
+ * three may be NULL).  Bit-identical to the two calls.
  * C <= 4096.
  * colmax (may be NULL; precision 3 / 4 callers): the per-channel maxima of |x| the same contraction epilogue left
  * (glf_gemm_params.colmax).  With it y is NOT written as fp32 but once, directly, as the packed pre-split image of
@@ -701,7 +702,12 @@ int glf_bn_apply_from_sums(const float* x, int ldx, const float* residual, int l
  * dy2 (may be NULL; row stride lddy2): a second addend of the incoming gradient -- the node sees dy + dy2.  The input of a
  * residual block feeds its shortcut and its first conv (models/resnet.py:59-79), so the gradient that reaches the previous
  * block's last BatchNorm is a sum of two tensors: both passes add them while reading instead of a separate add kernel
- * writing the sum (3 tensor passes) that both passes then read (2 more). */
+ * writing the sum (3 tensor passes) that both passes then read (2 more).
+ * Internal contract of the two-launch form (fused_sums) with BOTH dy2 and dres: the reduction pass stores the masked sum
+ * (dy + dy2) * mask to dres while it holds it in registers, and the apply pass reads dres in place of dy, dy2 and the sign
+ * source (28.25 instead of 32.5 bytes per element; dres and dx are bit-identical to the pass that re-added the pair).  dres is
+ * therefore written while dy, dy2 and x are still being read: it must not alias dy, dy2 or x (refused where the pointers are
+ * equal; overlapping views are the caller's to avoid). */
 int glf_bn_bwd(const float* dy, int lddy, const float* x, int ldx, const float* y, int ldy,
                const float* mean, const float* invstd, const float* gamma, const float* beta /* may be NULL with y */,
                float* dx, int lddx, float* dres, int lddres, float* dgamma, float* dbeta,
