@@ -61,6 +61,8 @@ bool use_f16s4(const GemmArgs& a);
 int launch_rows_f16s4(const GemmArgs& a, dim3 grid, bool gather, int nprod, hipStream_t s);
 int launch_amax(const float* x, long long rows, int cols, long long ld, int vec, float* out, hipStream_t s);
 int launch_split_packed(const float* x, long long rows, int cols, long long ld, const float* amax, float* out, long long ldo, hipStream_t s);   // gemm_f16s.hip
+int launch_split_packed_colsum(const float* x, int rows, int cols, long long ld, const float* amax, float* out, long long ldo,
+                               float* colsum, double* workspace, hipStream_t s);   // gemm_f16s.hip
 float* amax_scratch(int n, hipStream_t s);     // n consecutive device floats from the ring of stream s (glf_api.hip)
 const float* zero_page();                      // ZERO_PAGE_FLOATS zeros on the device (glf_api.hip)
 bool f16s_rows_ok(const GemmArgs& a);

@@ -1442,6 +1442,85 @@ __global__ __launch_bounds__(256) void split_packed_kernel(const float* __restri
     }
 }
 
+
+// split_packed_kernel that ALSO leaves the column sums of x (a bias gradient read off the pass that packs the output gradient).
+// The grid-stride walk above owns no columns, so this one is column-owning like the BatchNorm applies: a workgroup covers `tpr`
+// float4 columns and one slice of rows, a thread keeps its four columns for the whole kernel and walks down its rows with four
+// rows' loads in flight.  Sums: fp32 over at most 64 of the thread's rows, then double; the workgroup's row lanes are folded in a
+// fixed order through LDS into partial[slice][cols]; split_colsum_finalize folds the slices.  No atomics.
+constexpr int SC_FLUSH = 64;
+__global__ __launch_bounds__(256) void split_packed_colsum_kernel(const float* __restrict__ x, int rows, int cols4, long long ld,
+                                                                  const float* __restrict__ amax, float* __restrict__ out, long long ldo,
+                                                                  int tpr, int cblocks, int slices, double* __restrict__ partial) {
+    __shared__ double sh[256 * 4];
+    float sc, inv;
+    pow2_scale(amax, sc, inv);
+    const int rpp = 256 / tpr;
+    const int ct = threadIdx.x % tpr, rl = threadIdx.x / tpr;
+    const int cb = blockIdx.x % cblocks, slice = blockIdx.x / cblocks;
+    const int per = (rows + slices - 1) / slices;
+    const int r0 = slice * per, r1 = min(rows, r0 + per);
+    const int cc = cb * tpr + ct, c0 = cc * 4;
+    const bool live = cc < cols4 && rl < rpp;
+    double d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+    if (live) {
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        int n = 0;
+        auto emit = [&](long long row, const float4 v) __attribute__((always_inline)) {
+            const SplitH sp = split4h(v, sc);
+            const float2 h = __builtin_bit_cast(float2, sp.h), l = __builtin_bit_cast(float2, sp.l);
+            *reinterpret_cast<float4*>(out + row * ldo + c0) = make_float4(h.x, h.y, l.x, l.y);
+            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+        };
+        auto fold = [&]() __attribute__((always_inline)) {
+            d0 += (double)acc.x; d1 += (double)acc.y; d2 += (double)acc.z; d3 += (double)acc.w;
+            acc = make_float4(0.f, 0.f, 0.f, 0.f); n = 0;
+        };
+        int r = r0 + rl;
+        for (; r + 3 * rpp < r1; r += 4 * rpp) {
+            float4 qv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) qv[u] = *reinterpret_cast<const float4*>(x + (long long)(r + u * rpp) * ld + c0);
+            __builtin_amdgcn_sched_barrier(0);       // every load of the four rows is in flight before the first use
+#pragma unroll
+            for (int u = 0; u < 4; ++u) emit(r + u * rpp, qv[u]);
+            n += 4;
+            if (n >= SC_FLUSH) fold();
+        }
+        for (; r < r1; r += rpp) emit(r, *reinterpret_cast<const float4*>(x + (long long)r * ld + c0));      // at most three rows
+        fold();
+    }
+    sh[threadIdx.x * 4 + 0] = d0; sh[threadIdx.x * 4 + 1] = d1; sh[threadIdx.x * 4 + 2] = d2; sh[threadIdx.x * 4 + 3] = d3;
+    __syncthreads();
+    if (rl == 0 && cc < cols4) {
+        for (int k = 1; k < rpp; ++k) {
+            const int o = (k * tpr + ct) * 4;
+            d0 += sh[o]; d1 += sh[o + 1]; d2 += sh[o + 2]; d3 += sh[o + 3];
+        }
+        double* pd = partial + (long long)slice * (cols4 * 4) + c0;
+        pd[0] = d0; pd[1] = d1; pd[2] = d2; pd[3] = d3;
+    }
+}
+
+// colsum[c] = sum over slices of partial[slice][c]: 16 columns x 16 slice lanes per workgroup, every order fixed
+__global__ __launch_bounds__(256) void split_colsum_finalize(const double* __restrict__ partial, int slices, int cols, float* __restrict__ colsum) {
+    __shared__ double sh[256];
+    const int cx = threadIdx.x % 16, lane = threadIdx.x / 16;
+    const int ch = blockIdx.x * 16 + cx;
+    double s = 0, s1 = 0;
+    if (ch < cols) {
+        int i = lane;
+        for (; i + 16 < slices; i += 32) { s += partial[(long long)i * cols + ch]; s1 += partial[(long long)(i + 16) * cols + ch]; }
+        if (i < slices) s += partial[(long long)i * cols + ch];
+        s += s1;
+    }
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    if (lane != 0 || ch >= cols) return;
+    for (int l = 1; l < 16; ++l) s += sh[threadIdx.x + l * 16];
+    colsum[ch] = (float)s;
+}
+
 }  // namespace
 
 namespace glf {
@@ -1452,6 +1531,27 @@ int launch_split_packed(const float* x, long long rows, int cols, long long ld, 
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(split_packed_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, rows, cols / 4, ld, amax, out, ldo);
     return check_launch("split_f16_packed");
+}
+
+// slices of the column-owning split pass: as many workgroups as eight per CU, at most 1024 slices (the partials are
+// slices x cols doubles of the caller's workspace, glf_bn_workspace(rows, cols))
+int launch_split_packed_colsum(const float* x, int rows, int cols, long long ld, const float* amax, float* out, long long ldo,
+                               float* colsum, double* workspace, hipStream_t s) {
+    const int c4 = cols / 4;
+    const int tpr = c4 >= 64 ? 64 : (c4 < 16 ? c4 : 16);
+    const int rpp = 256 / tpr;
+    const int cblocks = (c4 + tpr - 1) / tpr;
+    long long sl = (long long)num_cus() * 8 / cblocks;
+    const int smax = (rows + rpp - 1) / rpp;
+    if (sl > smax) sl = smax;
+    if (sl > 1024) sl = 1024;
+    if (sl < 1) sl = 1;
+    const int slices = (int)sl;
+    hipLaunchKernelGGL(split_packed_colsum_kernel, dim3((unsigned)slices * (unsigned)cblocks), dim3(256), 0, s, x, rows, c4, ld, amax, out, ldo,
+                       tpr, cblocks, slices, workspace);
+    if (int rc = check_launch("split_f16_packed_colsum")) return rc;
+    hipLaunchKernelGGL(split_colsum_finalize, dim3((cols + 15) / 16), dim3(256), 0, s, workspace, slices, cols, colsum);
+    return check_launch("split_colsum_finalize");
 }
 
 int init_gemm_f16s_attrs() {

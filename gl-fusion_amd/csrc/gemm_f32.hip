@@ -900,6 +900,17 @@ extern "C" int glf_split_f16_packed(const float* x, int64_t rows, int cols, int6
     return glf::launch_split_packed(x, rows, cols, ld, amax, out, ldo, glf::S(stream));
 }
 
+extern "C" int glf_split_f16_packed_colsum(const float* x, int rows, int cols, int64_t ld, const float* amax, float* out, int64_t ldo,
+                                           float* colsum, double* workspace, glf_stream_t stream) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(x && amax && out && colsum && workspace, GLF_ERR_NULL, "split_f16_packed_colsum: null argument");
+    GLF_REQUIRE(rows > 0 && cols > 0 && cols % 4 == 0 && ld % 4 == 0 && ldo % 4 == 0 && ld >= cols && ldo >= cols, GLF_ERR_BAD_SHAPE,
+                "split_f16_packed_colsum: cols and the row strides must be multiples of 4");
+    GLF_REQUIRE(aligned16(x) && aligned16(out), GLF_ERR_BAD_SHAPE, "split_f16_packed_colsum: x and out must be 16-byte aligned");
+    GLF_REQUIRE(out != x, GLF_ERR_BAD_SHAPE, "split_f16_packed_colsum: out must not alias x");
+    return glf::launch_split_packed_colsum(x, rows, cols, ld, amax, out, ldo, colsum, workspace, glf::S(stream));
+}
+
 // ----------------------------------------------------------------------------------------------------------
 // Skinny NT: M <= 64 rows (the ASPP pooled branch, deeplabv3.py:123-135: ONE row per frame).  The tile kernels put such a
 // shape on one or two workgroups that walk the whole K alone -- 64 dependent global-memory round trips, 0.2 ms for 34 MFLOP

@@ -5,7 +5,8 @@
 //     partials per channel.  No atomics => bitwise reproducible.
 //   * BatchNorm apply (+residual, +ReLU) and the backward apply are single streaming passes.
 //   * the TPAVI tail z = LayerNorm_C(BN(W_z y) + x) runs one wavefront per row with shuffle
-//     reductions only (no LDS, no barrier).
+//     reductions only (no LDS, no barrier); its backward with every column sum that follows from du is one walk in which a
+//     workgroup owns a slab of rows and each wave a quarter of the channels (bn_res_ln_bwd_sums_kernel).
 #include "stream_common.h"
 #include "split_f16.h"
 
@@ -376,7 +377,7 @@ __global__ __launch_bounds__(256) void bn_stats_finalize(const double* __restric
 }
 
 // out_a[ch] = sum of first partial, out_b[ch] = sum of second (either may be NULL)
-__global__ __launch_bounds__(256) void sum_finalize(const double* __restrict__ partial, int slices, int c, float* out_a, float* out_b) {
+__device__ __forceinline__ void sum_finalize_body(const double* __restrict__ partial, int slices, int c, float* out_a, float* out_b) {
     __shared__ double sh[512];
     const int cx = threadIdx.x % FIN_CH, lane = threadIdx.x / FIN_CH;
     const int ch = blockIdx.x * FIN_CH + cx;
@@ -386,6 +387,9 @@ __global__ __launch_bounds__(256) void sum_finalize(const double* __restrict__ p
     if (out_a) out_a[ch] = (float)s;
     if (out_b) out_b[ch] = (float)q;
 }
+__global__ __launch_bounds__(256) void sum_finalize(const double* __restrict__ partial, int slices, int c, float* out_a, float* out_b) {
+    sum_finalize_body(partial, slices, c, out_a, out_b);
+}
 
 // BatchNorm-backward stage 2 for the packed-dx path: the two sums, and an upper bound of max |dx| over the whole tensor into
 // *bound (a zeroed device float; non-negative floats order like their bit patterns):
@@ -393,10 +397,10 @@ __global__ __launch_bounds__(256) void sum_finalize(const double* __restrict__ p
 //   eval    : |dx| = |gamma invstd| |g|
 // (x 1.0001: the apply kernel rounds its fp32 expression differently; the image's power-of-two scale leaves two bits of
 // fp16 headroom above the bound anyway)
-__global__ __launch_bounds__(256) void bnbwd_finalize(const double* __restrict__ partial, const float* __restrict__ pmax, int slices, int c,
-                                                      const float* __restrict__ gamma, const float* __restrict__ invstd, float inv_n,
-                                                      int training, float* out_a, float* out_b, float* __restrict__ bound,
-                                                      float* __restrict__ keep) {
+__device__ __forceinline__ void bnbwd_finalize_body(const double* __restrict__ partial, const float* __restrict__ pmax, int slices, int c,
+                                                    const float* __restrict__ gamma, const float* __restrict__ invstd, float inv_n,
+                                                    int training, float* out_a, float* out_b, float* __restrict__ bound,
+                                                    float* __restrict__ keep) {
     __shared__ double sh[512];
     __shared__ float shm[512];
     const int cx = threadIdx.x % FIN_CH, lane = threadIdx.x / FIN_CH;
@@ -428,7 +432,23 @@ __global__ __launch_bounds__(256) void bnbwd_finalize(const double* __restrict__
     if (keep) { keep[ch] = (float)s; keep[c + ch] = (float)q; }       // the caller's own copy for a later apply pass (packed_dx = 2)
     const float k = fabsf(gamma[ch] * invstd[ch]);
     const float b = 1.0001f * k * (training ? mg + inv_n * (fabsf((float)s) + mx * fabsf((float)q)) : mg);
-    if (b > 0.f && b < 3.0e38f) atomicMax(reinterpret_cast<unsigned*>(bound), __float_as_uint(b));
+    if (bound && b > 0.f && b < 3.0e38f) atomicMax(reinterpret_cast<unsigned*>(bound), __float_as_uint(b));
+}
+__global__ __launch_bounds__(256) void bnbwd_finalize(const double* __restrict__ partial, const float* __restrict__ pmax, int slices, int c,
+                                                      const float* __restrict__ gamma, const float* __restrict__ invstd, float inv_n,
+                                                      int training, float* out_a, float* out_b, float* __restrict__ bound,
+                                                      float* __restrict__ keep) {
+    bnbwd_finalize_body(partial, pmax, slices, c, gamma, invstd, inv_n, training, out_a, out_b, bound, keep);
+}
+// stage 2 of the fusion-block tail backward (bn_res_ln_bwd_sums_kernel): blockIdx.y = 0 finishes the LayerNorm parameter gradients
+// (sum_finalize's work on the first pair of partials), blockIdx.y = 1 the BatchNorm sums, the kept copy and the bound of the packed
+// dx image (bnbwd_finalize's work on the second pair) -- one launch
+__global__ __launch_bounds__(256) void tail_bwd_finalize(const double* __restrict__ partial, const float* __restrict__ pmax, int slices, int c,
+                                                         const float* __restrict__ gamma, const float* __restrict__ invstd, float inv_n,
+                                                         int training, float* dln_g, float* dln_b, float* dbn_b, float* dbn_g,
+                                                         float* __restrict__ bound, float* __restrict__ keep) {
+    if (blockIdx.y == 0) sum_finalize_body(partial, slices, c, dln_g, dln_b);
+    else bnbwd_finalize_body(partial + (size_t)2 * slices * c, pmax, slices, c, gamma, invstd, inv_n, training, dbn_b, dbn_g, bound, keep);
 }
 
 // running-statistics update of a train-mode BatchNorm replayed from its saved batch statistics (mean, invstd): what a second
@@ -851,6 +871,194 @@ __global__ __launch_bounds__(256) void bn_res_ln_kernel(const float* __restrict_
     }
 }
 
+// ---- TPAVI tail backward in ONE walk: du and the six column reductions that follow from it ------------------------------------
+// bn_res_ln_kernel<true> (du), colreduce_kernel<OpLnParam> (the LayerNorm parameter gradients) and the BatchNorm-backward
+// reduction over du each walked dz / w / x or du; here the tensors are read once.  A wavefront that owns a whole row has no
+// registers left for column accumulators over its 32 channels per lane, so a WORKGROUP owns the rows of its slice, TA_R at a
+// time, and each of its four waves a quarter of the channels for all of them: the float4 columns lane + 64 v, v = 2 q and
+// 2 q + 1 -- the columns the row-owning lane `lane` visits at steps 2 q and 2 q + 1 of its loop.  Per lane: 8 channels with
+// their coefficients in registers for the whole kernel and 4 x 8 fp32 accumulators (the sums and maxima over du, max |what|).
+//   du is bit-identical to bn_res_ln_kernel<true>'s: the per-row sums s1 / s2 are rebuilt in that kernel's order.  Every wave
+//   leaves its per-lane terms of a row in LDS (wave 0 the sum of its two, which is how the row-owning lane's chain starts); after
+//   the barrier every wave adds the seven values per lane in the order v = 0 .. 7 and folds the lanes with the same butterfly.
+//   (A column beyond C contributes +0.f, which leaves a chain that starts at +0.f unchanged bit for bit.)
+//   The roundings are spelled out, because -ffp-contract=fast lets the compiler choose them per context and the two kernels are
+//   different contexts: bn_res_ln_kernel<true> as compiled rounds d ln_g and the products gz uhat before adding them (its s1 / s2
+//   pair is evaluated with packed adds), except at column step v = 1, where s2 gets fma(gz.x, uhat.x, gz.y uhat.y) +
+//   fma(gz.z, uhat.z, gz.w uhat.w); u is fma((w - mean) invstd, gamma, beta) + x and du is rstd fma(-m2, uhat, gz - m1).
+//   rounded() keeps a product out of a contraction.  tests/test_gpu_tail_bwd_fused.py compares du bit for bit at every width.
+//   Accumulation: doubles in thread-private LDS cells (no atomics, no barrier; 32 doubles per thread do not fit beside the row
+//   data in registers at two waves per SIMD).  The LayerNorm sums are added there element by element, like the pass they
+//   replace; the sums over du in fp32 over at most TA_FLUSH rows first, like the BatchNorm reduction they replace.  One set of partials per
+//   workgroup in the two-stage layout, partial[stat][slice][c]: stat 0 = sum dz uhat, 1 = sum dz, 2 = sum du, 3 = sum du what;
+//   pmax[0][slice][c] = max |du|, pmax[1][slice][c] = max |what| (what = (w - mean) invstd).  Fixed order everywhere.
+// LDS: 14 KB of row terms + 64 KB of doubles = 78 KB, two workgroups per CU; the grid is at most that many workgroups.
+__device__ __forceinline__ float rounded(float p) { asm volatile("" : "+v"(p)); return p; }
+constexpr int TA_R = 3;            // rows of a slice in flight (every load of the TA_R rows is issued before the first use)
+constexpr int TA_FLUSH = 15;       // rows of du summed in fp32 before the fold into doubles
+constexpr int TA_MAX_SLICES = 512;
+
+inline int tail_slices(int rows) {
+    int s = (rows + 4 * TA_R - 1) / (4 * TA_R);
+    int cap = 2 * num_cus();
+    if (cap > TA_MAX_SLICES) cap = TA_MAX_SLICES;
+    return s < 1 ? 1 : (s > cap ? cap : s);
+}
+
+__global__ __launch_bounds__(256, 2) void bn_res_ln_bwd_sums_kernel(const float* __restrict__ dz, const float* __restrict__ w,
+                                                                    const float* __restrict__ x, Coef bn, const float* __restrict__ ln_g,
+                                                                    const float* __restrict__ row_mean, const float* __restrict__ row_rstd,
+                                                                    float* __restrict__ du, int rows, int c, int slices,
+                                                                    double* __restrict__ partial, float* __restrict__ pmax) {
+    __shared__ float sT[TA_R][2][7][64];          // [row][s1 | s2][chain slot][lane]
+    __shared__ double sD[32][256];                // [stat * 8 + column j * 4 + component][thread]
+    const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
+    const int c4 = c >> 2;
+    const int slice = blockIdx.x;
+    const int per = (rows + slices - 1) / slices;
+    const int r0 = slice * per, r1 = min(rows, r0 + per);
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    int ch[2]; bool lv[2];
+    float4 mu[2], is[2], ga[2], be[2], lg[2];
+    float4 sa[2], sb[2], mg[2], mx[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int cc = lane + 64 * (2 * q + j);
+        lv[j] = cc < c4; ch[j] = cc * 4;
+        mu[j] = is[j] = ga[j] = be[j] = lg[j] = zero4;
+        if (lv[j]) {
+            mu[j] = *reinterpret_cast<const float4*>(bn.mean + ch[j]);
+            is[j] = *reinterpret_cast<const float4*>(bn.invstd + ch[j]);
+            ga[j] = *reinterpret_cast<const float4*>(bn.gamma + ch[j]);
+            be[j] = *reinterpret_cast<const float4*>(bn.beta + ch[j]);
+            lg[j] = *reinterpret_cast<const float4*>(ln_g + ch[j]);
+        }
+        sa[j] = sb[j] = mg[j] = mx[j] = zero4;
+    }
+#pragma unroll
+    for (int k = 0; k < 32; ++k) sD[k][tid] = 0.0;
+    auto flush = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const float4 v[2] = {sa[j], sb[j]};
+#pragma unroll
+            for (int st = 0; st < 2; ++st) {
+                sD[16 + st * 8 + j * 4 + 0][tid] += (double)v[st].x; sD[16 + st * 8 + j * 4 + 1][tid] += (double)v[st].y;
+                sD[16 + st * 8 + j * 4 + 2][tid] += (double)v[st].z; sD[16 + st * 8 + j * 4 + 3][tid] += (double)v[st].w;
+            }
+            sa[j] = sb[j] = zero4;
+        }
+    };
+    int pending = 0;
+    for (int rb = r0; rb < r1; rb += TA_R) {
+        // gz = dz ln_g, uh = uhat and wh = what of the TA_R rows replace the loaded dz, x and w in place
+        float4 gz[TA_R][2], uh[TA_R][2], wh[TA_R][2];
+        float rm[TA_R], rs[TA_R];
+#pragma unroll
+        for (int u = 0; u < TA_R; ++u) {
+            const int row = rb + u;
+            const bool ok = row < r1;
+            const long long base = (long long)row * c;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                gz[u][j] = uh[u][j] = wh[u][j] = zero4;
+                if (ok && lv[j]) {
+                    gz[u][j] = *reinterpret_cast<const float4*>(dz + base + ch[j]);
+                    wh[u][j] = *reinterpret_cast<const float4*>(w + base + ch[j]);
+                    uh[u][j] = *reinterpret_cast<const float4*>(x + base + ch[j]);
+                }
+            }
+            rm[u] = ok ? row_mean[row] : 0.f;
+            rs[u] = ok ? row_rstd[row] : 0.f;
+        }
+        __builtin_amdgcn_sched_barrier(0);       // every load of the TA_R rows is in flight before the first use
+#pragma unroll
+        for (int u = 0; u < TA_R; ++u) {
+            const bool ok = rb + u < r1;
+            const float mean = rm[u], rstd = rs[u];
+            float t1[2], t2[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const float4 d = gz[u][j], ww = wh[u][j], xx = uh[u][j];
+                const float4 wn = make_float4((ww.x - mu[j].x) * is[j].x, (ww.y - mu[j].y) * is[j].y, (ww.z - mu[j].z) * is[j].z, (ww.w - mu[j].w) * is[j].w);
+                float4 uu = make_float4(__builtin_fmaf(wn.x, ga[j].x, be[j].x) + xx.x, __builtin_fmaf(wn.y, ga[j].y, be[j].y) + xx.y,
+                                        __builtin_fmaf(wn.z, ga[j].z, be[j].z) + xx.z, __builtin_fmaf(wn.w, ga[j].w, be[j].w) + xx.w);
+                uu = make_float4((uu.x - mean) * rstd, (uu.y - mean) * rstd, (uu.z - mean) * rstd, (uu.w - mean) * rstd);
+                const float4 g = make_float4(rounded(d.x * lg[j].x), rounded(d.y * lg[j].y), rounded(d.z * lg[j].z), rounded(d.w * lg[j].w));
+                const float4 pr = make_float4(rounded(g.x * uu.x), rounded(g.y * uu.y), rounded(g.z * uu.z), rounded(g.w * uu.w));
+                t1[j] = (g.x + g.y) + (g.z + g.w);
+                // column step v = 1 of the row-owning kernel (wave 0, j = 1) is the one whose s2 term was compiled with fused products
+                t2[j] = (j == 1 && q == 0) ? __builtin_fmaf(g.x, uu.x, pr.y) + __builtin_fmaf(g.z, uu.z, pr.w) : (pr.x + pr.y) + (pr.z + pr.w);
+                // the LayerNorm parameter sums go to their doubles element by element, as colreduce_kernel<OpLnParam> adds them
+                // (a row or column that does not exist holds d = 0)
+                sD[j * 4 + 0][tid] += (double)(d.x * uu.x); sD[j * 4 + 1][tid] += (double)(d.y * uu.y);
+                sD[j * 4 + 2][tid] += (double)(d.z * uu.z); sD[j * 4 + 3][tid] += (double)(d.w * uu.w);
+                sD[8 + j * 4 + 0][tid] += (double)d.x; sD[8 + j * 4 + 1][tid] += (double)d.y;
+                sD[8 + j * 4 + 2][tid] += (double)d.z; sD[8 + j * 4 + 3][tid] += (double)d.w;
+                if (ok && lv[j]) {
+                    mx[j].x = fmaxf(mx[j].x, fabsf(wn.x)); mx[j].y = fmaxf(mx[j].y, fabsf(wn.y));
+                    mx[j].z = fmaxf(mx[j].z, fabsf(wn.z)); mx[j].w = fmaxf(mx[j].w, fabsf(wn.w));
+                }
+                gz[u][j] = g; uh[u][j] = uu; wh[u][j] = wn;
+            }
+            if (q == 0) {
+                float p1 = 0.f, p2 = 0.f;
+                if (lv[0]) { p1 += t1[0]; p2 += t2[0]; }
+                if (lv[1]) { p1 += t1[1]; p2 += t2[1]; }
+                sT[u][0][0][lane] = p1; sT[u][1][0][lane] = p2;
+            } else {
+                sT[u][0][2 * q - 1][lane] = lv[0] ? t1[0] : 0.f; sT[u][1][2 * q - 1][lane] = lv[0] ? t2[0] : 0.f;
+                sT[u][0][2 * q][lane] = lv[1] ? t1[1] : 0.f;     sT[u][1][2 * q][lane] = lv[1] ? t2[1] : 0.f;
+            }
+        }
+        __syncthreads();
+        float m1[TA_R], m2[TA_R];
+#pragma unroll
+        for (int u = 0; u < TA_R; ++u) {
+            float s1 = sT[u][0][0][lane], s2 = sT[u][1][0][lane];
+#pragma unroll
+            for (int k = 1; k < 7; ++k) { s1 += sT[u][0][k][lane]; s2 += sT[u][1][k][lane]; }
+            m1[u] = wave_sum(s1) / c; m2[u] = wave_sum(s2) / c;
+        }
+        __syncthreads();                         // the row terms are free for the next TA_R rows
+#pragma unroll
+        for (int u = 0; u < TA_R; ++u) {
+            const int row = rb + u;
+            if (row < r1) {
+                const float rstd = rs[u];
+                const long long base = (long long)row * c;
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    if (lv[j]) {
+                        const float4 g = gz[u][j], uu = uh[u][j], wn = wh[u][j];
+                        const float4 o = make_float4(rstd * __builtin_fmaf(-m2[u], uu.x, g.x - m1[u]), rstd * __builtin_fmaf(-m2[u], uu.y, g.y - m1[u]),
+                                                     rstd * __builtin_fmaf(-m2[u], uu.z, g.z - m1[u]), rstd * __builtin_fmaf(-m2[u], uu.w, g.w - m1[u]));
+                        *reinterpret_cast<float4*>(du + base + ch[j]) = o;
+                        sa[j].x += o.x; sa[j].y += o.y; sa[j].z += o.z; sa[j].w += o.w;
+                        sb[j].x += o.x * wn.x; sb[j].y += o.y * wn.y; sb[j].z += o.z * wn.z; sb[j].w += o.w * wn.w;
+                        mg[j].x = fmaxf(mg[j].x, fabsf(o.x)); mg[j].y = fmaxf(mg[j].y, fabsf(o.y));
+                        mg[j].z = fmaxf(mg[j].z, fabsf(o.z)); mg[j].w = fmaxf(mg[j].w, fabsf(o.w));
+                    }
+            }
+        }
+        pending += TA_R;
+        if (pending + TA_R > TA_FLUSH) { flush(); pending = 0; }
+    }
+    flush();
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+        if (lv[j]) {
+#pragma unroll
+            for (int st = 0; st < 4; ++st) {
+                double* pd = partial + ((long long)st * slices + slice) * c + ch[j];
+                pd[0] = sD[st * 8 + j * 4 + 0][tid]; pd[1] = sD[st * 8 + j * 4 + 1][tid];
+                pd[2] = sD[st * 8 + j * 4 + 2][tid]; pd[3] = sD[st * 8 + j * 4 + 3][tid];
+            }
+            *reinterpret_cast<float4*>(pmax + (long long)slice * c + ch[j]) = mg[j];
+            *reinterpret_cast<float4*>(pmax + (long long)(slices + slice) * c + ch[j]) = mx[j];
+        }
+}
+
 template <class Op>
 int launch_colreduce(Op op, int rows, int c, double* ws, hipStream_t s) {
     const int slices = n_slices_c(rows, c);
@@ -956,7 +1164,7 @@ extern "C" int glf_bn_bwd(const float* dy, int lddy, const float* x, int ldx, co
     if (int rc = glf::ensure_init()) return rc;
     GLF_REQUIRE(dy && x && mean && invstd && gamma && dx && (workspace || fused_sums), GLF_ERR_NULL, "bn_bwd: null argument");
     if (relu_mask) y = nullptr;
-    GLF_REQUIRE(!packed_dx || amax_out, GLF_ERR_NULL, "bn_bwd: packed_dx needs amax_out (a zeroed device float that receives the bound the image is scaled with)");
+    GLF_REQUIRE(!packed_dx || packed_dx == 4 || amax_out, GLF_ERR_NULL, "bn_bwd: packed_dx needs amax_out (a zeroed device float that receives the bound the image is scaled with)");
     GLF_REQUIRE(!relu || y || beta || relu_mask, GLF_ERR_NULL, "bn_bwd: relu != 0 needs relu_mask, y (the forward output) or beta (to recompute its sign from x)");
     GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "bn_bwd: rows must be > 0");
     REQ_C4(c); REQ_AL(dy, "dy"); REQ_AL(x, "x"); REQ_AL(dx, "dx"); REQ_LD(lddy, "lddy"); REQ_LD(ldx, "ldx"); REQ_LD(lddx, "lddx");
@@ -967,15 +1175,17 @@ extern "C" int glf_bn_bwd(const float* dy, int lddy, const float* x, int ldx, co
     const ColGrid ag = col_grid(rows, c);
     BwdApply ap{dy, lddy, x, ldx, y, ldy, Coef{mean, invstd, gamma, beta}, nullptr, nullptr, dx, lddx, dres, lddres,
                 rows, c, ag.tpr, ag.cblocks, ag.slices, training, 1.0f / (float)rows,
-                amax_out, packed_dx, relu_mask, dy2, lddy2, nullptr, nullptr, nullptr, nullptr};
+                amax_out, packed_dx == 4 ? 0 : packed_dx, relu_mask, dy2, lddy2, nullptr, nullptr, nullptr, nullptr};
     // packed_dx = 2 / 3: the two halves of the packed three-launch form for SEVERAL layers whose images share one scale (column
     // slices of one buffer): 2 = reduction + finalize only (dgamma / dbeta final, the bound raised into *amax_out by atomic max),
     // 3 = the apply pass only, scaled by *amax_out -- the caller runs every layer's half 2 before the first half 3.  Half 3 reads
     // the sums from `fused_sums` (here 2 c floats the CALLER owns, written by half 2), never from dgamma / dbeta: those are handed
-    // on after half 2 and may be summed over ranks or accumulated into before half 3 runs
+    // on after half 2 and may be summed over ranks or accumulated into before half 3 runs.  4 = half 3 with dx written as plain
+    // fp32 (max |dx| raised into *amax_out when given): the apply behind a reduction that left its sums in fused_sums the same way
+    // (glf_bn_res_ln_bwd_sums)
     const int phase = packed_dx >= 2 ? packed_dx : 0;
-    GLF_REQUIRE(packed_dx >= 0 && packed_dx <= 3, GLF_ERR_BAD_SHAPE, "bn_bwd: packed_dx must be 0 .. 3");
-    GLF_REQUIRE(!phase || (workspace && fused_sums), GLF_ERR_NULL, "bn_bwd: packed_dx = 2 / 3 needs the workspace and fused_sums (2 c floats kept from half 2 to half 3)");
+    GLF_REQUIRE(packed_dx >= 0 && packed_dx <= 4, GLF_ERR_BAD_SHAPE, "bn_bwd: packed_dx must be 0 .. 4");
+    GLF_REQUIRE(!phase || (workspace && fused_sums), GLF_ERR_NULL, "bn_bwd: packed_dx = 2 / 3 / 4 needs the workspace and fused_sums (2 c floats kept from half 2 to half 3)");
     GLF_REQUIRE(phase != 2 || (dgamma && dbeta), GLF_ERR_NULL, "bn_bwd: packed_dx = 2 needs dgamma and dbeta");
     float* keep = phase ? reinterpret_cast<float*>(fused_sums) : (float*)nullptr;
     if (!phase && fused_sums && c <= APPLY_MAX_C) {
@@ -1010,7 +1220,7 @@ extern "C" int glf_bn_bwd(const float* dy, int lddy, const float* x, int ldx, co
     float* sums = reinterpret_cast<float*>(workspace + (size_t)2 * slices * c);
     float* s_dy = dbeta ? dbeta : sums;
     float* s_dyx = dgamma ? dgamma : sums + c;
-    if (phase == 3) {
+    if (phase >= 3) {
         s_dy = keep; s_dyx = keep + c;      // the sums are where half 2 kept them, the bound in *amax_out
     } else if (packed_dx) {
         float* pmax = reinterpret_cast<float*>(workspace + (size_t)2 * slices * c + (size_t)2 * c);
@@ -1074,4 +1284,28 @@ extern "C" int glf_bn_res_ln_bwd(const float* dz, const float* w, const float* x
     if (int rc = launch_colreduce(OpLnParam{dz, w, x, bn, row_mean, row_rstd, c}, rows, c, workspace, glf::S(s))) return rc;
     hipLaunchKernelGGL(sum_finalize, dim3((c + FIN_CH - 1) / FIN_CH), dim3(256), 0, glf::S(s), workspace, n_slices_c(rows, c), c, dln_gamma, dln_beta);
     return glf::check_launch("ln_param_finalize");
+}
+
+extern "C" int glf_bn_res_ln_bwd_sums(const float* dz, const float* w, const float* x, const float* bn_mean,
+                                      const float* bn_invstd, const float* bn_gamma, const float* bn_beta,
+                                      const float* ln_gamma, const float* row_mean, const float* row_rstd,
+                                      float* du, float* dln_gamma, float* dln_beta, float* dbn_gamma, float* dbn_beta,
+                                      float* bn_sums, float* amax_out, int rows, int c, int training,
+                                      double* workspace, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(dz && w && x && bn_mean && bn_invstd && bn_gamma && bn_beta && ln_gamma && row_mean && row_rstd && du &&
+                dln_gamma && dln_beta && dbn_gamma && dbn_beta && bn_sums && workspace, GLF_ERR_NULL, "bn_res_ln_bwd_sums: null argument");
+    GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "bn_res_ln_bwd_sums: rows must be > 0");
+    REQ_C4(c); GLF_REQUIRE(c <= 64 * 4 * LN_NV, GLF_ERR_UNSUPPORTED, "bn_res_ln: C must be <= %d", 64 * 4 * LN_NV);
+    REQ_AL(dz, "dz"); REQ_AL(w, "w"); REQ_AL(x, "x"); REQ_AL(du, "du");
+    // du is written TA_R rows at a time while later rows of the inputs are still to be read, by other workgroups too
+    GLF_REQUIRE(du != dz && du != w && du != x, GLF_ERR_BAD_SHAPE, "bn_res_ln_bwd_sums: du must not alias dz, w or x");
+    const int slices = tail_slices(rows);
+    float* pmax = reinterpret_cast<float*>(workspace + (size_t)4 * slices * c);      // 4 S c doubles + 2 S c floats <= glf_bn_workspace
+    hipLaunchKernelGGL(bn_res_ln_bwd_sums_kernel, dim3(slices), dim3(256), 0, glf::S(s), dz, w, x, Coef{bn_mean, bn_invstd, bn_gamma, bn_beta},
+                       ln_gamma, row_mean, row_rstd, du, rows, c, slices, workspace, pmax);
+    if (int rc = glf::check_launch("bn_res_ln_bwd_sums")) return rc;
+    hipLaunchKernelGGL(tail_bwd_finalize, dim3((c + FIN_CH - 1) / FIN_CH, 2), dim3(256), 0, glf::S(s), workspace, pmax, slices, c, bn_gamma,
+                       bn_invstd, 1.0f / (float)rows, training, dln_gamma, dln_beta, dbn_beta, dbn_gamma, amax_out, bn_sums);
+    return glf::check_launch("tail_bwd_finalize");
 }

@@ -34,7 +34,8 @@ from torch.autograd.function import once_differentiable
 
 from ._lib import AttnPairParams, AttnParams, check, lib
 from .ops import (_chk, _contig, _p, _stream, _tn_split, _ws, _wimage, _registry, WJ_COPY, stats_slot, bnbwd_slot, amax_of, amax_slot, colsum, gemm, set_amax, split_mode,
-                  transpose2d, weight_T, weight_packed, nt_presplit_ok, tn_presplit_ok, act_packed, packed_hit, pick, zeros, _ones4)
+                  transpose2d, weight_T, weight_packed, nt_presplit_ok, tn_presplit_ok, act_packed, act_packed_colsum, packed_hit, pick, zeros,
+                  _ones4)
 
 
 FUSED_SOFTMAX = os.environ.get("GLF_FUSED_SOFTMAX", "1") != "0"
@@ -46,6 +47,10 @@ FUSED_SOFTMAX = os.environ.get("GLF_FUSED_SOFTMAX", "1") != "0"
 # 256-deep chains were within 1e-3 in every regime measured (5.6e-4 / 9.5e-4), for +14 % on the strict-precision leg
 # (profiles/r04_exact_leg_spread.txt -- measurable since the leg is reproducible, see ops.Conv2dFn.forward).
 EXACT_KCHUNK = int(os.environ.get("GLF_EXACT_KCHUNK", "256"))
+# The tail's backward in one walk: du, the LayerNorm parameter gradients and the BatchNorm-backward sums of w from ONE pass over
+# dz / w / x (glf_bn_res_ln_bwd_sums) instead of three, and the stacked projection's bias gradient from the pass that packs dqkv
+# (glf_split_f16_packed_colsum) instead of a second one.  0 = the separate passes (A/B, profiles/tail_bwd_fused.txt).
+TAIL_BWD_FUSED = os.environ.get("GLF_TAIL_BWD_FUSED", "1") != "0"
 _gemm = gemm
 
 
@@ -473,11 +478,15 @@ def _project_bwd(G, x, dqkv, Wcat, du, x_packed):
     dWcat = torch.empty(c3, c, **G.f32)
     am_dq = amax_of(dqkv)
     ok = tn_presplit_ok(c3, c, c3, c)
+    dbcat = None
+    if ok and TAIL_BWD_FUSED and rows < (1 << 31) // c3:
+        _, dbcat = act_packed_colsum(dqkv, am_dq, rows, c3)          # the image is found again by act_packed
     dq_a, pa = pick(dqkv, act_packed(dqkv, am_dq, True) if ok else None, ok)
     am_x = x_packed[1] if x_packed is not None else amax_of(x)
     xb, pb = pick(x, x_packed[0] if x_packed is not None else None, ok)
     gemm("tn", dq_a, xb, dWcat, M=c3, N=c, K=rows, lda=c3, ldb=c, ldc=c, split=sp, amax_a=am_dq, amax_b=am_x, a_packed=pa, b_packed=pb)
-    dbcat = colsum(dqkv, rows, c3)
+    if dbcat is None:
+        dbcat = colsum(dqkv, rows, c3)
     if _split_dgrad(G):
         WcatT = weight_T(Wcat, Wcat)                        # cached with the stacked operand (one rebuild per weight update)
         am_wc = amax_of(Wcat)
@@ -535,8 +544,6 @@ def _tail_bwd(G, dz, x, y, wz, mean, invstd, rmu, rrs, zW, wz_o, bn_g, bn_b, ln_
     du = torch.empty(rows, c, **G.f32)
     dln_g = torch.empty(c, **G.f32)
     dln_b = torch.empty(c, **G.f32)
-    check(lib.glf_bn_res_ln_bwd(_p(dz), _p(wz), _p(x), _p(mean), _p(invstd), _p(bn_g), _p(bn_b), _p(ln_g), _p(rmu), _p(rrs),
-                                _p(du), _p(dln_g), _p(dln_b), rows, c, _p(_ws(rows, c, dev)), _stream()), "bn_res_ln_bwd")
     # BatchNorm3d backward on w.  Its result dwz has three readers: the weight gradient and the dgrad of W_z -- contractions --
     # and W_z's bias gradient, the column sum of dwz.  In train mode that sum is ZERO in exact arithmetic (the bias feeds a
     # BatchNorm: sum_r dwz = -gamma invstd (sum_r xhat) sum(g xhat) / n and sum_r xhat = 0); what fp32 kernels -- the
@@ -548,10 +555,24 @@ def _tail_bwd(G, dz, x, y, wz, mean, invstd, rmu, rrs, zW, wz_o, bn_g, bn_b, ln_
     dbn_g = torch.empty(c, **G.f32)
     dbn_b = torch.empty(c, **G.f32)
     dwz_pk = bool(training and split and am_dwz_slot is not None and nt_presplit_ok(c, c, c) and tn_presplit_ok(c, ci, c, ci))
-    fused = bnbwd_slot(c, dev) if c <= 4096 else None
-    check(lib.glf_bn_bwd(_p(du), c, _p(wz), c, None, c, _p(mean), _p(invstd), _p(bn_g), None, _p(dwz), c, None, c,
-                         _p(dbn_g), _p(dbn_b), rows, c, 0, int(training), None if fused is not None else _p(_ws(rows, c, dev)), _p(am_dwz_slot),
-                         int(dwz_pk), None, None, 0, _p(fused), _stream()), "bn_bwd")
+    if TAIL_BWD_FUSED:
+        # one walk over dz / w / x: du, the LayerNorm parameter gradients, the BatchNorm sums (kept in `keep` for the apply half) and,
+        # for the packed image, its bound -- then the apply half alone (packed_dx 3: the packed image, 4: plain fp32)
+        keep = torch.empty(2 * c, **G.f32)
+        ws = _ws(rows, c, dev)
+        check(lib.glf_bn_res_ln_bwd_sums(_p(dz), _p(wz), _p(x), _p(mean), _p(invstd), _p(bn_g), _p(bn_b), _p(ln_g), _p(rmu), _p(rrs),
+                                         _p(du), _p(dln_g), _p(dln_b), _p(dbn_g), _p(dbn_b), _p(keep), _p(am_dwz_slot) if dwz_pk else None,
+                                         rows, c, int(training), _p(ws), _stream()), "bn_res_ln_bwd_sums")
+        check(lib.glf_bn_bwd(_p(du), c, _p(wz), c, None, c, _p(mean), _p(invstd), _p(bn_g), None, _p(dwz), c, None, c,
+                             None, None, rows, c, 0, int(training), _p(ws), _p(am_dwz_slot), 3 if dwz_pk else 4, None, None, 0, _p(keep),
+                             _stream()), "bn_bwd")
+    else:
+        check(lib.glf_bn_res_ln_bwd(_p(dz), _p(wz), _p(x), _p(mean), _p(invstd), _p(bn_g), _p(bn_b), _p(ln_g), _p(rmu), _p(rrs),
+                                    _p(du), _p(dln_g), _p(dln_b), rows, c, _p(_ws(rows, c, dev)), _stream()), "bn_res_ln_bwd")
+        fused = bnbwd_slot(c, dev) if c <= 4096 else None
+        check(lib.glf_bn_bwd(_p(du), c, _p(wz), c, None, c, _p(mean), _p(invstd), _p(bn_g), None, _p(dwz), c, None, c,
+                             _p(dbn_g), _p(dbn_b), rows, c, 0, int(training), None if fused is not None else _p(_ws(rows, c, dev)), _p(am_dwz_slot),
+                             int(dwz_pk), None, None, 0, _p(fused), _stream()), "bn_bwd")
     set_amax(dwz, am_dwz_slot)
     # W_z: w = y zW^T + b
     sp = _tn_split(rows, c, ci, 1)

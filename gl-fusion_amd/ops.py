@@ -825,6 +825,23 @@ def act_packed(t: torch.Tensor, amax: Optional[torch.Tensor], retain: Optional[b
     return pk
 
 
+def act_packed_colsum(t: torch.Tensor, amax: Optional[torch.Tensor], rows: int, cols: int):
+    """act_packed(t, amax, True) for a gradient [rows, cols] whose column sums are wanted too (a bias gradient): ONE pass writes the
+    image and the sums (glf_split_f16_packed_colsum).  -> (image, sums); (None, None) where no image is made here -- not
+    applicable, or one exists already -- and the caller takes act_packed / colsum."""
+    if not presplit_ok(t, amax) or packed_hit(t, amax) is not None:
+        return None, None
+    pk = torch.empty_like(t)
+    db = torch.empty(cols, dtype=torch.float32, device=t.device)
+    check(lib.glf_split_f16_packed_colsum(_p(t), rows, cols, cols, _p(amax), _p(pk), cols, _p(db), _p(_ws(rows, cols, t.device)), _stream()),
+          "split_f16_packed_colsum")
+    try:
+        t._glf_packed = (t._version, t.data_ptr(), amax, pk, torch.cuda.current_stream() if STREAMS else None)
+    except AttributeError:
+        pass
+    return pk, db
+
+
 def nt_presplit_ok(K: int, lda: int, ldb: int) -> bool:
     """Mirror of the library's eligibility test for the aligned split-fp16 NT kernel (gemm_f16s.hip f16s_rows_ok)."""
     return _PREC[0] >= 2 and K % 32 == 0 and 32 <= K <= (1 << 18) and lda % 4 == 0 and ldb % 4 == 0

@@ -196,6 +196,12 @@ int glf_amax(const float* x, int64_t rows, int cols, int64_t ld, float* out, glf
  * kernels derive from *amax (a device float >= max|x|).  For glf_gemm_params.a_presplit / b_presplit. */
 int glf_split_f16_packed(const float* x, int64_t rows, int cols, int64_t ld, const float* amax, float* out, int64_t ldo,
                          glf_stream_t stream);
+/* glf_split_f16_packed that ALSO writes colsum[cols] = sum_r x[r][c] -- the bias gradient of a layer whose output gradient is
+ * packed for its contractions anyway, read off the same pass instead of a second one over the tensor.  The image is
+ * bit-identical to glf_split_f16_packed's.  The sums go through fixed-order two-stage partials (fp32 over at most 64 rows, then
+ * double; no atomics: equal inputs give equal bits).  workspace: glf_bn_workspace(rows, cols) doubles.  out must not be x. */
+int glf_split_f16_packed_colsum(const float* x, int rows, int cols, int64_t ld, const float* amax, float* out, int64_t ldo,
+                                float* colsum, double* workspace, glf_stream_t stream);
 
 /* A[m][k] (k contiguous, rows gathered per `gather`), B_tap[n][k] (k contiguous: torch's
  * [Cout][Cin] weight layout per tap), C[m][n].  Replaces F.conv2d / nn.Conv3d(1x1x1) forward:
@@ -699,6 +705,7 @@ int glf_bn_apply_from_sums(const float* x, int ldx, const float* residual, int l
  * with the same amax_out before the first half 3.  In both halves fused_sums is required and means something else: 2 c floats
  * (no zero fill) that the caller keeps per layer from half 2, which stores the channel sums there as well, to half 3, which
  * reads them there and never touches dgamma / dbeta (which it takes as NULL) -- those may be reduced over ranks or accumulated into in between.
+ * packed_dx = 4 is half 3 with dx written as plain fp32 (amax_out may be NULL; non-NULL it receives max|dx| as with packed_dx = 0).
  * dy2 (may be NULL; row stride lddy2): a second addend of the incoming gradient -- the node sees dy + dy2.  The input of a
  * residual block feeds its shortcut and its first conv (models/resnet.py:59-79), so the gradient that reaches the previous
  * block's last BatchNorm is a sum of two tensors: both passes add them while reading instead of a separate add kernel
@@ -790,6 +797,20 @@ int glf_bn_res_ln_bwd(const float* dz, const float* w, const float* x, const flo
                       const float* ln_gamma, const float* row_mean, const float* row_rstd,
                       float* du, float* dln_gamma, float* dln_beta, int rows, int c,
                       double* workspace, glf_stream_t s);
+/* glf_bn_res_ln_bwd and the reduction half of the BatchNorm backward that follows it (glf_bn_bwd on dy = du, x = w, no ReLU)
+ * in ONE walk over dz, w and x: du (bit-identical to glf_bn_res_ln_bwd's), dln_gamma / dln_beta, and from du while it is in
+ * registers dbn_beta = sum_r du, dbn_gamma = sum_r du what (what = (w - mean) invstd), both also kept as floats in bn_sums
+ * [2 c] for the apply half, and -- amax_out non-NULL: a zeroed device float -- the upper bound of max |dx| of that BatchNorm
+ * backward (training as in glf_bn_bwd) raised into *amax_out, as glf_bn_bwd's packed_dx = 2 does.  Finish with
+ * glf_bn_bwd(du, ..., packed_dx = 3 (packed dx, same amax_out) or 4 (fp32 dx), fused_sums = bn_sums).
+ * Two launches (the walk, one finalize); fixed-order sums, no atomics on them: equal inputs give equal bits.
+ * C <= 2048 as glf_bn_res_ln_bwd; du must not alias dz, w or x.  workspace: glf_bn_workspace(rows, c) doubles. */
+int glf_bn_res_ln_bwd_sums(const float* dz, const float* w, const float* x, const float* bn_mean,
+                           const float* bn_invstd, const float* bn_gamma, const float* bn_beta,
+                           const float* ln_gamma, const float* row_mean, const float* row_rstd,
+                           float* du, float* dln_gamma, float* dln_beta, float* dbn_gamma, float* dbn_beta,
+                           float* bn_sums, float* amax_out /* may be NULL */, int rows, int c, int training,
+                           double* workspace, glf_stream_t s);
 /* Row softmax in place over `cols` (TPAVI 'embedded' mode, ours.py:896-897) and its backward
  * ds = p * (dp - sum(dp*p)). */
 int glf_softmax_rows(float* x, int64_t rows, int cols, glf_stream_t s);
