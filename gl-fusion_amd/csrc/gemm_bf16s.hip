@@ -14,7 +14,7 @@
 //     transposed on the fly by ds_read_b64_tr_b16 (two per fragment), conflict-free for that stride.
 // Same gather / tap_mask / rect semantics, epilogues and XCD-aware tile order as gemm_f32.hip.  Only the aligned
 // fast path is built (K % 32 == 0, 16-byte aligned rows); everything else stays on the exact-fp32 kernels.
-#include "gemm_common.h"
+#include "gemm_rows_walk.h"
 
 namespace {
 
@@ -520,16 +520,7 @@ bool bf16s_tn_ok(const GemmArgs& a) {
 // 256-row tiles: the grid is re-derived for BM8; rect mode sums its tiles per tap as setup_rect does
 int launch_rows_bf16s8(const GemmArgs& a0, bool gather, int batch, hipStream_t s) {
     GemmArgs a = a0;
-    long long tiles_m = (a.M + BM8 - 1) / BM8;
-    if (a.rect) {
-        tiles_m = 0;
-        for (unsigned mm = a.tap_mask; mm; mm &= mm - 1) {
-            const int t = __builtin_ctz(mm);
-            int y0, y1, x0, x1;
-            tap_rect(a.gather, t, a.g.kw, a.g.pad, a.g.dil, a.g.hs, a.g.ws, a.g.hd, a.g.wd, y0, y1, x0, x1);
-            tiles_m += ((long long)a.g.n_img * (y1 - y0) * (x1 - x0) + BM8 - 1) / BM8;
-        }
-    }
+    const long long tiles_m = rows_tiles_m<BM8, false>(a.rect ? 1 : 0, a.M, a.tap_mask, a.g, a.gather);
     a.tiles_m = (int)tiles_m;
     dim3 grid((unsigned)(tiles_m * a.tiles_n), 1, batch);
     if (gather) hipLaunchKernelGGL((gemm_rows_bf16s8_kernel<true>), grid, dim3(NT8), SMEM_ROWS_S8, s, a);

@@ -212,26 +212,6 @@ GemmArgs make_args(const float* A, const float* B, const float* bias, float* C, 
     return a;
 }
 
-// rect mode (tap-parallel rectangles): validates and sizes the grid as the sum over taps of their tiles
-int setup_rect(const glf_gemm_params* p, const float* bias, GemmArgs& a, dim3& grid, const char* who) {
-    GLF_REQUIRE(p->gather == 1 || p->gather == 2, GLF_ERR_BAD_SHAPE, "%s: rect mode needs a conv gather", who);
-    GLF_REQUIRE(p->stride == 1, GLF_ERR_UNSUPPORTED, "%s: rect mode needs stride 1", who);
-    GLF_REQUIRE(bias == nullptr && !p->accumulate && p->batch == 1, GLF_ERR_UNSUPPORTED,
-                "%s: rect mode takes no bias / accumulate / batch (C must be zero-filled by the caller)", who);
-    long long tiles = 0;
-    for (unsigned mm = p->tap_mask; mm; mm &= mm - 1) {
-        const int t = __builtin_ctz(mm);
-        int y0, y1, x0, x1;
-        tap_rect(p->gather, t, p->kw, p->pad, p->dil, p->hs, p->ws, p->hd, p->wd, y0, y1, x0, x1);
-        const long long mt = (long long)p->n_img * (y1 - y0) * (x1 - x0);
-        tiles += (mt + BM - 1) / BM;
-    }
-    GLF_REQUIRE(tiles > 0 && tiles * a.tiles_n < 2147483647LL, GLF_ERR_BAD_SHAPE, "%s: rect mode grid out of range", who);
-    a.rect = 1;
-    grid = dim3((unsigned)(tiles * a.tiles_n), 1, 1);
-    return GLF_OK;
-}
-
 // contraction precision of this call: glf_gemm_params.precision (1 + mode) or, when 0, the process default
 inline int call_precision(const glf_gemm_params* p) {
     return (p->precision >= 1 && p->precision <= 4) ? p->precision - 1 : glf::precision();

@@ -18,7 +18,7 @@
 // Same tiling, LDS swizzle, software pipeline, gather / tap_mask / rect semantics and XCD-aware tile order as
 // gemm_bf16s.hip, with two planes per operand instead of three (96 KB of LDS).  Only the aligned fast path is
 // built; everything else stays on the exact-fp32 kernels.
-#include "gemm_common.h"
+#include "gemm_rows_walk.h"
 #include "split_f16.h"
 #include <cstdlib>
 #include <cstring>
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
     const float* __restrict__ p_zero = args.zeros;
     const int g_hs = args.g.hs, g_ws = args.g.ws, g_hd = args.g.hd, g_wd = args.g.wd, g_kw = args.g.kw;
     const int g_stride = args.g.stride, g_pad = args.g.pad, g_dil = args.g.dil;
-    const int g_nimg = args.g.n_img, p_rect = SEG ? 2 : (GATHER ? args.rect : 0);
+    const int p_rect = SEG ? 2 : (GATHER ? args.rect : 0);
     const int* __restrict__ p_seg = args.seg_tab;
     const int p_kx = args.seg_kx;
     float sc_a, sc_b, inv_a, inv_b;
@@ -107,65 +107,21 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    // tile order inside an XCD's contiguous range: groups of `gm` row tiles x all column tiles, walked down the rows first, so
-    // that the ~32 workgroups an XCD runs at a time form a gm x (32 / gm) block of tiles: each A row tile is shared by 32 / gm
-    // of them and each B column tile by gm of them through that XCD's L2 (gm = 0: the plain row-major order, every B tile
-    // fetched from the Infinity Cache once per row tile)
-    int tn, tm;
-    {
-        const int gm = (args.flags >> 8) & 0xff;
-        if (gm > 1) {
-            const int tiles_m_all = gridDim.x / p_tiles_n;
-            const int per_group = gm * p_tiles_n;
-            const int grp = bid / per_group, in_grp = bid - grp * per_group;
-            const int first_m = grp * gm;
-            const int gsz = min(tiles_m_all - first_m, gm);
-            tn = in_grp / gsz;
-            tm = first_m + (in_grp - tn * gsz);
-        } else {
-            tn = bid % p_tiles_n;
-            tm = bid / p_tiles_n;
-        }
-    }
-    int pMe = pM;
-    int r_y0 = 0, r_x0 = 0, r_h = g_hd, r_w = g_wd;
-    unsigned mask = p_tap_mask;
+    const RowsGeo G{p_gather, args.g.n_img, g_hs, g_ws, g_hd, g_wd, g_kw, g_stride, g_pad, g_dil};
+    int tn;
+    RowTile rt{0, pM, 0, 0, g_hd, g_wd, p_tap_mask};
+    rows_tile_order((args.flags >> 8) & 0xff, p_tiles_n, tn, rt.tm);
     unsigned seg_mask = 0;
     if constexpr (SEG) {
         // the plan's regions: lane r holds the first row tile of region r (INT_MAX beyond the last), one ballot finds this tile's
         const int start = p_seg[lane];
-        const int r = __builtin_amdgcn_readfirstlane(__popcll(__ballot(tm >= start)) - 1);
+        const int r = __builtin_amdgcn_readfirstlane(__popcll(__ballot(rt.tm >= start)) - 1);
         const int* __restrict__ reg = p_seg + SEG_TAB_REGIONS + SEG_REGION_INTS * r;
-        tm -= p_seg[r];
-        r_y0 = reg[0]; r_x0 = reg[1]; r_h = reg[2]; r_w = reg[3]; seg_mask = (unsigned)reg[4]; pMe = reg[5];
-    } else
-    if (p_rect == 2) {                              // region mode: tiles laid out region after region (see region_of)
-        bool found = false;
-#pragma unroll
-        for (int r = 0; r < 9; ++r) {
-            int y0, y1, x0, x1;
-            unsigned rm;
-            region_of(p_gather, r, g_dil, g_hd, g_wd, y0, y1, x0, x1, rm);
-            const int mt = g_nimg * (y1 - y0) * (x1 - x0);
-            const int tiles = (rm & p_tap_mask) ? (mt + BM8 - 1) / BM8 : 0;      // a region none of whose taps is kept gets no tiles
-            if (!found) {
-                if (tm < tiles) { found = true; mask = rm & p_tap_mask; pMe = mt; r_y0 = y0; r_x0 = x0; r_h = y1 - y0; r_w = x1 - x0; }
-                else tm -= tiles;
-            }
-        }
-        if (!found) return;
-    } else if (p_rect) {
-        for (unsigned mm = p_tap_mask; mm; mm &= mm - 1) {
-            const int t = __ffs(mm) - 1;
-            int y0, y1, x0, x1;
-            tap_rect(p_gather, t, g_kw, g_pad, g_dil, g_hs, g_ws, g_hd, g_wd, y0, y1, x0, x1);
-            const int mt = g_nimg * (y1 - y0) * (x1 - x0);
-            const int tiles = (mt + BM8 - 1) / BM8;
-            if (tm < tiles || (mm & (mm - 1)) == 0) { mask = 1u << t; pMe = mt; r_y0 = y0; r_x0 = x0; r_h = y1 - y0; r_w = x1 - x0; break; }
-            tm -= tiles;
-        }
-    }
+        rt.tm -= p_seg[r];
+        rt.y0 = reg[0]; rt.x0 = reg[1]; rt.h = reg[2]; rt.w = reg[3]; seg_mask = (unsigned)reg[4]; rt.rows = reg[5];
+    } else if (p_rect && !rows_locate<BM8, true>(p_rect, p_tap_mask, G, rt)) return;
+    const int tm = rt.tm, pMe = rt.rows;
+    unsigned mask = rt.mask;
     const int bz = blockIdx.z;
     const float* __restrict__ A = p_A + (long long)bz * p_bsa;
     const float* __restrict__ B = p_B + (long long)bz * p_bsb;
@@ -173,94 +129,11 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
 
     const int ac = tid & 7, ar = tid >> 3;              // 8 float4 per 32-deep row; rows ar + 64 j
 
-    int a_n[4], a_y[4], a_x[4];
-    long long a_off[4];
-    {
-        // pixel coordinates of the thread's first row by division, of the other three (64 rows further each) by carrying
-        int cn = 0, cy = 0, cx = 0;
-        if (GATHER || SEG) {
-            const int m0 = tm * BM8 + ar, hw = r_h * r_w;
-            cn = m0 / hw;
-            const int rem = m0 - cn * hw;
-            cy = rem / r_w; cx = rem - cy * r_w;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int m = tm * BM8 + ar + 64 * j;
-            if constexpr (SEG) {                    // the row's own pixel; a segment adds one uniform offset (advance)
-                a_n[j] = 0; a_y[j] = 0; a_x[j] = 0;
-                a_off[j] = (m < pMe) ? (long long)((cn * g_hd + r_y0 + cy) * g_wd + r_x0 + cx) * p_lda : -1;
-                if (j < 3 && m + 64 < pMe) {
-                    cx += 64;
-                    while (cx >= r_w) { cx -= r_w; ++cy; }
-                    while (cy >= r_h) { cy -= r_h; ++cn; }
-                }
-            } else
-            if (GATHER) {
-                if (m < pMe) { a_n[j] = cn; a_y[j] = r_y0 + cy; a_x[j] = r_x0 + cx; }
-                else { a_n[j] = -1; a_y[j] = 0; a_x[j] = 0; }
-                a_off[j] = -1;
-                if (j < 3 && m + 64 < pMe) {
-                    cx += 64;
-                    while (cx >= r_w) { cx -= r_w; ++cy; }
-                    while (cy >= r_h) { cy -= r_h; ++cn; }
-                }
-            } else {
-                a_n[j] = 0; a_y[j] = 0; a_x[j] = 0;
-                a_off[j] = (m < pM) ? (long long)m * p_lda : -1;
-            }
-        }
-    }
-    // Fast gather form (forward / wgrad-style gathers, and dgrad gathers of stride-1 convs -- everything but the dgrad of a
-    // strided conv): a row keeps (rb, y0, x0) = its source pixel index and coordinates for tap offset (0, 0); a tap then is
-    // one uniform offset pair (oy, ox): source = rb + oy * ws + ox, in range iff 0 <= y0 + oy < hs and 0 <= x0 + ox < ws.  The
-    // general map_src() (an integer division per call, two more for a strided dgrad, divergent branches around each) cost
-    // ~3.7 k cycles per tap change and ~20 k in the tap census below: 29 % of a 256 -> 256 3x3 conv's workgroup time
-    // (in-kernel stamps: prologue 26 k, 2 333 cycles per iteration against 1 869 for a plain GEMM).
-    const bool fastg = GATHER && (p_gather == 1 || g_stride == 1);
-    if (fastg) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (a_n[j] >= 0) {
-                const int y0 = (p_gather == 1) ? a_y[j] * g_stride - g_pad : a_y[j] + g_pad;
-                const int x0 = (p_gather == 1) ? a_x[j] * g_stride - g_pad : a_x[j] + g_pad;
-                a_n[j] = (a_n[j] * g_hs + y0) * g_ws + x0; a_y[j] = y0; a_x[j] = x0;
-            } else { a_n[j] = 0; a_y[j] = -(1 << 30); a_x[j] = 0; }          // never in range
-        }
-    }
-    // tap -> its uniform offsets (oy, ox) in source pixels
-    auto tap_offsets = [&](int t, int& oy, int& ox) __attribute__((always_inline)) {
-        int ky = 0, kx = __builtin_amdgcn_readfirstlane(t);
-        while (kx >= g_kw) { kx -= g_kw; ++ky; }
-        oy = (p_gather == 1 ? ky : -ky) * g_dil;
-        ox = (p_gather == 1 ? kx : -kx) * g_dil;
-    };
-    // tap census: drop the taps that fall into the padding for EVERY row of this tile.  It can only find one when the tile
-    // covers fewer than dil + 1 full image rows (otherwise each tap has a row it reaches): skipped for the small dilations.
-    if (GATHER && p_taps > 1 && !p_rect && BM8 < g_wd * (g_dil + 1)) {
-        if (tid == 0) *s_mask = 0u;
-        __syncthreads();
-        if (ac == 0) {
-            unsigned local = 0;
-            for (unsigned mm = mask; mm; mm &= mm - 1) {
-                const int t = __ffs(mm) - 1;
-                if (fastg) {
-                    int oy, ox;
-                    tap_offsets(t, oy, ox);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if ((unsigned)(a_y[j] + oy) < (unsigned)g_hs && (unsigned)(a_x[j] + ox) < (unsigned)g_ws) local |= 1u << t;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (a_n[j] >= 0 && map_src(g_hs, g_ws, g_kw, g_stride, g_pad, g_dil, p_gather, a_n[j], a_y[j], a_x[j], t) >= 0) local |= 1u << t;
-                }
-            }
-            if (local) atomicOr(s_mask, local);
-        }
-        __syncthreads();
-        mask &= *s_mask;
-    }
+    RowState<4> rows;
+    rows_init<4, 64, GATHER, SEG>(rows, tm * BM8 + ar, rt, p_lda, g_hd, g_wd);
+    const bool fastg = GATHER && rows_fast_gather(G);
+    if (fastg) rows_to_fast(rows, G);
+    rows_census<BM8, 4, GATHER>(rows, mask, fastg, ac == 0, p_taps, p_rect, G, s_mask);
 
     const int nkc = pK / BK;
     const int ntiles = SEG ? nkc + __popc(seg_mask) * (p_kx / BK) : __popc(mask) * nkc;
@@ -274,6 +147,7 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
     int bo_cur = 0;
     const float* pa[4];
     const float* pb[2];
+    const int a_col[4] = {4 * ac, 4 * ac, 4 * ac, 4 * ac};
 
     auto advance = [&]() __attribute__((always_inline)) {
         if constexpr (SEG) {
@@ -282,7 +156,7 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
                 if (tap == -1) {
                     tap = 0;                        // the K columns of the plain contraction come first
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) pa[j] = (a_off[j] >= 0 ? A + a_off[j] : p_zero) + 4 * ac;      // overhang rows read the zero page
+                    for (int j = 0; j < 4; ++j) pa[j] = (rows.off[j] >= 0 ? A + rows.off[j] : p_zero) + 4 * ac;      // overhang rows read the zero page
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
                         const int n = tn * BN + ar + 64 * j;
@@ -313,30 +187,7 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
         } else
         if (++kc >= nkc) {
             kc = 0;
-            tap = __ffs(rem_mask) - 1;
-            rem_mask &= rem_mask - 1;
-            if (fastg) {
-                int oy, ox;
-                tap_offsets(tap, oy, ox);
-                const int d = oy * g_ws + ox;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const bool ok = (unsigned)(a_y[j] + oy) < (unsigned)g_hs && (unsigned)(a_x[j] + ox) < (unsigned)g_ws;
-                    pa[j] = (ok ? A + (long long)(a_n[j] + d) * p_lda : p_zero) + 4 * ac;          // padding rows read the zero page
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    long long off;
-                    if (GATHER) {
-                        const int sr = (a_n[j] >= 0) ? map_src(g_hs, g_ws, g_kw, g_stride, g_pad, g_dil, p_gather, a_n[j], a_y[j], a_x[j], tap) : -1;
-                        off = (sr >= 0) ? (long long)sr * p_lda : -1;
-                    } else {
-                        off = a_off[j];
-                    }
-                    pa[j] = (off >= 0 ? A + off : p_zero) + 4 * ac;          // padding / overhang rows read the zero page
-                }
-            }
+            tap = rows_next_tap<4, GATHER>(rows, rem_mask, pa, A, p_zero, p_lda, fastg, G, a_col);
             const float* Bt = B + (long long)tap * p_tsb;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -639,192 +490,9 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
 #endif
     }
 
-    float cmax = 0.f;
-    const bool p_colstats = args.colstats != nullptr;
-    const float* __restrict__ p_res = EPI ? args.res : nullptr;
-    const long long p_ldr = args.ld_res;
-    const bool p_relu = EPI && args.relu != 0;
-    const bool res_vec = (p_ldr % 4) == 0 && (reinterpret_cast<size_t>(p_res) % 16) == 0;
-    // one result element -> C (plain / accumulate / region store, or the atomic of per-tap rectangles); cs / cq: the calling
-    // lane's column sum and sum of squares over the elements it stores (colstats)
-    auto put = [&](float a, int row, int col, float bv, double& cs, double& cq) __attribute__((always_inline)) {
-        if (row >= pMe) return;
-        long long orow = row;
-        if (p_rect) {
-            const int hw = r_h * r_w;
-            const int n = row / hw, rem = row - n * hw;
-            const int yy = rem / r_w;
-            orow = ((long long)n * g_hd + r_y0 + yy) * g_wd + r_x0 + (rem - yy * r_w);
-            if (p_rect == 1) { atomicAdd(C + orow * p_ldc + col, p_alpha * a); return; }
-        }
-        float* dst = C + orow * p_ldc + col;
-        float v = p_alpha * a + bv;
-        if constexpr (EPI) {
-            if (p_res) v += p_res[orow * p_ldr + col];
-            if (p_relu) v = fmaxf(v, 0.f);
-        }
-        if (p_accumulate) v += *dst;
-        *dst = v;
-        cmax = fmaxf(cmax, fabsf(v));
-        if (p_colstats) { const double vd = (double)v; cs += vd; cq = fma(vd, vd, cq); }
-    };
-    // column statistics in double from the first product on: E[x^2] - E[x]^2 cancels badly when a channel's values are close
-    // together (the ASPP pooled branch: N nearly equal frame averages), fp32 partial sums cost 4e-4 on its BatchNorm output
-    // Fast epilogue (everything but the atomics of per-tap rectangles and unaligned outputs): every wave parks its 64 x 64
-    // results in LDS (free once the main loop's last barrier is passed: 8 x 16 KB) and stores them as whole 16-byte pieces
-    // of rows -- 16 global_store_dwordx4 per lane instead of 64 one-dword stores.  The one-dword form took ~19 k cycles per
-    // workgroup (in-kernel stamps, profiles/r02_stamps_*.txt): 13 % of a K = 2048 tile's time, 40 % of a K = 512 tile's,
-    // with the matrix pipe idle (one workgroup per CU: nothing else runs meanwhile).
-    const bool wide_store = p_rect != 1 && (p_ldc % 4) == 0 && (pN % 4) == 0 && (reinterpret_cast<size_t>(C) % 16) == 0 &&
-                            (p_bsc % 4) == 0;
-    if (wide_store) {
-        float* tile = reinterpret_cast<float*>(smem_s) + wave * (64 * 64);
-        const int col_l = lane & 31, row_l = 4 * (lane >> 5);
-        auto park = [&](const f32x16& acc, int ti, int tj) __attribute__((always_inline)) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) tile[(32 * ti + (r & 3) + 8 * (r >> 2) + row_l) * 64 + 32 * tj + col_l] = acc[r];
-        };
-        park(c00 + m00 * 0x1p-11f, 0, 0); park(c01 + m01 * 0x1p-11f, 0, 1);
-        park(c10 + m10 * 0x1p-11f, 1, 0); park(c11 + m11 * 0x1p-11f, 1, 1);
-        __syncthreads();
-        const int c4 = 4 * (lane & 15), r0 = lane >> 4;
-        const int col = tn * BN + wn + c4;
-        double cs[4] = {0.0, 0.0, 0.0, 0.0}, cq[4] = {0.0, 0.0, 0.0, 0.0};
-        float cx[4] = {0.f, 0.f, 0.f, 0.f};          // column maxima of |C| (args.colmax)
-        if (col < pN) {
-            float bv[4] = {0.f, 0.f, 0.f, 0.f};
-            if (p_bias) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) bv[j] = p_bias[col + j];
-            }
-            // region / rectangle stores: pixel coordinates of the lane's first row by division, of the next ones (4 rows on) by carrying
-            int en = 0, ey = 0, ex = 0;
-            if (p_rect) {
-                const int row0 = tm * BM8 + wm + r0, hw = r_h * r_w;
-                en = row0 / hw;
-                const int rem = row0 - en * hw;
-                ey = rem / r_w; ex = rem - ey * r_w;
-            }
-            if (p_accumulate && !p_rect && !p_colstats) {
-                // C += result (the accumulate epilogue of glf_gemm): all 16 old values are requested before the first is
-                // needed -- fetched inside the store loop, each of its 4-deep batches waited out a full memory round trip
-                float4 prev[16];
-                const int rowb = tm * BM8 + wm + r0;
-#pragma unroll
-                for (int i = 0; i < 16; ++i)
-                    prev[i] = rowb + 4 * i < pMe ? *reinterpret_cast<const float4*>(C + (long long)(rowb + 4 * i) * p_ldc + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    if (rowb + 4 * i < pMe) {
-                        const float4 a = *reinterpret_cast<const float4*>(tile + (r0 + 4 * i) * 64 + c4);
-                        float4 v = make_float4(p_alpha * a.x + bv[0], p_alpha * a.y + bv[1], p_alpha * a.z + bv[2], p_alpha * a.w + bv[3]);
-                        v.x += prev[i].x; v.y += prev[i].y; v.z += prev[i].z; v.w += prev[i].w;
-                        *reinterpret_cast<float4*>(C + (long long)(rowb + 4 * i) * p_ldc + col) = v;
-                        cmax = fmaxf(cmax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-                    }
-                }
-            } else
-#pragma unroll 4
-            for (int i = 0; i < 16; ++i) {
-                const int rin = r0 + 4 * i;
-                const int row = tm * BM8 + wm + rin;
-                if (row >= pMe) break;
-                long long orow = row;
-                if (p_rect) {
-                    orow = ((long long)en * g_hd + r_y0 + ey) * g_wd + r_x0 + ex;
-                    ex += 4;
-                    while (ex >= r_w) { ex -= r_w; ++ey; }
-                    while (ey >= r_h) { ey -= r_h; ++en; }
-                }
-                const float4 a = *reinterpret_cast<const float4*>(tile + rin * 64 + c4);
-                float* dst = C + orow * p_ldc + col;
-                float v[4] = {p_alpha * a.x + bv[0], p_alpha * a.y + bv[1], p_alpha * a.z + bv[2], p_alpha * a.w + bv[3]};
-                if constexpr (EPI) {
-                    if (p_res) {
-                        const float* rp = p_res + orow * p_ldr + col;
-                        const float4 r = ld4(rp, 4, res_vec);
-                        v[0] += r.x; v[1] += r.y; v[2] += r.z; v[3] += r.w;
-                    }
-                    if (p_relu) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-                    }
-                }
-                if (p_accumulate) {
-                    const float4 o = *reinterpret_cast<const float4*>(dst);
-                    v[0] += o.x; v[1] += o.y; v[2] += o.z; v[3] += o.w;
-                }
-                *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-                cmax = fmaxf(cmax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-                if (p_colstats) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { const double vd = (double)v[j]; cs[j] += vd; cq[j] = fma(vd, vd, cq[j]); cx[j] = fmaxf(cx[j], fabsf(v[j])); }
-                }
-            }
-        }
-        if (p_colstats) {
-            // lanes l, l + 16, l + 32, l + 48 hold the four row groups of the same four columns; the wave rows of the workgroup
-            // are then folded through LDS (each wave's own parking area is free once its stores are issued), so that ONE f64
-            // atomic per column, statistic and WORKGROUP reaches memory.  Per wave it was M / 64 atomics on each of the N
-            // addresses: 3 025 per address on a 193 600-row layer-1 conv output -- ~150 us of serialised atomics behind a 60 us
-            // contraction (profiles/r03_colstats_atomics.txt).
-            double* st = args.colstats;
-            double* fold = reinterpret_cast<double*>(tile);              // [64 columns][3]: sum, sum of squares, maximum
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                cs[j] += __shfl_xor(cs[j], 16, 64); cq[j] += __shfl_xor(cq[j], 16, 64);
-                cs[j] += __shfl_xor(cs[j], 32, 64); cq[j] += __shfl_xor(cq[j], 32, 64);
-                cx[j] = fmaxf(cx[j], __shfl_xor(cx[j], 16, 64)); cx[j] = fmaxf(cx[j], __shfl_xor(cx[j], 32, 64));
-                if (lane < 16) { fold[3 * (c4 + j)] = cs[j]; fold[3 * (c4 + j) + 1] = cq[j]; fold[3 * (c4 + j) + 2] = (double)cx[j]; }
-            }
-            __syncthreads();
-            if (wm == 0) {                                               // waves 0 / 1: the two column halves of the tile
-                const int cl = lane;                                     // column within the wave's 64
-                double s = 0.0, q = 0.0;
-                float mx = 0.f;
-#pragma unroll
-                for (int w = 0; w < WAVE_ROWS; ++w) {
-                    const double* f = reinterpret_cast<const double*>(reinterpret_cast<const float*>(smem_s) + (2 * w + (wave & 1)) * (64 * 64));
-                    s += f[3 * cl]; q += f[3 * cl + 1]; mx = fmaxf(mx, (float)f[3 * cl + 2]);
-                }
-                const int cg = tn * BN + wn + cl;
-                if (cg < pN) {
-                    atomicAdd(st + cg, s); atomicAdd(st + pN + cg, q);
-                    if (args.colmax && mx > 0.f) atomicMax(reinterpret_cast<unsigned*>(args.colmax + cg), __float_as_uint(mx));
-                }
-            }
-        }
-    } else {
-        const int col_l = lane & 31, row_l = 4 * (lane >> 5);
-        auto emit = [&](const f32x16& acc, int ti, int tj, double& cs, double& cq) {
-            const int col = tn * BN + wn + 32 * tj + col_l;
-            if (col >= pN) return;
-            const float bv = p_bias ? p_bias[col] : 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) put(acc[r], tm * BM8 + wm + 32 * ti + (r & 3) + 8 * (r >> 2) + row_l, col, bv, cs, cq);
-        };
-        double cs0 = 0.0, cq0 = 0.0, cs1 = 0.0, cq1 = 0.0;
-        emit(c00 + m00 * 0x1p-11f, 0, 0, cs0, cq0); emit(c01 + m01 * 0x1p-11f, 0, 1, cs1, cq1);
-        emit(c10 + m10 * 0x1p-11f, 1, 0, cs0, cq0); emit(c11 + m11 * 0x1p-11f, 1, 1, cs1, cq1);
-        if (args.colstats && p_rect != 1) {
-            // lanes l and l + 32 hold the two row groups of the same column: fold them, then one f64 atomic per column
-            // and statistic from this wave's 64 rows
-            double* st = args.colstats;
-            cs0 += __shfl_xor(cs0, 32, 64); cq0 += __shfl_xor(cq0, 32, 64);
-            cs1 += __shfl_xor(cs1, 32, 64); cq1 += __shfl_xor(cq1, 32, 64);
-            if (lane < 32) {
-                const int col0 = tn * BN + wn + col_l, col1 = col0 + 32;
-                if (col0 < pN) { atomicAdd(st + col0, cs0); atomicAdd(st + pN + col0, cq0); }
-                if (col1 < pN) { atomicAdd(st + col1, cs1); atomicAdd(st + pN + col1, cq1); }
-            }
-        }
-    }
-    if (args.amax_c && p_rect != 1) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cmax = fmaxf(cmax, __shfl_xor(cmax, o, 64));
-        if (lane == 0 && cmax > *reinterpret_cast<volatile float*>(args.amax_c))      // thousands of waves, ONE address: only a wave that raises it
-            atomicMax(reinterpret_cast<unsigned*>(args.amax_c), __float_as_uint(cmax));
-    }
+    const RowsOut out{C, p_bias, args.res, args.colstats, args.colmax, args.amax_c, args.ld_res, p_bsc,
+                      pN, p_ldc, p_accumulate, p_rect, args.relu, tn, g_hd, g_wd, p_alpha};
+    rows_f16s_epilogue<BM8, WAVE_ROWS, EPI>(out, rt, smem_s, c00, c01, c10, c11, m00, m01, m10, m11);
 #if defined(GLF_STAMPS) && GLF_STAMPS == 2
     if (args.partial != nullptr && blockIdx.x == gridDim.x / 2) {
         __builtin_amdgcn_s_waitcnt(0);          // the stores of this wave's part of C have been accepted
@@ -1598,25 +1266,8 @@ int launch_rows_f16s(const GemmArgs& a0, dim3 grid, bool gather, int nprod, hipS
     if (use_f16s4(a0)) return launch_rows_f16s4(a0, grid, gather, nprod, s);      // short reductions: two workgroups per CU
     GemmArgs a = a0;
     a.zeros = zero_page();
-    long long tiles_m = (a.M + BM8 - 1) / BM8;
-    if (a.rect == 2) {
-        tiles_m = 0;
-        for (int r = 0; r < 9; ++r) {
-            int y0, y1, x0, x1;
-            unsigned rm;
-            region_of(a.gather, r, a.g.dil, a.g.hd, a.g.wd, y0, y1, x0, x1, rm);
-            if (rm & a.tap_mask) tiles_m += ((long long)a.g.n_img * (y1 - y0) * (x1 - x0) + BM8 - 1) / BM8;      // as the kernel's region walk
-        }
-        if (tiles_m == 0) return GLF_OK;             // every region's tap set is empty under this mask: nothing to add
-    } else if (a.rect) {
-        tiles_m = 0;
-        for (unsigned mm = a.tap_mask; mm; mm &= mm - 1) {
-            const int t = __builtin_ctz(mm);
-            int y0, y1, x0, x1;
-            tap_rect(a.gather, t, a.g.kw, a.g.pad, a.g.dil, a.g.hs, a.g.ws, a.g.hd, a.g.wd, y0, y1, x0, x1);
-            tiles_m += ((long long)a.g.n_img * (y1 - y0) * (x1 - x0) + BM8 - 1) / BM8;
-        }
-    }
+    const long long tiles_m = rows_tiles_m<BM8, true>(a.rect, a.M, a.tap_mask, a.g, a.gather);
+    if (a.rect == 2 && tiles_m == 0) return GLF_OK;  // every region's tap set is empty under this mask: nothing to add
     a.tiles_m = (int)tiles_m;
     dim3 g2((unsigned)(tiles_m * a.tiles_n), 1, grid.z);
     // tile order: groups of 4 row tiles x all column tiles once there are >= 8 column tiles (more of the streamed operands

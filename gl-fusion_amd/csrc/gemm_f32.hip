@@ -18,7 +18,7 @@
 //   gemm_rows_kernel<0>  A[m][k] (gathered rows) x B[n][k]   -> conv forward, 1x1 / linear
 //   gemm_rows_kernel<1>  A[m][k] (gathered rows) x B[k][n]   -> conv dgrad, y = theta @ M
 //   gemm_tn_kernel       sum_r A[r][m] * B[src(r)][n]        -> conv wgrad, M = phi^T g
-#include "gemm_common.h"
+#include "gemm_rows_walk.h"
 
 namespace {
 

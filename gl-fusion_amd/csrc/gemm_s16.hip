@@ -19,7 +19,7 @@
 //     256 x 128 tiles over 64 reduction rows per stage; LDS images stay [r][m] / [r][n] (dense 512 / 256-byte rows, 64-byte
 //     chunks XORed with r & 3) and fragments are transposed on the way out by ds_read_b64_tr_b16; split-K slices store
 //     partial slabs that s16_tn_reduce_kernel folds in slice order (no atomics: bitwise reproducible gradients).
-#include "gemm_common.h"
+#include "gemm_rows_walk.h"
 #include <type_traits>
 
 namespace {
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(NTH, TK_ == 64 ? 2 : 4) void s16_rows_kernel(const 
     const u16* __restrict__ p_zero = args.zeros;
     const int g_hs = args.g.hs, g_ws = args.g.ws, g_hd = args.g.hd, g_wd = args.g.wd, g_kw = args.g.kw;
     const int g_stride = args.g.stride, g_pad = args.g.pad, g_dil = args.g.dil;
-    const int g_nimg = args.g.n_img, p_rect = GATHER ? args.rect : 0;
+    const int p_rect = GATHER ? args.rect : 0;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned* s_mask = reinterpret_cast<unsigned*>(smem + Cfg::SMEM - 16);
@@ -119,28 +119,14 @@ __global__ __launch_bounds__(NTH, TK_ == 64 ? 2 : 4) void s16_rows_kernel(const 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * WNC;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tn = bid % p_tiles_n;
-    int tm = bid / p_tiles_n;
-    int pMe = pM;
-    int r_y0 = 0, r_x0 = 0, r_h = g_hd, r_w = g_wd;
-    unsigned mask = p_tap_mask;
-    if (p_rect == 2) {                                  // region mode: tiles laid out region after region (region_of)
-        bool found = false;
-#pragma unroll
-        for (int r = 0; r < 9; ++r) {
-            int y0, y1, x0, x1;
-            unsigned rm;
-            region_of(p_gather, r, g_dil, g_hd, g_wd, y0, y1, x0, x1, rm);
-            const int mt = g_nimg * (y1 - y0) * (x1 - x0);
-            const int tiles = (mt + TM - 1) / TM;
-            if (!found) {
-                if (tm < tiles) { found = true; mask = rm & p_tap_mask; pMe = mt; r_y0 = y0; r_x0 = x0; r_h = y1 - y0; r_w = x1 - x0; }
-                else tm -= tiles;
-            }
-        }
-        if (!found) return;
-    }
+    const RowsGeo G{p_gather, args.g.n_img, g_hs, g_ws, g_hd, g_wd, g_kw, g_stride, g_pad, g_dil};
+    int tn;
+    RowTile rt{0, pM, 0, 0, g_hd, g_wd, p_tap_mask};
+    rows_tile_order(0, p_tiles_n, tn, rt.tm);
+    // region mode only (rect = 2); a region without kept taps keeps its tiles: this launch stores every element once
+    if (p_rect == 2 && !rows_locate<TM, false>(2, p_tap_mask, G, rt)) return;
+    const int tm = rt.tm, pMe = rt.rows, r_y0 = rt.y0, r_x0 = rt.x0, r_h = rt.h, r_w = rt.w;
+    unsigned mask = rt.mask;
     const int bz = blockIdx.z;
     const u16* __restrict__ A = args.A + (long long)bz * args.bsa;
     const u16* __restrict__ B = args.B + (long long)bz * args.bsb;
@@ -151,81 +137,16 @@ __global__ __launch_bounds__(NTH, TK_ == 64 ? 2 : 4) void s16_rows_kernel(const 
     // ds_read_b128 for the 32x32x16 operand map (row = lane & 31, chunk = 2 s + (lane >> 5)) in both cases
     auto swz = [](int r) __attribute__((always_inline)) { return CPR == 8 ? ((r >> 1) & 7) : ((r >> 2) & 3); };
     // A rows of this lane: wave * (AJ * RPI) + RPI j + lrow
-    int a_rb[AJ], a_y[AJ], a_x[AJ];                      // gather: source pixel index / coordinates for tap offset (0, 0)
-    long long a_off[AJ];                                 // plain: element offset of the row, -1 = overhang
+    RowState<AJ> rows;
     int a_sw[AJ];
-    {
-        int cn = 0, cy = 0, cx = 0;
-        if (GATHER) {
-            const int m0 = tm * TM + wave * (AJ * RPI) + lrow, hw = r_h * r_w;
-            cn = m0 / hw;
-            const int rem = m0 - cn * hw;
-            cy = rem / r_w; cx = rem - cy * r_w;
-        }
 #pragma unroll
-        for (int j = 0; j < AJ; ++j) {
-            const int m = tm * TM + wave * (AJ * RPI) + RPI * j + lrow;
-            a_sw[j] = (lch ^ swz(wave * (AJ * RPI) + RPI * j + lrow)) * 8;
-            if (GATHER) {
-                if (m < pMe) { a_rb[j] = cn; a_y[j] = r_y0 + cy; a_x[j] = r_x0 + cx; }
-                else { a_rb[j] = -1; a_y[j] = 0; a_x[j] = 0; }
-                a_off[j] = -1;
-                if (j < AJ - 1) {
-                    cx += RPI;
-                    while (cx >= r_w) { cx -= r_w; ++cy; }
-                    while (cy >= r_h) { cy -= r_h; ++cn; }
-                }
-            } else {
-                a_rb[j] = 0; a_y[j] = 0; a_x[j] = 0;
-                a_off[j] = (m < pM) ? (long long)m * p_lda : -1;
-            }
-        }
-    }
+    for (int j = 0; j < AJ; ++j) a_sw[j] = (lch ^ swz(wave * (AJ * RPI) + RPI * j + lrow)) * 8;
+    rows_init<AJ, RPI, GATHER>(rows, tm * TM + wave * (AJ * RPI) + lrow, rt, p_lda, g_hd, g_wd);
     // fast gather form: everything but the dgrad of a strided conv keeps (source index, y, x) for tap offset (0, 0)
-    const bool fastg = GATHER && (p_gather == 1 || g_stride == 1);
-    if (fastg) {
-#pragma unroll
-        for (int j = 0; j < AJ; ++j) {
-            if (a_rb[j] >= 0) {
-                const int y0 = (p_gather == 1) ? a_y[j] * g_stride - g_pad : a_y[j] + g_pad;
-                const int x0 = (p_gather == 1) ? a_x[j] * g_stride - g_pad : a_x[j] + g_pad;
-                a_rb[j] = (a_rb[j] * g_hs + y0) * g_ws + x0; a_y[j] = y0; a_x[j] = x0;
-            } else { a_rb[j] = 0; a_y[j] = -(1 << 30); a_x[j] = 0; }
-        }
-    }
-    auto tap_offsets = [&](int t, int& oy, int& ox) __attribute__((always_inline)) {
-        int ky = 0, kx = __builtin_amdgcn_readfirstlane(t);
-        while (kx >= g_kw) { kx -= g_kw; ++ky; }
-        oy = (p_gather == 1 ? ky : -ky) * g_dil;
-        ox = (p_gather == 1 ? kx : -kx) * g_dil;
-    };
-    // tap census: drop the taps that are padding for EVERY row of this tile (only possible when the tile covers fewer than
-    // dil + 1 image rows)
-    if (GATHER && p_taps > 1 && !p_rect && TM < g_wd * (g_dil + 1)) {
-        if (tid == 0) *s_mask = 0u;
-        __syncthreads();
-        if (lch == 0) {
-            unsigned local = 0;
-            for (unsigned mm = mask; mm; mm &= mm - 1) {
-                const int t = __ffs(mm) - 1;
-                if (fastg) {
-                    int oy, ox;
-                    tap_offsets(t, oy, ox);
-#pragma unroll
-                    for (int j = 0; j < AJ; ++j)
-                        if ((unsigned)(a_y[j] + oy) < (unsigned)g_hs && (unsigned)(a_x[j] + ox) < (unsigned)g_ws) local |= 1u << t;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < AJ; ++j)
-                        if (a_rb[j] >= 0 && map_src(g_hs, g_ws, g_kw, g_stride, g_pad, g_dil, p_gather, a_rb[j], a_y[j], a_x[j], t) >= 0) local |= 1u << t;
-                }
-            }
-            if (local) atomicOr(s_mask, local);
-        }
-        __syncthreads();
-        mask &= *s_mask;
+    const bool fastg = GATHER && rows_fast_gather(G);
+    if (fastg) rows_to_fast(rows, G);
+    if (rows_census<TM, AJ, GATHER>(rows, mask, fastg, lch == 0, p_taps, p_rect, G, s_mask))
         __syncthreads();                                  // s_mask shares LDS with nothing else, but keep the read ahead of any reuse
-    }
 
     const int nkc = pK / TK_;
     const int ntiles = __popc(mask) * nkc;
@@ -242,30 +163,7 @@ __global__ __launch_bounds__(NTH, TK_ == 64 ? 2 : 4) void s16_rows_kernel(const 
     auto advance = [&]() __attribute__((always_inline)) {
         if (++kc >= nkc) {
             kc = 0;
-            tap = __ffs(rem_mask) - 1;
-            rem_mask &= rem_mask - 1;
-            if (fastg) {
-                int oy, ox;
-                tap_offsets(tap, oy, ox);
-                const int d = oy * g_ws + ox;
-#pragma unroll
-                for (int j = 0; j < AJ; ++j) {
-                    const bool ok = (unsigned)(a_y[j] + oy) < (unsigned)g_hs && (unsigned)(a_x[j] + ox) < (unsigned)g_ws;
-                    pa[j] = (ok ? A + (long long)(a_rb[j] + d) * p_lda : p_zero) + a_sw[j];
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < AJ; ++j) {
-                    long long off;
-                    if (GATHER) {
-                        const int sr = (a_rb[j] >= 0) ? map_src(g_hs, g_ws, g_kw, g_stride, g_pad, g_dil, p_gather, a_rb[j], a_y[j], a_x[j], tap) : -1;
-                        off = (sr >= 0) ? (long long)sr * p_lda : -1;
-                    } else {
-                        off = a_off[j];
-                    }
-                    pa[j] = (off >= 0 ? A + off : p_zero) + a_sw[j];
-                }
-            }
+            tap = rows_next_tap<AJ, GATHER>(rows, rem_mask, pa, A, p_zero, p_lda, fastg, G, a_sw);
             const u16* Bt = B + (long long)tap * p_tsb;
 #pragma unroll
             for (int j = 0; j < BJ; ++j) {
@@ -967,20 +865,13 @@ int rows_plan16(const glf_gemm_params* p, RowsPlan16& r, const char* who) {
     // chains run, was measured: +1.4 ms per step -- profiles/r04_ab_s16.txt)
     r.bn = p->N <= 64 ? 64 : 128;
     r.tiles_n = (p->N + r.bn - 1) / r.bn;
-    r.tiles_m = (p->M + TM - 1) / TM;
     r.rect = 0;
     if (p->rect == 2) {
         GLF_REQUIRE(p->gather != 0 && p->kh == 3 && p->kw == 3 && p->stride == 1 && p->pad == p->dil && p->hs == p->hd && p->ws == p->wd && p->batch == 1,
                     GLF_ERR_UNSUPPORTED, "%s: region mode needs a 3x3 stride-1 conv with pad == dil on equal maps, batch 1", who);
         r.rect = 2;
-        r.tiles_m = 0;
-        for (int i = 0; i < 9; ++i) {
-            int y0, y1, x0, x1;
-            unsigned rm;
-            region_of(p->gather, i, p->dil, p->hd, p->wd, y0, y1, x0, x1, rm);
-            r.tiles_m += ((long long)p->n_img * (y1 - y0) * (x1 - x0) + TM - 1) / TM;
-        }
     }
+    r.tiles_m = rows_tiles_m<TM, false>(r.rect, p->M, p->tap_mask, Geo{p->n_img, p->hs, p->ws, p->hd, p->wd, p->kh, p->kw, p->stride, p->pad, p->dil}, p->gather);
     GLF_REQUIRE(r.tiles_m * r.tiles_n < 2147483647LL, GLF_ERR_BAD_SHAPE, "%s: grid out of range", who);
     // stage depth: 32 = two workgroups per CU (the default), 64 = one per CU with half the barriers; GLF_S16_TK=32|64 forces one
     static const int tk_force = []() { const char* e = getenv("GLF_S16_TK"); return e ? atoi(e) : 0; }();

@@ -37,7 +37,12 @@ def ops(precision):
 # ------------------------------------------------------------------------------------------ GEMM
 @pytest.mark.parametrize("M,N,K,batch", [(300, 70, 52, 1), (128, 128, 32, 1), (517, 260, 100, 3), (64, 5, 256, 1), (1000, 256, 5, 1),
                                          # <= 64 rows, K % 16 == 0, N >= 64: glf_gemm_nt's skinny kernel (the ASPP pooled branch's shape last)
-                                         (1, 64, 16, 1), (37, 131, 80, 1), (64, 256, 2048, 1)])
+                                         (1, 64, 16, 1), (37, 131, 80, 1), (64, 256, 2048, 1),
+                                         # split-fp16 NT, both tile heights (K <= 256: 128-row tiles, above: 256-row tiles), one row more than a
+                                         # tile: N = 132 wide store with a ragged second column tile, N = 70 the one-dword store
+                                         (129, 132, 32, 1), (257, 132, 288, 1), (129, 70, 32, 1), (257, 70, 288, 1),
+                                         # 8 column tiles: grouped tile order, 5 row tiles so that the last group is short
+                                         (513, 900, 32, 1), (1025, 900, 288, 1)])
 def test_gemm_nt_nn_tn_plain(ops, M, N, K, batch):
     A = rnd(batch, M, K, seed=1)
     Bnk = rnd(batch, N, K, seed=2)
@@ -311,7 +316,9 @@ def test_softmax_rows(ops):
 
 
 @pytest.mark.parametrize("cfg", [(3, 9, 11, 64, 96, 1, 1, 0, 1), (2, 28, 28, 32, 160, 3, 1, 2, 2), (2, 28, 28, 64, 40, 3, 1, 36, 36),
-                                 (2, 55, 55, 32, 48, 3, 2, 1, 1), (5, 1, 1, 64, 32, 1, 1, 0, 1)])
+                                 (2, 55, 55, 32, 48, 3, 2, 1, 1), (5, 1, 1, 64, 32, 1, 1, 0, 1),
+                                 # two row tiles + 3 rows of either split-fp16 tile height: every wave row, two workgroups per column
+                                 (7, 37, 1, 32, 48, 1, 1, 0, 1), (5, 103, 1, 288, 48, 1, 1, 0, 1)])
 def test_conv_epilogue_column_statistics(ops, cfg):
     """f16x3: the conv epilogue accumulates (sum y, sum y^2) per output channel; BatchNorm fed with them must equal
     BatchNorm computing its statistics with its own pass over y."""

@@ -386,7 +386,7 @@ def call16(mode, A, B, Cm, **kw):
 # ----------------------------------------------------------------------------------------
 def nt_spec(M=None, N=64, K=64, *, batch=1, bias=False, alpha=1.0, alpha_g=1.0 / 49, gather=0, conv=None, rect=0, lda=None, ldb=None,
             ldc=None, bsa=None, bsb=None, bsc=None, a_off=16, c_off=16, families=("dense", "gauss"), colstats=False,
-            dtypes=(BF, F32), accumulates=(False, True), emulate=True):
+            dtypes=(BF, F32), accumulates=(False, True), emulate=True, tap_mask=None):
     s = dict(locals())
     if gather:
         geo = geo_of(gather, conv)
@@ -416,6 +416,8 @@ def run_nt(s, seed=1):
     M, N, K, batch, gather, conv, taps = s["M"], s["N"], s["K"], s["batch"], s["gather"], s["conv"], s["taps"]
     src = src_index(gather, s["geo"]) if gather else torch.arange(M).view(1, M)
     mask = mask_of(src) if gather else 1
+    if s["tap_mask"] is not None:                  # a caller's mask: only some of the in-range taps are contracted
+        mask &= s["tap_mask"]
     kept = bin(mask).count("1")
     n_terms = K * kept
     print(f"\n  NT M {M} N {N} K {K} batch {batch} gather {gather} conv {conv} rect {s['rect']} mask {mask:#x}: "
@@ -430,7 +432,7 @@ def run_nt(s, seed=1):
             bias = dense_ints((N,), seed + 2, -8, 8) if exact else gauss((N,), seed + 2, dtype=F32)
         P, Q = zip(*(nt_products(A[b], B[b], src, mask) for b in range(batch)))
         P, Q = torch.stack(P), torch.stack(Q)
-        if gather and batch == 1:
+        if gather and batch == 1 and s["tap_mask"] is None:
             # the reference proper is F.conv2d (and its autograd) in float64; the index form gives the magnitudes and the emulation
             cref = (conv_fwd_ref if gather == 1 else conv_dgrad_ref)(A[0], B[0], conv)
             if exact:
@@ -510,6 +512,7 @@ NT_NARROW = {
     "ldc_odd_n136": nt_spec(300, 136, 64, ldc=139, bias=True),
     "bsc_odd_b3": nt_spec(300, 72, 128, batch=3, bsc=300 * 80 + 4),
     "c_off_2": nt_spec(300, 136, 128, c_off=18, alpha=-2.0),
+    "m257_n60": nt_spec(257, 60, 64, ldc=64, bias=True),                            # BN 64: one row past a tile, ragged columns
 }
 for _s in NT_NARROW.values():
     assert not nt_spec_variant(_s, True)["wide"] and not nt_spec_variant(_s, False)["wide"]
@@ -558,6 +561,8 @@ NT_GATHER_CONVS = {
     "3x3_d12_28x28_census": dict(conv=(2, 28, 28, 3, 1, 12, 12), N=64, K=64),
     "3x3_d4_60x72_census": dict(conv=(1, 60, 72, 3, 1, 4, 4), N=136, K=64),
     "3x3_d1_13x11_k2048": dict(conv=(2, 13, 11, 3, 1, 1, 1), N=136, K=2048, alpha=0.5, gathers=(1,)),   # 18 432 terms
+    "3x3_d12_28x28_n1_census": dict(conv=(1, 28, 28, 3, 1, 12, 12), N=136, K=64),                       # 784 rows: a ragged last tile
+    "3x3_s2_55to28_n1": dict(conv=(1, 55, 55, 3, 2, 1, 1), N=136, K=64, gathers=(2,)),                  # strided dgrad, 3025 rows
 }
 NT_GATHER = {f"g{g}_{k}": nt_spec(gather=g, **{a: b for a, b in v.items() if a != "gathers"})
              for k, v in NT_GATHER_CONVS.items() for g in v.get("gathers", (1, 2))}
@@ -570,6 +575,10 @@ NT_REGION_CONVS = {
     "d12_10x12_centre_only": dict(conv=(3, 10, 12, 3, 1, 12, 12), N=64, K=64),   # h, w <= dil: side regions empty
 }
 NT_REGION = {f"g{g}_{k}": nt_spec(gather=g, rect=2, **v) for k, v in NT_REGION_CONVS.items() for g in (1, 2)}
+# a caller's tap mask under which the first corner region (y, x < 12) has no tap left: its rows are still stored (zeros plus bias),
+# because this launch stores every element exactly once.  Forward gather: the corner reaches taps 4, 5, 7, 8; transposed: 0, 1, 3, 4.
+NT_REGION["g1_d12_28x28_empty_region"] = nt_spec(gather=1, rect=2, conv=(1, 28, 28, 3, 1, 12, 12), N=136, K=64, bias=True, tap_mask=0x04F)
+NT_REGION["g2_d12_28x28_empty_region"] = nt_spec(gather=2, rect=2, conv=(1, 28, 28, 3, 1, 12, 12), N=136, K=64, bias=True, tap_mask=0x1E4)
 
 
 @pytest.mark.parametrize("name", list(NT_GATHER))
