@@ -5,12 +5,18 @@
 //     [H0][W0][T] volume and writing the model's layout directly: frames [T][1][112][112], masks [T][5][112][112].
 //   * glf_overlap_counts_nchw: tp / fp / fn / tn of sigmoid(logit) > 0.5 against the mask PER CLASS CHANNEL
 //     (main.py:537-543 slices the accumulated predictions per part), int64, one pass over [N][C][HW].
+//   * glf_render_labels / glf_restore_labels: the visual mode (main.py:546-648).  Label map = argmax over [0.5, on_0 .. on_{C-1}]
+//     (main.py:606-612), coloured through a palette (main.py:623-634) with an optional integer blend over the grey frame, and the
+//     way back from the 112 x 112 crop to the source volume's geometry (the inverse of glf_prepare_frames), [H0][W0][T] uint8.
 // HBM-bound byte / index work: one thread per output pixel, coalesced along x.
 #include "glf_common.h"
+#include <cstdint>
 
 namespace {
 
 __device__ __forceinline__ float sigmoid_d(float x) { return 1.0f / (1.0f + expf(-x)); }
+// THE binarisation of a logit (main.py:250, 385, 606): metrics, label maps and restored volumes all decide a pixel here
+__device__ __forceinline__ bool channel_on(float x) { return sigmoid_d(x) > 0.5f; }
 
 // nearest-neighbour source index exactly as ATen's upsample_nearest (legacy 'nearest'): floor(dst * (in / out)) in
 // fp32, clamped to in - 1
@@ -52,7 +58,7 @@ __global__ __launch_bounds__(256) void overlap_nchw_kernel(const float* __restri
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < per; i += (long long)gridDim.x * blockDim.x) {
         const long long n = i / hw, p = i - n * hw;
         const long long o = (n * C + c) * hw + p;
-        const bool pr = sigmoid_d(x[o]) > 0.5f;               // main.py:250, 385
+        const bool pr = channel_on(x[o]);                     // main.py:250, 385
         const bool gt = t[o] != 0.f;
         tp += pr && gt; fp += pr && !gt; fn += !pr && gt; tn += !pr && !gt;
     }
@@ -63,6 +69,85 @@ __global__ __launch_bounds__(256) void overlap_nchw_kernel(const float* __restri
     if ((threadIdx.x & 63) == 0) {
         unsigned long long* k = counts + 4 * c;
         atomicAdd(k + 0, tp); atomicAdd(k + 1, fp); atomicAdd(k + 2, fn); atomicAdd(k + 3, tn);
+    }
+}
+
+constexpr int kMaxClasses = 8;                      // channels of a rendered / restored prediction (the model's C is 5)
+struct Palette { uint32_t rgba[kMaxClasses + 1]; };  // r | g << 8 | b << 16 | a << 24 per label: the byte order of the store
+struct ClassTable { uint8_t cls[kMaxClasses]; };     // channel -> class id, 0 = not shown by this view
+
+// (alpha * colour + (255 - alpha) * grey + 127) / 255 on each of r, g, b; the alpha byte becomes 255
+__device__ __forceinline__ uint32_t blend_rgba(uint32_t colour, int grey, int alpha) {
+    uint32_t out = 0xff000000u;
+#pragma unroll
+    for (int k = 0; k < 24; k += 8) out |= (uint32_t)((alpha * (int)((colour >> k) & 0xffu) + (255 - alpha) * grey + 127) / 255) << k;
+    return out;
+}
+
+// logits [N][C][hw]; frames [N][hw] or null; labels [N][hw] or null; rgba [N][hw] packed pixels or null.  One thread per pixel:
+// the C plane reads, the byte store and the 32-bit store are all coalesced along x
+__global__ __launch_bounds__(256) void render_labels_kernel(const float* __restrict__ logits, const float* __restrict__ frames,
+                                                            uint8_t* __restrict__ labels, uint32_t* __restrict__ rgba, long long total,
+                                                            int C, long long hw, Palette pal, int alpha) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long n = i / hw, p = i - n * hw;
+        const float* x = logits + n * C * hw + p;
+        int label = 0;
+        for (int c = C - 1; c >= 0; --c)
+            if (channel_on(x[c * hw])) label = c + 1;         // the first maximum of [0.5, on_0, ...]: the lowest channel that is on
+        if (labels) labels[i] = (uint8_t)label;
+        if (rgba) {
+            uint32_t px = pal.rgba[label];
+            if (frames) {
+                // individually rounded (no fma): the grey level is the same on any host that restates it
+                const float g = __fadd_rn(__fmul_rn(frames[i], 255.0f), 0.5f);
+                const int grey = g >= 1.0f ? (g >= 255.0f ? 255 : (int)g) : 0;                  // NaN -> 0
+                px = label ? blend_rgba(px, grey, alpha) : (0xff000000u | (uint32_t)grey * 0x010101u);
+            }
+            rgba[i] = px;
+        }
+    }
+}
+
+constexpr int kRestoreX = 64, kRestoreT = 64;       // one tile: 64 source pixels of one row x 64 frames
+
+// logits [T][C][oh][ow] -> vol [H0][W0][T].  The reads run along x, the store along t, so a tile goes through LDS: a wave
+// classifies 64 consecutive x0 of one frame (coalesced plane reads, up to the repeats / strides of the nearest mapping), then
+// the block writes the tile's bytes in address order -- per x0 a run of up to 64 frames, the whole tile one run when T <= 64.
+__global__ __launch_bounds__(256) void restore_labels_kernel(const float* __restrict__ logits, uint8_t* __restrict__ vol, int T, int C,
+                                                             int oh, int ow, int H0, int W0, int rs, int oy, int ox, ClassTable tab,
+                                                             long long tiles, int xtiles, int ttiles) {
+    __shared__ uint8_t tile[kRestoreX][kRestoreT + 1];
+    const float sy = (float)rs / (float)H0, sx = (float)rs / (float)W0;
+    const long long plane = (long long)oh * ow;
+    for (long long b = blockIdx.x; b < tiles; b += gridDim.x) {
+        const int tt = (int)(b % ttiles), xt = (int)((b / ttiles) % xtiles), y0 = (int)(b / ((long long)ttiles * xtiles));
+        const int t0 = tt * kRestoreT, x00 = xt * kRestoreX;
+        const int nt = T - t0 < kRestoreT ? T - t0 : kRestoreT, nx = W0 - x00 < kRestoreX ? W0 - x00 : kRestoreX;
+        const int xl = threadIdx.x & (kRestoreX - 1);
+        const int y = nearest_src(y0, sy, rs) - oy;
+        const int x = xl < nx ? nearest_src(x00 + xl, sx, rs) - ox : -1;
+        const bool inside = y >= 0 && y < oh && x >= 0 && x < ow;
+        for (int tl = threadIdx.x / kRestoreX; tl < nt; tl += 256 / kRestoreX) {
+            int cls = 0;
+            if (inside) {
+                const float* src = logits + (long long)(t0 + tl) * C * plane + (long long)y * ow + x;
+                float best = 0.f;
+                for (int c = 0; c < C; ++c) {
+                    if (tab.cls[c] == 0) continue;               // uniform over the grid: a channel this view does not show is not read
+                    const float v = src[c * plane];
+                    if (channel_on(v) && (cls == 0 || v > best)) { cls = tab.cls[c]; best = v; }
+                }
+            }
+            tile[xl][tl] = (uint8_t)cls;
+        }
+        __syncthreads();
+        uint8_t* dst = vol + ((long long)y0 * W0 + x00) * T + t0;
+        for (int j = threadIdx.x; j < nx * nt; j += 256) {
+            const int xj = j / nt, tj = j - xj * nt;
+            dst[(long long)xj * T + tj] = tile[xj][tj];
+        }
+        __syncthreads();
     }
 }
 
@@ -105,4 +190,52 @@ extern "C" int glf_overlap_counts_nchw(const float* logits, const float* target,
     hipLaunchKernelGGL(overlap_nchw_kernel, dim3((unsigned)blocks, c), dim3(256), 0, glf::S(s), logits, target,
                        reinterpret_cast<unsigned long long*>(counts), n, c, (long long)hw);
     return glf::check_launch("overlap_counts_nchw");
+}
+
+extern "C" int glf_render_labels(const float* logits, const float* frames, uint8_t* labels, uint8_t* rgba, int n, int c, int h, int w,
+                                 const uint8_t* palette, int alpha, glf_stream_t s) {
+    GLF_REQUIRE(logits != nullptr, GLF_ERR_NULL, "render_labels: null logits");
+    GLF_REQUIRE(labels != nullptr || rgba != nullptr, GLF_ERR_NULL, "render_labels: nothing to do (labels and rgba both null)");
+    GLF_REQUIRE(rgba == nullptr || palette != nullptr, GLF_ERR_NULL, "render_labels: null palette ((c + 1) x 4 host bytes)");
+    GLF_REQUIRE(n > 0 && c > 0 && h > 0 && w > 0, GLF_ERR_BAD_SHAPE, "render_labels: n, c, h, w must be > 0 (got %d, %d, %d, %d)", n, c, h, w);
+    GLF_REQUIRE(c <= kMaxClasses, GLF_ERR_BAD_SHAPE, "render_labels: c = %d channels, at most %d", c, kMaxClasses);
+    GLF_REQUIRE(alpha >= 0 && alpha <= 255, GLF_ERR_BAD_SHAPE, "render_labels: alpha = %d is outside 0..255", alpha);
+    GLF_REQUIRE((reinterpret_cast<uintptr_t>(rgba) & 3u) == 0, GLF_ERR_BAD_SHAPE, "render_labels: rgba must be 4-byte aligned");
+    Palette pal = {};
+    if (rgba)
+        for (int k = 0; k <= c; ++k)
+            pal.rgba[k] = (uint32_t)palette[4 * k] | (uint32_t)palette[4 * k + 1] << 8 | (uint32_t)palette[4 * k + 2] << 16 |
+                          (uint32_t)palette[4 * k + 3] << 24;
+    if (int rc = glf::ensure_init()) return rc;
+    const long long hw = (long long)h * w, total = hw * n;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(render_labels_kernel, dim3((unsigned)blocks), dim3(256), 0, glf::S(s), logits, frames, labels,
+                       reinterpret_cast<uint32_t*>(rgba), total, c, hw, pal, alpha);
+    return glf::check_launch("render_labels");
+}
+
+extern "C" int glf_restore_labels(const float* logits, uint8_t* volume, int T, int c, int out_h, int out_w, int H0, int W0, int resize,
+                                  int off_y, int off_x, const int* channel_to_class, glf_stream_t s) {
+    GLF_REQUIRE(logits != nullptr, GLF_ERR_NULL, "restore_labels: null logits");
+    GLF_REQUIRE(volume != nullptr, GLF_ERR_NULL, "restore_labels: null volume");
+    GLF_REQUIRE(channel_to_class != nullptr, GLF_ERR_NULL, "restore_labels: null channel_to_class (c host ints: class of each channel, 0 = none)");
+    GLF_REQUIRE(T > 0 && c > 0 && out_h > 0 && out_w > 0 && H0 > 0 && W0 > 0 && resize > 0, GLF_ERR_BAD_SHAPE,
+                "restore_labels: sizes must be > 0");
+    GLF_REQUIRE(c <= kMaxClasses, GLF_ERR_BAD_SHAPE, "restore_labels: c = %d channels, at most %d", c, kMaxClasses);
+    ClassTable tab = {};
+    for (int k = 0; k < c; ++k) {
+        GLF_REQUIRE(channel_to_class[k] >= 0 && channel_to_class[k] <= 255, GLF_ERR_BAD_SHAPE,
+                    "restore_labels: channel_to_class[%d] = %d is outside 0..255", k, channel_to_class[k]);
+        tab.cls[k] = (uint8_t)channel_to_class[k];
+    }
+    GLF_REQUIRE(off_y >= 0 && off_x >= 0 && off_y <= resize - out_h && off_x <= resize - out_w, GLF_ERR_BAD_SHAPE,
+                "restore_labels: crop window [%d+%d, %d+%d] leaves the %d x %d resized image", off_y, out_h, off_x, out_w, resize, resize);
+    if (int rc = glf::ensure_init()) return rc;
+    const int xtiles = (W0 + kRestoreX - 1) / kRestoreX, ttiles = (T + kRestoreT - 1) / kRestoreT;
+    const long long tiles = (long long)H0 * xtiles * ttiles;
+    const long long blocks = tiles < 8192 ? tiles : 8192;
+    hipLaunchKernelGGL(restore_labels_kernel, dim3((unsigned)blocks), dim3(256), 0, glf::S(s), logits, volume, T, c, out_h, out_w, H0, W0,
+                       resize, off_y, off_x, tab, tiles, xtiles, ttiles);
+    return glf::check_launch("restore_labels");
 }

@@ -8,6 +8,8 @@ input layout directly: frames [T,1,112,112] and masks [T,5,112,112] -- the `[1,1
 of main.py:361-365 / 495-499 included.  NIfTI files themselves are not shipped with the reference (absolute paths on the
 authors' machine); `SyntheticPatients` produces volumes with the same tensor contract.
 (The RandFlipd objects of loader.py:468-474 are constructed but never put into the Compose: no flip is applied.)
+The way out is here too: `render_labels` (the label maps and colours of main.py:606-634) and `restore_labels` (predictions back in the
+source volume's geometry, the inverse of `prepare_frames`), the two kernels of Trainer.test_visualize.
 """
 from __future__ import annotations
 
@@ -28,6 +30,12 @@ CLASS_TO_CHANNEL: Dict[str, Tuple[int, int, int, int]] = {
     "4": (3, 2, 0, 1),          # apical four chamber: LV -> 3, LA -> 2, RA -> 0, RV -> 1
 }
 RESIZE, CROP = 144, 112         # loader.py:462-463
+# the way back: class id (0 = this view does not show the channel) of each of the 5 mask channels, per view
+CHANNEL_TO_CLASS: Dict[str, Tuple[int, ...]] = {
+    v: tuple(table.index(ch) + 1 if ch in table else 0 for ch in range(5)) for v, table in CLASS_TO_CHANNEL.items()}
+# colour of label 0 (background) and labels 1..5 (1 + class channel), r, g, b, a: main.py:623-634
+PALETTE: Tuple[Tuple[int, int, int, int], ...] = (
+    (0, 0, 0, 255), (55, 255, 254, 255), (27, 255, 46, 255), (45, 0, 251, 255), (251, 13, 15, 255), (223, 48, 236, 255))
 
 
 def prepare_frames(images: Optional[torch.Tensor], labels: Optional[torch.Tensor], view: str, train: bool = False,
@@ -80,6 +88,53 @@ def part_overlap_counts(logits: torch.Tensor, target: torch.Tensor) -> torch.Ten
     counts = torch.empty(c, 4, dtype=torch.int64, device=logits.device)
     check(lib.glf_overlap_counts_nchw(_p(logits), _p(target), _p(counts), n, c, h * w, _stream()), "overlap_counts_nchw")
     return counts
+
+
+def render_labels(logits: torch.Tensor, frames: Optional[torch.Tensor] = None, alpha: int = 255, palette=PALETTE):
+    """The pictures of main.py:606-634 in one kernel (glf_render_labels).  logits [N,C,H,W] (C = 1..8, float32: predictions are
+    fp32 under every precision; a 0/1 mask renders to the reference's `visual_gnd`) -> (labels uint8 [N,H,W], rgba uint8
+    [N,H,W,4]).  label = argmax over [0.5, on_0, .., on_{C-1}], first maximum: 0 = no channel on, else 1 + the lowest channel
+    with sigmoid(logit) > 0.5 -- the predicate part_overlap_counts counts with.  rgba = palette[label] (C + 1 rows r, g, b, a).
+    With `frames` [N,1,H,W] in [0,1] the colours are laid over the grey frame instead (not in the reference): integer alpha
+    0..255, (alpha * colour + (255 - alpha) * grey + 127) // 255 where label != 0, the grey level elsewhere, opaque."""
+    logits = _contig(_chk(logits, "logits"))
+    if logits.dim() != 4:
+        raise RuntimeError("render_labels: [N,C,H,W] logits expected")
+    n, c, h, w = logits.shape
+    pal = [int(x) for row in palette for x in row]
+    if len(pal) != 4 * (c + 1) or any(len(row) != 4 for row in palette) or not all(0 <= x <= 255 for x in pal):
+        raise ValueError(f"render_labels: the palette needs {c + 1} rows of 4 bytes (label 0 and one per channel)")
+    if int(alpha) != alpha:
+        raise ValueError("render_labels: alpha is an integer 0..255")
+    if frames is not None:
+        frames = _contig(_chk(frames, "frames"))
+        if frames.numel() != n * h * w or tuple(frames.shape[-2:]) != (h, w):
+            raise RuntimeError("render_labels: frames [N,1,H,W] must match the logits")
+    labels = torch.empty(n, h, w, dtype=torch.uint8, device=logits.device)
+    rgba = torch.empty(n, h, w, 4, dtype=torch.uint8, device=logits.device)
+    check(lib.glf_render_labels(_p(logits), _p(frames), _p(labels), _p(rgba), n, c, h, w, (C.c_uint8 * len(pal))(*pal), int(alpha),
+                                _stream()), "render_labels")
+    return labels, rgba
+
+
+def restore_labels(logits: torch.Tensor, view: str, shape: Sequence[int], crop_offset: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """The inverse geometry of prepare_frames (glf_restore_labels; no reference counterpart): logits [T,C,112,112] of `view`
+    -> class-id volume uint8 [H0,W0,T] with (H0, W0) = shape[:2], the source volume's geometry and axis order, ready for
+    nifti.write next to the file the clip came from.  A source pixel takes the class of its nearest pixel of the 144 x 144
+    resized image (0 outside the crop window; `crop_offset` None = the centre crop): among the channels that are on and that
+    the view shows (CHANNEL_TO_CLASS), the one with the largest logit, the lowest channel on a tie; 0 when there is none."""
+    if view not in CHANNEL_TO_CLASS:
+        raise KeyError(f"glfusion_amd.data: no part table for view {view!r} (loader.py:298-316 defines views 1-4)")
+    logits = _contig(_chk(logits, "logits"))
+    if logits.dim() != 4 or logits.shape[1] != len(CHANNEL_TO_CLASS[view]):
+        raise RuntimeError(f"restore_labels: [T,{len(CHANNEL_TO_CLASS[view])},H,W] logits expected")
+    t, c, oh, ow = logits.shape
+    h0, w0 = int(shape[0]), int(shape[1])
+    oy, ox = ((RESIZE - oh) // 2, (RESIZE - ow) // 2) if crop_offset is None else (int(crop_offset[0]), int(crop_offset[1]))
+    volume = torch.empty(h0, w0, t, dtype=torch.uint8, device=logits.device)
+    table = (C.c_int * c)(*CHANNEL_TO_CLASS[view])
+    check(lib.glf_restore_labels(_p(logits), _p(volume), t, c, oh, ow, h0, w0, RESIZE, oy, ox, table, _stream()), "restore_labels")
+    return volume
 
 
 class SyntheticPatients:

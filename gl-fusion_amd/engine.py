@@ -1,6 +1,6 @@
 """Caller-side harness with the reference Trainer's surface (main.py:63-883) for the hot path:
 `Trainer(config)`, `.train(is_backbone, is_cycle)`, `.eval(net_path, is_fuse, raw_data)`,
-`_calculate_overlap_metrics`, `save()`, `load()`.  The reference's data layer needs NIfTI files that are not
+`.test_visualize(method_name, net_path)`, `_calculate_overlap_metrics`, `save()`, `load()`.  The reference's data layer needs NIfTI files that are not
 shipped (absolute paths on the authors' machine), so loaders here produce synthetic clips with
 the reference's tensor contract: images [N,1,112,112] in [0,1], masks [N,5,112,112] in {0,1}
 (datasets/loader.py:298-330); the unlabelled "video" loader of the cycle term yields clips of `clip_length`
@@ -347,6 +347,64 @@ class Trainer:
                       f"precision {result[v][2]:.4f} specificity {result[v][3]:.4f} recall {result[v][4]:.4f}; part dice "
                       + " ".join(f"{d:.4f}" for d in part_dice[v]))
         return result
+
+    @torch.no_grad()
+    @_fold_bn_scope
+    def test_visualize(self, method_name: str, net_path: str = None, out_root: str = "./visualze_for_ppt", patients=None,
+                       is_fuse: bool = True, overlay_alpha=96, nifti: bool = True, on_clip=None):
+        """main.py:546-648.  The data path of eval(): `patients` yields {view: (image volume, label volume)} (default: the
+        synthetic patients eval() scores), patient k has the id '0_<k>', every clip goes through data.prepare_frames(train=False)
+        and the model in eval mode (the fused mask, or the backbone mask when is_fuse is False).  Per patient and view of
+        `test_view`, under <out_root>/<method_name>/192_data/<id>/<view>/ (the reference's directory and file name): pred_<frame>.png,
+        the label map of main.py:606-609 in the colours of main.py:623-634; gnd_<frame>.png, the same rendering of the masks (the
+        `visual_gnd` the reference computes and never saves); overlay_<frame>.png, the prediction laid over the grey frame with
+        opacity overlay_alpha / 255 (None: not written; not in the reference).  With `nifti`, <out_root>/<method_name>/nifti/<id>/
+        view<view>_pred.nii.gz holds the predicted class ids uint8 [H0,W0,T] in the geometry of the source volume
+        (data.restore_labels), to be opened next to it.  The pictures are the model's own H x W pixels, one per prediction: the
+        reference's dpi-600 matplotlib upscaling is not reproduced.  Rendering, colouring, blending and the back-projection are
+        kernels; each output crosses to the host once per (patient, view).  on_clip(patient_id, view, logits, masks), if given,
+        sees the device tensors of each (patient, view) before they are rendered.  Only the printing rank runs the pass; there is
+        no collective in it.  Returns (and keeps as `self.visual_report`) {id: {view: {'png_dir', 'nifti' (path or None), 'frames'}}}."""
+        from . import data as _data
+        from . import nifti as _nifti
+        from . import png as _png
+        self.visual_report = manifest = {}
+        if not self.print_val:
+            return manifest
+        if net_path and os.path.exists(net_path):
+            self.model.load_state_dict(torch.load(net_path, map_location=self.device)["network"], strict=True)
+        self.model.eval()
+        if patients is None:
+            patients = _data.SyntheticPatients(self.view_num, int(self.config["train"].get("eval_patients", 2)),
+                                               int(self.config["train"].get("clip_length", 40)), device=self.device, seed=77)
+        root = os.path.join(out_root, method_name)
+        for k, sample in enumerate(patients):
+            pid = f"0_{k}"
+            imgs, masks = {}, {}
+            for v in self.view_num:
+                imgs[v], masks[v] = _data.prepare_frames(sample[v][0], sample[v][1], v, train=False)
+            out = self.model(imgs)
+            pred = out[0] if is_fuse else out[1]
+            manifest[pid] = {}
+            for v in self.test_view:
+                if on_clip is not None:
+                    on_clip(pid, v, pred[v], masks[v])
+                pictures = {"pred": _data.render_labels(pred[v])[1], "gnd": _data.render_labels(masks[v])[1]}
+                if overlay_alpha is not None:
+                    pictures["overlay"] = _data.render_labels(pred[v], frames=imgs[v], alpha=overlay_alpha)[1]
+                png_dir = os.path.join(root, "192_data", pid, v)
+                os.makedirs(png_dir, exist_ok=True)
+                for kind, rgba in pictures.items():
+                    for frame_i, picture in enumerate(rgba.cpu().numpy()):       # one copy per (patient, view) and output
+                        _png.write_rgba(os.path.join(png_dir, f"{kind}_{frame_i}.png"), picture)
+                nii = None
+                if nifti:
+                    os.makedirs(os.path.join(root, "nifti", pid), exist_ok=True)
+                    nii = os.path.join(root, "nifti", pid, f"view{v}_pred.nii.gz")
+                    _nifti.write(nii, _data.restore_labels(pred[v], v, sample[v][0].shape).cpu().numpy())
+                manifest[pid][v] = {"png_dir": png_dir, "nifti": nii, "frames": int(pred[v].shape[0])}
+            print(f"patient {pid} pred finished")                                 # main.py:648
+        return manifest
 
     @torch.no_grad()
     @_fold_bn_scope

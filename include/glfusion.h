@@ -919,6 +919,33 @@ int glf_prepare_frames(const float* img, const float* lab, float* out_img, float
                        int resize, int out_h, int out_w, int off_y, int off_x, const int* class_to_channel, float img_div,
                        glf_stream_t s);
 int glf_overlap_counts_nchw(const float* logits, const float* target, int64_t* counts, int n, int c, int64_t hw, glf_stream_t s);
+/* ---------------------------------------------------------------------------------------
+ * Visual mode (Trainer.test_visualize, main.py:546-648): predictions as label maps, pictures and volumes.
+ * A channel is ON when sigmoid(logit) > 0.5, by the device predicate glf_overlap_counts_nchw counts with: logit 0.0, -0.0,
+ * -inf and NaN are off, +inf is on.
+ * glf_render_labels: logits [n][c][h][w] (c = 1..8) -> labels [n][h][w] (uint8) = argmax over [0.5, on_0, .., on_{c-1}], the
+ * first maximum winning (main.py:606-612): 0 when no channel is on, else 1 + the lowest channel that is on; and
+ * rgba [n][h][w][4] (uint8, 4-byte aligned, one 32-bit store per pixel) = palette[label], palette = (c + 1) x 4 HOST bytes
+ * (r, g, b, a per label).  Either output may be NULL, not both; palette may be NULL when rgba is.
+ * frames [n][1][h][w] (fp32 in [0, 1], may be NULL) adds the overlay, which the reference does not have: with the grey level
+ * G = clamp((int)(v * 255.0f + 0.5f), 0, 255) (product and sum individually rounded; NaN -> 0) every colour byte becomes
+ * (alpha * colour + (255 - alpha) * G + 127) / 255 in integer arithmetic where label != 0 and G where label == 0; the alpha
+ * byte becomes 255.  alpha = 0..255 (checked with or without frames).
+ * glf_restore_labels: the inverse geometry of glf_prepare_frames.  logits [T][c][out_h][out_w] -> volume [H0][W0][T] (uint8,
+ * T fastest: the order of the NIfTI volume the clip was cut from).  Source pixel (y0, x0) looks up the resized pixel
+ * yr = min(floor(y0 * ((float)resize / (float)H0)), resize - 1), xr likewise (ATen's legacy 'nearest' from resize x resize up
+ * or down to H0 x W0); outside the crop window [off_y, off_y + out_h) x [off_x, off_x + out_w) the voxel is 0; inside it is
+ * channel_to_class[ch] of the channel ch with the largest logit among those that are on AND have channel_to_class[ch] != 0
+ * (ties: the lowest channel), 0 when there is none.  channel_to_class: c HOST ints 0..255, 0 = this view does not show that
+ * channel.
+ * Both check their arguments before any HIP runtime call, in this order: GLF_ERR_NULL (logits, both outputs / volume, palette /
+ * table; a null pointer wins over every other error), then GLF_ERR_BAD_SHAPE (n, c, h, w, T, H0, W0, resize < 1, c > 8, alpha or a
+ * table entry outside 0..255, a crop window that leaves the resized image, rgba not 4-byte aligned).
+ * ------------------------------------------------------------------------------------- */
+int glf_render_labels(const float* logits, const float* frames, uint8_t* labels, uint8_t* rgba, int n, int c, int h, int w,
+                      const uint8_t* palette, int alpha, glf_stream_t s);
+int glf_restore_labels(const float* logits, uint8_t* volume, int T, int c, int out_h, int out_w, int H0, int W0, int resize,
+                       int off_y, int off_x, const int* channel_to_class, glf_stream_t s);
 /* Zero `bytes` bytes at p on the stream (accumulation targets: atomically summed gradients, column statistics, maxima). */
 int glf_zero(void* p, int64_t bytes, glf_stream_t s);
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Entry point with the reference's surface (GLfusion/main.py:885-965): the same `config` dict keys, `--mode
-{train,val}`, `main(rank, config)`, `Trainer(config)` -- running the MI355X HIP engine on synthetic clips (the
+{train,val,visual}`, `main(rank, config)`, `Trainer(config)` -- running the MI355X HIP engine on synthetic clips (the
 reference's data files are not shipped).  Multi-GPU: `python -m torch.distributed.run --nproc-per-node N main.py
 --mode train` (one process per GPU, RCCL gradient all-reduce) instead of the reference's nn.DataParallel."""
 from __future__ import annotations
@@ -54,8 +54,10 @@ def main(rank, config):
         trainer.train(is_backbone=False, is_cycle=True)
     elif args.mode == "val":
         print(trainer.eval(net_path="./path/to/ckpt", is_fuse=True, raw_data=True))
+    elif args.mode == "visual":
+        trainer.test_visualize("glfusion_amd")
     else:
-        raise SystemExit("--mode visual (matplotlib dumps, main.py:546-648) is out of scope of the hot path")
+        raise SystemExit(f"--mode {args.mode}: unknown mode; the valid modes are train, val and visual")
 
 
 if __name__ == "__main__":
