@@ -1006,7 +1006,7 @@ extern "C" int glf_maxpool3x3s2_bwd(const float* dy, const uint8_t* idx, float* 
     if (int rc = glf::ensure_init()) return rc;
     GLF_REQUIRE(dy && idx && dx, GLF_ERR_NULL, "maxpool_bwd: null argument");
     GLF_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0 && (c % 4) == 0, GLF_ERR_BAD_SHAPE, "maxpool_bwd: bad shape (C %% 4 == 0 required)");
-    GLF_REQUIRE(al16(dy) && al16(dx), GLF_ERR_BAD_SHAPE, "maxpool_bwd: alignment");
+    GLF_REQUIRE(al16(dy) && al16(dx) && ((reinterpret_cast<uintptr_t>(idx) & 3u) == 0), GLF_ERR_BAD_SHAPE, "maxpool_bwd: alignment");
     return launch_maxpool_bwd<float, 4>(dy, idx, dx, n, h, w, c, glf::S(s), "maxpool_bwd");
 }
 extern "C" int glf_s16_maxpool3x3s2_fwd(const void* x, void* y, uint8_t* idx, int n, int h, int w, int c, glf_stream_t s) {
@@ -1014,6 +1014,7 @@ extern "C" int glf_s16_maxpool3x3s2_fwd(const void* x, void* y, uint8_t* idx, in
     GLF_REQUIRE(x && y && idx, GLF_ERR_NULL, "s16_maxpool_fwd: null argument");
     GLF_REQUIRE(n > 0 && h > 0 && w > 0, GLF_ERR_BAD_SHAPE, "s16_maxpool_fwd: bad extents");
     REQ_C8(c); REQ_AL(x, "x"); REQ_AL(y, "y");
+    GLF_REQUIRE((reinterpret_cast<uintptr_t>(idx) & 7u) == 0, GLF_ERR_BAD_SHAPE, "s16_maxpool_fwd: idx must be 8-byte aligned");
     return launch_maxpool_fwd<u16, 8>(x, y, idx, n, h, w, c, glf::S(s), "s16_maxpool_fwd");
 }
 extern "C" int glf_s16_maxpool3x3s2_bwd(const void* dy, const uint8_t* idx, void* dx, int n, int h, int w, int c, glf_stream_t s) {
@@ -1021,6 +1022,7 @@ extern "C" int glf_s16_maxpool3x3s2_bwd(const void* dy, const uint8_t* idx, void
     GLF_REQUIRE(dy && dx && idx, GLF_ERR_NULL, "s16_maxpool_bwd: null argument");
     GLF_REQUIRE(n > 0 && h > 0 && w > 0, GLF_ERR_BAD_SHAPE, "s16_maxpool_bwd: bad extents");
     REQ_C8(c); REQ_AL(dy, "dy"); REQ_AL(dx, "dx");
+    GLF_REQUIRE((reinterpret_cast<uintptr_t>(idx) & 7u) == 0, GLF_ERR_BAD_SHAPE, "s16_maxpool_bwd: idx must be 8-byte aligned");
     return launch_maxpool_bwd<u16, 8>(dy, idx, dx, n, h, w, c, glf::S(s), "s16_maxpool_bwd");
 }
 

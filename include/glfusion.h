@@ -730,7 +730,8 @@ int glf_bn_bwd(const float* dy, int lddy, const float* x, int ldx, const float* 
  * Pooling / resampling / pointwise pieces of the path.
  * ------------------------------------------------------------------------------------- */
 /* nn.MaxPool2d(3, stride 2, pad 1) on [N][H][W][C] -> [N][Ho][Wo][C]; idx (uint8, same shape as
- * y) records the winning tap (first maximum in scan order, as ATen). */
+ * y) records the winning tap (first maximum in scan order, as ATen).  idx is accessed one pixel's channel group at a time: 4-byte
+ * aligned here, 8-byte aligned for the glf_s16_* pair (forward and backward refuse anything else). */
 int glf_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* idx, int n, int h, int w, int c, glf_stream_t s);
 int glf_maxpool3x3s2_bwd(const float* dy, const uint8_t* idx, float* dx, int n, int h, int w, int c, glf_stream_t s);
 /* AdaptiveAvgPool2d(1) (deeplabv3.py:126): x [N][P][C] -> y [N][C], and its backward. */
