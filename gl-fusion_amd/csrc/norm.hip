@@ -1,20 +1,23 @@
-// Normalisation kernels of the GL-Fusion path (HBM-bound; channels-last [rows][C], C % 4 == 0).
+// Normalisation kernels of the GL-Fusion path for BOTH storages (HBM-bound; channels-last [rows][C]; fp32 storage: C % 4 == 0,
+// bf16 storage -- the glf_s16_* entry points -- C % 8 == 0: 16-byte accesses either way, fp32 arithmetic, bf16 rounded once at the store).
 //   * column reductions (BatchNorm statistics, BatchNorm / LayerNorm / bias gradients) share one
 //     two-stage scheme: stage 1 streams a slice of rows per workgroup with 16-byte loads and
 //     accumulates in f64 (sum / sum-of-squares cancellation-free), stage 2 folds the per-slice
 //     partials per channel.  No atomics => bitwise reproducible.
+//   * the single-stage reductions (one f64 atomic per column and workgroup: BatchNorm backward of both storages, statistics and
+//     column sum of bf16 storage) and the statistics finish are written once for both storages (col_reduce.h, bn_finish).
 //   * BatchNorm apply (+residual, +ReLU) and the backward apply are single streaming passes.
 //   * the TPAVI tail z = LayerNorm_C(BN(W_z y) + x) runs one wavefront per row with shuffle
 //     reductions only (no LDS, no barrier); its backward with every column sum that follows from du is one walk in which a
 //     workgroup owns a slab of rows and each wave a quarter of the channels (bn_res_ln_bwd_sums_kernel).
-#include "stream_common.h"
+#include "col_reduce.h"
 #include "split_f16.h"
 
 using namespace glf;
 
 namespace {
 
-constexpr int RT = 256;               // threads of a reduction workgroup
+constexpr int RT = RED_THREADS;       // threads of a reduction workgroup
 constexpr int MAX_SLICES = 1024;
 
 // row slices of the stage-1 grid: enough workgroups to stream at the HBM rate (grid = slices x channel blocks of
@@ -45,15 +48,34 @@ struct OpColsum {         // (dy, 0)
         b = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 };
+struct OpStats16 {        // bf16 storage: (x, x^2)
+    const u16* x; int ldx;
+    __device__ void operator()(int r, int c, F8& a, F8& b) const {
+        a = ld8(x + (long long)r * ldx + c);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b.v[j] = a.v[j] * a.v[j];
+    }
+};
+struct OpColsum16 {       // bf16 storage: (dy, 0)
+    const u16* dy; int ld;
+    __device__ void operator()(int r, int c, F8& a, F8& b) const {
+        a = ld8(dy + (long long)r * ld + c);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b.v[j] = 0.f;
+    }
+};
 // the forward value of one element; ONE definition so that the ReLU mask recomputed in backward (y == NULL) is the
 // mask the forward applied
 __device__ __forceinline__ float bn_val(float x, float mu, float is, float ga, float be) { return (x - mu) * is * ga + be; }
 
-struct OpBnBwd {          // (dy', dy' * xhat), dy' = dy * (y > 0) when relu; y == NULL: the mask is recomputed from x
-    const float* dy; int lddy; const float* x; int ldx; const float* y; int ldy;
+// operands of a BatchNorm-backward reduction over storage type T, W = 16 / sizeof(T) elements per access
+template <class T> struct BnBwdIn {
+    const T* dy; int lddy; const T* x; int ldx; const T* y; int ldy;
     const float* mean; const float* invstd; const float* gamma; const float* beta; int relu;
-    const unsigned char* mask; int c4;          // relu with a residual: the forward's sign bits, one byte per float4 (instead of y)
-    const float* dy2; int lddy2;                // second addend of the incoming gradient (a fan-in not yet summed), or null
+    const unsigned char* mask; int cw;          // relu with a residual: the forward's sign bits, one byte per access (instead of y)
+    const T* dy2; int lddy2;                    // second addend of the incoming gradient (a fan-in not yet summed), or null
+};
+struct OpBnBwd : BnBwdIn<float> {   // (dy', dy' * xhat), dy' = dy * (y > 0) when relu; y == NULL: the mask is recomputed from x
     __device__ void operator()(int r, int c, float4& a, float4& b) const {
         a = *reinterpret_cast<const float4*>(dy + (long long)r * lddy + c);
         if (dy2) {
@@ -64,7 +86,7 @@ struct OpBnBwd {          // (dy', dy' * xhat), dy' = dy * (y > 0) when relu; y 
         const float4 mu = *reinterpret_cast<const float4*>(mean + c);
         const float4 is = *reinterpret_cast<const float4*>(invstd + c);
         if (relu && mask) {
-            const unsigned m = mask[(long long)r * c4 + (c >> 2)];
+            const unsigned m = mask[(long long)r * cw + (c >> 2)];
             a.x = (m & 1u) ? a.x : 0.f; a.y = (m & 2u) ? a.y : 0.f; a.z = (m & 4u) ? a.z : 0.f; a.w = (m & 8u) ? a.w : 0.f;
         } else if (relu) {
             float4 yy;
@@ -104,225 +126,200 @@ struct OpLnParam {        // (dz * uhat, dz) with u = BN(w) + x and per-row Laye
 };
 
 // stage 1: partial[0][slice][c], partial[1][slice][c]
-template <class Op>
-__global__ __launch_bounds__(RT) void colreduce_kernel(Op op, int rows, int c, int slices, double* __restrict__ partial) {
-    __shared__ double sh_a[RT * 4];
-    __shared__ double sh_b[RT * 4];
-    const int tid = threadIdx.x;
-    const int c4 = c >> 2;
-    const int tpr = c4 < RT ? c4 : RT;            // threads per row
-    const int rpp = RT / tpr;                     // rows per pass
-    const int ct = tid % tpr, rl = tid / tpr;
-    const int slice = blockIdx.x;
-    const int per = (rows + slices - 1) / slices;
-    const int r0 = slice * per, r1 = min(rows, r0 + per);
-    for (int cb = blockIdx.y * tpr; cb < c4; cb += gridDim.y * tpr) {
-        const int cc = cb + ct;
-        double a0 = 0, a1 = 0, a2 = 0, a3 = 0, b0 = 0, b1 = 0, b2 = 0, b3 = 0;
-        if (cc < c4 && rl < rpp) {
-            for (int r = r0 + rl; r < r1; r += rpp) {
-                float4 a, b;
-                op(r, cc * 4, a, b);
-                a0 += a.x; a1 += a.y; a2 += a.z; a3 += a.w;
-                b0 += b.x; b1 += b.y; b2 += b.z; b3 += b.w;
-            }
-        }
-        sh_a[tid * 4 + 0] = a0; sh_a[tid * 4 + 1] = a1; sh_a[tid * 4 + 2] = a2; sh_a[tid * 4 + 3] = a3;
-        sh_b[tid * 4 + 0] = b0; sh_b[tid * 4 + 1] = b1; sh_b[tid * 4 + 2] = b2; sh_b[tid * 4 + 3] = b3;
-        __syncthreads();
-        if (rl == 0 && cc < c4) {
-            for (int q = 1; q < rpp; ++q) {
-                const int o = (q * tpr + ct) * 4;
-                a0 += sh_a[o]; a1 += sh_a[o + 1]; a2 += sh_a[o + 2]; a3 += sh_a[o + 3];
-                b0 += sh_b[o]; b1 += sh_b[o + 1]; b2 += sh_b[o + 2]; b3 += sh_b[o + 3];
-            }
-            double* pa = partial + (long long)slice * c + cc * 4;
-            double* pb = partial + (long long)(slices + slice) * c + cc * 4;
-            pa[0] = a0; pa[1] = a1; pa[2] = a2; pa[3] = a3;
-            pb[0] = b0; pb[1] = b1; pb[2] = b2; pb[3] = b3;
-        }
-        __syncthreads();
-    }
-}
-
-// BatchNorm-backward stage 1 with two more per-channel reductions over the same elements: max |dy'| and max |xhat|.  They cost
-// no memory traffic (the values are in registers for the sums) and let the finalize kernel bound max |dx| BEFORE dx is
-// written -- which is what allows bn_bwd_apply to emit dx directly as the packed pre-split fp16 image the consuming
-// contractions read (the image's power-of-two scale must be known when the first element is written).
+// MAXIMA (Op = OpBnBwd): two more per-channel reductions over the same elements, max |dy'| and max |xhat|.  They cost no memory
+// traffic (the values are in registers for the sums) and let the finalize kernel bound max |dx| BEFORE dx is written -- which is
+// what allows bn_bwd_apply to emit dx directly as the packed pre-split fp16 image the consuming contractions read (the image's
+// power-of-two scale must be known when the first element is written).
 // pmax[0][slice][c] = max |dy'|, pmax[1][slice][c] = max |xhat| (floats, behind the f64 partials).
-__global__ __launch_bounds__(RT) void bnbwd_reduce_kernel(OpBnBwd op, int rows, int c, int slices, double* __restrict__ partial,
-                                                          float* __restrict__ pmax) {
+template <class Op, bool MAXIMA = false>
+__global__ __launch_bounds__(RT) void colreduce_kernel(Op op, int rows, int c, int slices, double* __restrict__ partial, float* __restrict__ pmax) {
     __shared__ double sh_a[RT * 4];
     __shared__ double sh_b[RT * 4];
-    __shared__ float sh_m[RT * 8];
-    const int tid = threadIdx.x;
-    const int c4 = c >> 2;
-    const int tpr = c4 < RT ? c4 : RT;            // threads per row
-    const int rpp = RT / tpr;                     // rows per pass
-    const int ct = tid % tpr, rl = tid / tpr;
-    const int slice = blockIdx.x;
-    const int per = (rows + slices - 1) / slices;
-    const int r0 = slice * per, r1 = min(rows, r0 + per);
-    for (int cb = blockIdx.y * tpr; cb < c4; cb += gridDim.y * tpr) {
-        const int cc = cb + ct;
-        double a0 = 0, a1 = 0, a2 = 0, a3 = 0, b0 = 0, b1 = 0, b2 = 0, b3 = 0;
-        float mg[4] = {0.f, 0.f, 0.f, 0.f}, mx[4] = {0.f, 0.f, 0.f, 0.f};
-        if (cc < c4 && rl < rpp) {
-            const float4 mu = *reinterpret_cast<const float4*>(op.mean + cc * 4);
-            const float4 is = *reinterpret_cast<const float4*>(op.invstd + cc * 4);
-            for (int r = r0 + rl; r < r1; r += rpp) {
-                float4 a, b;
-                op(r, cc * 4, a, b);
-                a0 += a.x; a1 += a.y; a2 += a.z; a3 += a.w;
-                b0 += b.x; b1 += b.y; b2 += b.z; b3 += b.w;
-                const float4 xx = *reinterpret_cast<const float4*>(op.x + (long long)r * op.ldx + cc * 4);   // (the load op() made: CSE'd)
+    __shared__ float sh_m[MAXIMA ? RT * 8 : 1];
+    const int tid = threadIdx.x, slice = blockIdx.x;
+    const RedLane L = red_lane<4>(rows, c, slices, RT);      // column blocks of up to RT float4
+    double a0 = 0, a1 = 0, a2 = 0, a3 = 0, b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+    float mg[4] = {0.f, 0.f, 0.f, 0.f}, mx[4] = {0.f, 0.f, 0.f, 0.f};
+    if (L.live) {
+        float4 mu, is;
+        if constexpr (MAXIMA) { mu = *reinterpret_cast<const float4*>(op.mean + L.c0); is = *reinterpret_cast<const float4*>(op.invstd + L.c0); }
+        for (int r = L.r; r < L.r1; r += L.rpp) {
+            float4 a, b;
+            op(r, L.c0, a, b);
+            a0 += a.x; a1 += a.y; a2 += a.z; a3 += a.w;
+            b0 += b.x; b1 += b.y; b2 += b.z; b3 += b.w;
+            if constexpr (MAXIMA) {
+                const float4 xx = *reinterpret_cast<const float4*>(op.x + (long long)r * op.ldx + L.c0);   // (the load op() made: CSE'd)
                 mg[0] = fmaxf(mg[0], fabsf(a.x)); mg[1] = fmaxf(mg[1], fabsf(a.y)); mg[2] = fmaxf(mg[2], fabsf(a.z)); mg[3] = fmaxf(mg[3], fabsf(a.w));
                 mx[0] = fmaxf(mx[0], fabsf((xx.x - mu.x) * is.x)); mx[1] = fmaxf(mx[1], fabsf((xx.y - mu.y) * is.y));
                 mx[2] = fmaxf(mx[2], fabsf((xx.z - mu.z) * is.z)); mx[3] = fmaxf(mx[3], fabsf((xx.w - mu.w) * is.w));
             }
         }
-        sh_a[tid * 4 + 0] = a0; sh_a[tid * 4 + 1] = a1; sh_a[tid * 4 + 2] = a2; sh_a[tid * 4 + 3] = a3;
-        sh_b[tid * 4 + 0] = b0; sh_b[tid * 4 + 1] = b1; sh_b[tid * 4 + 2] = b2; sh_b[tid * 4 + 3] = b3;
+    }
+    sh_a[tid * 4 + 0] = a0; sh_a[tid * 4 + 1] = a1; sh_a[tid * 4 + 2] = a2; sh_a[tid * 4 + 3] = a3;
+    sh_b[tid * 4 + 0] = b0; sh_b[tid * 4 + 1] = b1; sh_b[tid * 4 + 2] = b2; sh_b[tid * 4 + 3] = b3;
+    if constexpr (MAXIMA) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) { sh_m[tid * 8 + j] = mg[j]; sh_m[tid * 8 + 4 + j] = mx[j]; }
-        __syncthreads();
-        if (rl == 0 && cc < c4) {
-            for (int q = 1; q < rpp; ++q) {
-                const int o = (q * tpr + ct) * 4;
-                a0 += sh_a[o]; a1 += sh_a[o + 1]; a2 += sh_a[o + 2]; a3 += sh_a[o + 3];
-                b0 += sh_b[o]; b1 += sh_b[o + 1]; b2 += sh_b[o + 2]; b3 += sh_b[o + 3];
+    }
+    __syncthreads();
+    if (L.rl == 0 && L.live) {
+#pragma unroll 2      // (left to the compiler, this fold's unrolling took the whole kernel from 8 waves per SIMD to 6)
+        for (int q = 1; q < L.rpp; ++q) {
+            const int o = (q * L.tpr + L.ct) * 4;
+            a0 += sh_a[o]; a1 += sh_a[o + 1]; a2 += sh_a[o + 2]; a3 += sh_a[o + 3];
+            b0 += sh_b[o]; b1 += sh_b[o + 1]; b2 += sh_b[o + 2]; b3 += sh_b[o + 3];
+            if constexpr (MAXIMA) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { mg[j] = fmaxf(mg[j], sh_m[2 * o + j]); mx[j] = fmaxf(mx[j], sh_m[2 * o + 4 + j]); }
             }
-            double* pa = partial + (long long)slice * c + cc * 4;
-            double* pb = partial + (long long)(slices + slice) * c + cc * 4;
-            pa[0] = a0; pa[1] = a1; pa[2] = a2; pa[3] = a3;
-            pb[0] = b0; pb[1] = b1; pb[2] = b2; pb[3] = b3;
-            *reinterpret_cast<float4*>(pmax + (long long)slice * c + cc * 4) = make_float4(mg[0], mg[1], mg[2], mg[3]);
-            *reinterpret_cast<float4*>(pmax + (long long)(slices + slice) * c + cc * 4) = make_float4(mx[0], mx[1], mx[2], mx[3]);
         }
-        __syncthreads();
+        double* pa = partial + (long long)slice * c + L.c0;
+        double* pb = partial + (long long)(slices + slice) * c + L.c0;
+        pa[0] = a0; pa[1] = a1; pa[2] = a2; pa[3] = a3;
+        pb[0] = b0; pb[1] = b1; pb[2] = b2; pb[3] = b3;
+        if constexpr (MAXIMA) {
+            *reinterpret_cast<float4*>(pmax + (long long)slice * c + L.c0) = make_float4(mg[0], mg[1], mg[2], mg[3]);
+            *reinterpret_cast<float4*>(pmax + (long long)(slices + slice) * c + L.c0) = make_float4(mx[0], mx[1], mx[2], mx[3]);
+        }
     }
 }
 
-// ---- the same reduction WITHOUT a second stage (round 4): per-thread fp32 partial sums over its <= ~16-64 rows (four rows' loads
-// in flight at a time), the workgroup's row lanes folded in double through LDS, then ONE f64 atomic per column, statistic and
-// workgroup into a zero-filled [2][c] buffer (consecutive threads own consecutive columns: a wave's atomics cover 512 contiguous
-// bytes), and one atomicMax per column for the two maxima the packed-gradient bound needs.  bn_bwd_apply_kernel finishes the sums
-// in its prologue: two launches per BatchNorm backward instead of three (the finalize kernels were 221 launches of ~14 us per step).
-// Column blocks are FUSED_TPR float4 wide (64 columns): what limits these reductions is the number of f64 atomics that land on one
-// address -- same-address atomics are serialised by the L2, ~25-30 ns each -- so many narrow column blocks with few row slices each
-// beat whole rows (profiles/r04_bn_reduce_sweep.txt, measured on the 16-bit twin of this kernel).
-constexpr int FUSED_TPR = 16;
-__host__ __device__ inline int fused_slices(int rows, int c) {
-    const int c4 = c > 4 ? c / 4 : 1;
-    const int tpr = c4 < FUSED_TPR ? c4 : FUSED_TPR;
-    const int rpp = RT / tpr;
-    int s = (rows + 16 * rpp - 1) / (16 * rpp);
-    const int cblocks = (c4 + tpr - 1) / tpr;
-    int cap = 1024 / cblocks;
-    if (cap < 1) cap = 1;
-    return s < 1 ? 1 : (s > cap ? cap : s);
-}
-// HAS2: second gradient addend; RM: 0 = no ReLU, 1 = sign bytes, 2 = sign recomputed from x, 3 = sign of the saved output y.
-// WRES: the masked gradient (dy + dy2) * mask is stored to dres while it is in registers -- the apply pass then reads that ONE
-// tensor instead of dy, dy2 and the sign bytes again (dres must not alias dy, dy2 or x: other rows of them are still to be read).
-// The loads of FOUR rows are issued back to back before any arithmetic (through the generic op() the compiler emitted one
-// dependent load -> wait chain per row, the coefficient vectors re-loaded for every row).
-template <bool HAS2, int RM, bool WRES>
-__global__ __launch_bounds__(RT) void bnbwd_reduce_atomic_kernel(OpBnBwd op, int rows, int c, int slices, double* __restrict__ sums,
-                                                                 float* __restrict__ cmax, float* __restrict__ dres, int lddres) {
-    __shared__ float sh[RT * 8];                  // [statistic][row lane][column] for the sums, reused for the maxima
-    const int tid = threadIdx.x;
-    const int c4 = c >> 2;
-    const int tpr = c4 < FUSED_TPR ? c4 : FUSED_TPR;
-    const int rpp = RT / tpr;
-    const int ct = tid % tpr, rl = tid / tpr;
-    const int slice = blockIdx.x;
-    const int per = (rows + slices - 1) / slices;
-    const int r0 = slice * per, r1 = min(rows, r0 + per);
-    for (int cb = blockIdx.y * tpr; cb < c4; cb += gridDim.y * tpr) {
-        const int cc = cb + ct;
-        float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = sa, mg = sa, mx = sa;
-        if (cc < c4 && rl < rpp) {
-            const int c0 = cc * 4;
-            const float4 mu = *reinterpret_cast<const float4*>(op.mean + c0);
-            const float4 is = *reinterpret_cast<const float4*>(op.invstd + c0);
-            float4 ga = mu, be = mu;
-            if (RM == 2) { ga = *reinterpret_cast<const float4*>(op.gamma + c0); be = *reinterpret_cast<const float4*>(op.beta + c0); }
-            auto fold = [&](long long row, float4 a, const float4 a2, const float4 xx, const float4 yy, unsigned m) __attribute__((always_inline)) {
-                if (HAS2) { a.x += a2.x; a.y += a2.y; a.z += a2.z; a.w += a2.w; }
-                if (RM == 2) {
-                    m = (bn_val(xx.x, mu.x, is.x, ga.x, be.x) > 0.f ? 1u : 0u) | (bn_val(xx.y, mu.y, is.y, ga.y, be.y) > 0.f ? 2u : 0u) |
-                        (bn_val(xx.z, mu.z, is.z, ga.z, be.z) > 0.f ? 4u : 0u) | (bn_val(xx.w, mu.w, is.w, ga.w, be.w) > 0.f ? 8u : 0u);
-                } else if (RM == 3) {
-                    m = (yy.x > 0.f ? 1u : 0u) | (yy.y > 0.f ? 2u : 0u) | (yy.z > 0.f ? 4u : 0u) | (yy.w > 0.f ? 8u : 0u);
-                }
-                if (RM != 0) { a.x = (m & 1u) ? a.x : 0.f; a.y = (m & 2u) ? a.y : 0.f; a.z = (m & 4u) ? a.z : 0.f; a.w = (m & 8u) ? a.w : 0.f; }
-                if (WRES) *reinterpret_cast<float4*>(dres + row * lddres + c0) = a;
-                const float4 xh = make_float4((xx.x - mu.x) * is.x, (xx.y - mu.y) * is.y, (xx.z - mu.z) * is.z, (xx.w - mu.w) * is.w);
-                sa.x += a.x; sa.y += a.y; sa.z += a.z; sa.w += a.w;
-                sb.x += a.x * (xx.x - mu.x) * is.x; sb.y += a.y * (xx.y - mu.y) * is.y; sb.z += a.z * (xx.z - mu.z) * is.z; sb.w += a.w * (xx.w - mu.w) * is.w;
-                if (cmax) {
-                    mg.x = fmaxf(mg.x, fabsf(a.x)); mg.y = fmaxf(mg.y, fabsf(a.y)); mg.z = fmaxf(mg.z, fabsf(a.z)); mg.w = fmaxf(mg.w, fabsf(a.w));
-                    mx.x = fmaxf(mx.x, fabsf(xh.x)); mx.y = fmaxf(mx.y, fabsf(xh.y)); mx.z = fmaxf(mx.z, fabsf(xh.z)); mx.w = fmaxf(mx.w, fabsf(xh.w));
-                }
-            };
-            int r = r0 + rl;
-            for (; r + 3 * rpp < r1; r += 4 * rpp) {
-                float4 qa[4], qa2[4], qx[4], qy[4];
-                unsigned m[4] = {15u, 15u, 15u, 15u};
+// ---- the same reductions WITHOUT a second stage, for both storages (col_reduce.h: red_geom, red_lane, red_fold): per-thread fp32
+// partial sums over its <= ~16-64 rows (four rows' loads in flight at a time), the workgroup's row lanes folded in double through
+// LDS, then ONE f64 atomic per column, statistic and workgroup into a zero-filled [2][c] buffer -- the same contract as
+// glf_gemm_params.colstats, so a BatchNorm takes its sums from the producing contraction's epilogue or from a kernel here alike,
+// and the apply kernels finish the statistics in their prologue: two launches per BatchNorm backward instead of three (the
+// finalize kernels were 221 launches of ~14 us per step).
+
+// generic two-value reduction of bf16 storage (statistics, column sum): op(r, c0, a, b)
+template <class Op>
+__global__ __launch_bounds__(RT) void s16_colreduce_kernel(Op op, int rows, int c, int slices, double* __restrict__ sums) {
+    __shared__ float sh[RT * 16];
+    const RedLane L = red_lane<8>(rows, c, slices, RED_TPR);
+    float acc[16];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const long long row = r + u * rpp;
-                    qa[u] = *reinterpret_cast<const float4*>(op.dy + row * op.lddy + c0);
-                    if (HAS2) qa2[u] = *reinterpret_cast<const float4*>(op.dy2 + row * op.lddy2 + c0);
-                    qx[u] = *reinterpret_cast<const float4*>(op.x + row * op.ldx + c0);
-                    if (RM == 3) qy[u] = *reinterpret_cast<const float4*>(op.y + row * op.ldy + c0);
-                    if (RM == 1) m[u] = op.mask[row * op.c4 + cc];
-                }
-                __builtin_amdgcn_sched_barrier(0);       // every load of the four rows is in flight before the first use
+    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+    if (L.live) {
+        const int rpp = L.rpp, c0 = L.c0;
+        int r = L.r;
+        for (; r + 3 * rpp < L.r1; r += 4 * rpp) {
+            F8 a0, b0, a1, b1, a2, b2, a3, b3;
+            op(r, c0, a0, b0); op(r + rpp, c0, a1, b1); op(r + 2 * rpp, c0, a2, b2); op(r + 3 * rpp, c0, a3, b3);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) fold(r + u * rpp, qa[u], HAS2 ? qa2[u] : qa[u], qx[u], RM == 3 ? qy[u] : qx[u], m[u]);
-            }
-            for (; r < r1; r += rpp) {
-                const long long row = r;
-                const float4 qa = *reinterpret_cast<const float4*>(op.dy + row * op.lddy + c0);
-                const float4 qa2 = HAS2 ? *reinterpret_cast<const float4*>(op.dy2 + row * op.lddy2 + c0) : qa;
-                const float4 qx = *reinterpret_cast<const float4*>(op.x + row * op.ldx + c0);
-                const float4 qy = RM == 3 ? *reinterpret_cast<const float4*>(op.y + row * op.ldy + c0) : qx;
-                const unsigned m = RM == 1 ? op.mask[row * op.c4 + cc] : 15u;
-                fold(row, qa, qa2, qx, qy, m);
-            }
+            for (int j = 0; j < 8; ++j) { acc[j] += (a0.v[j] + a1.v[j]) + (a2.v[j] + a3.v[j]); acc[8 + j] += (b0.v[j] + b1.v[j]) + (b2.v[j] + b3.v[j]); }
         }
-        const int ncol = tpr * 4;
-        for (int pass = 0; pass < (cmax ? 2 : 1); ++pass) {
-            if (rl < rpp) {
-                const float4 u = pass == 0 ? sa : mg, v = pass == 0 ? sb : mx;
-                float* d0 = sh + (0 * rpp + rl) * ncol + ct * 4;
-                float* d1 = sh + (1 * rpp + rl) * ncol + ct * 4;
-                d0[0] = u.x; d0[1] = u.y; d0[2] = u.z; d0[3] = u.w;
-                d1[0] = v.x; d1[1] = v.y; d1[2] = v.z; d1[3] = v.w;
-            }
-            __syncthreads();
-            for (int idx = tid; idx < 2 * ncol; idx += RT) {
-                const int st = idx / ncol, col = idx - st * ncol;
-                const int gc = cb * 4 + col;
-                if (gc < c) {
-                    if (pass == 0) {
-                        double d = 0;
-                        for (int q = 0; q < rpp; ++q) d += sh[(st * rpp + q) * ncol + col];
-                        atomicAdd(sums + st * c + gc, d);
-                    } else {
-                        float m = 0.f;
-                        for (int q = 0; q < rpp; ++q) m = fmaxf(m, sh[(st * rpp + q) * ncol + col]);
-                        if (m > 0.f) atomicMax(reinterpret_cast<unsigned*>(cmax + st * c + gc), __float_as_uint(m));
-                    }
-                }
-            }
-            __syncthreads();
+        for (; r < L.r1; r += rpp) {
+            F8 a, b;
+            op(r, c0, a, b);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { acc[j] += a.v[j]; acc[8 + j] += b.v[j]; }
         }
     }
+    red_fold<8, false>(sh, L, acc, c, sums);
+}
+
+// BatchNorm backward: sums[0][c] += sum dy', sums[1][c] += sum dy' xhat with dy' = (dy + dy2) * relu-mask, over storage T with
+// W = 16 / sizeof(T) elements per access and W sign bits per mask byte.
+// HAS2: second gradient addend; RM: 0 = no ReLU, 1 = sign bytes, 2 = sign recomputed from x, 3 = sign of the saved output y.
+// WRES: the masked gradient is stored to dres while it is in registers -- the apply pass then reads that ONE tensor instead of dy,
+// dy2 and the sign bytes again (dres must not alias dy, dy2 or x: other rows of them are still to be read).
+// fp32 storage with cmax != null: also one atomic max per column for max |dy'| and max |xhat|, which the packed-gradient bound
+// needs (bf16 storage has no packed image: compiled out).  bf16 storage instantiates RM 0 .. 2 without WRES.
+// The coefficient vectors are loaded once; the loads of FOUR rows (8-12 x 16 bytes per lane) are issued back to back before any
+// arithmetic (through a generic op() the compiler emitted one dependent load -> wait chain per row -- five s_waitcnt vmcnt(0)
+// per row, 2.3 TB/s -- with the coefficient vectors re-loaded for every row).
+template <class T, bool HAS2, int RM, bool WRES>
+__global__ __launch_bounds__(RT) void bnbwd_reduce_atomic_kernel(BnBwdIn<T> op, int rows, int c, int slices, double* __restrict__ sums,
+                                                                 float* __restrict__ cmax, T* __restrict__ dres, int lddres) {
+    constexpr int W = 16 / sizeof(T);
+    constexpr bool MAXIMA = sizeof(T) == 4;
+    typedef Stream<T, W> S;
+    typedef typename S::Raw Raw;
+    __shared__ float sh[RT * 2 * W];              // [statistic][row lane][column] for the sums, reused for the maxima
+    const RedLane L = red_lane<W>(rows, c, slices, RED_TPR);
+    // (sum dy', sum dy' xhat) and (max |dy'|, max |xhat|), each pair as ONE array: as two FV<W> the bf16 <false, 2> instantiation
+    // compiled to 160 VGPRs instead of 127 and lost its fourth wave (profiles/bn_merge_resources.txt)
+    float acc[2 * W], top[2 * W];
+#pragma unroll
+    for (int j = 0; j < 2 * W; ++j) acc[j] = top[j] = 0.f;
+    if (L.live) {
+        const int c0 = L.c0, cc = L.cc, rpp = L.rpp;
+        const FV<W> mu = Stream<float, W>::ld(op.mean + c0), is = Stream<float, W>::ld(op.invstd + c0);
+        FV<W> ga = mu, be = mu;
+        if (RM == 2) { ga = Stream<float, W>::ld(op.gamma + c0); be = Stream<float, W>::ld(op.beta + c0); }
+        auto fold = [&](long long row, const Raw qa, const Raw qa2, const Raw qx, const Raw qy, unsigned m) __attribute__((always_inline)) {
+            FV<W> a = S::unpack(qa);
+            if (HAS2) {
+                const FV<W> a2 = S::unpack(qa2);
+#pragma unroll
+                for (int j = 0; j < W; ++j) a.v[j] += a2.v[j];
+            }
+            const FV<W> xx = S::unpack(qx);
+            if (RM == 2 || RM == 3) {
+                const FV<W> yy = S::unpack(qy);
+                m = 0;
+#pragma unroll
+                for (int j = 0; j < W; ++j) m |= ((RM == 2 ? bn_val(xx.v[j], mu.v[j], is.v[j], ga.v[j], be.v[j]) : yy.v[j]) > 0.f ? 1u : 0u) << j;
+            }
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                a.v[j] = (RM == 0 || ((m >> j) & 1u)) ? a.v[j] : 0.f;
+                acc[j] += a.v[j];
+                acc[W + j] += a.v[j] * (xx.v[j] - mu.v[j]) * is.v[j];
+            }
+            if (WRES) S::st(dres + row * lddres + c0, a);
+            if (MAXIMA && cmax) {
+#pragma unroll
+                for (int j = 0; j < W; ++j) { top[j] = fmaxf(top[j], fabsf(a.v[j])); top[W + j] = fmaxf(top[W + j], fabsf((xx.v[j] - mu.v[j]) * is.v[j])); }
+            }
+        };
+        int r = L.r;
+        for (; r + 3 * rpp < L.r1; r += 4 * rpp) {
+            Raw qa[4], qa2[4], qx[4], qy[4];
+            unsigned m[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const long long row = r + u * rpp;
+                qa[u] = S::ldraw(op.dy + row * op.lddy + c0);
+                if (HAS2) qa2[u] = S::ldraw(op.dy2 + row * op.lddy2 + c0);
+                qx[u] = S::ldraw(op.x + row * op.ldx + c0);
+                if (RM == 3) qy[u] = S::ldraw(op.y + row * op.ldy + c0);
+                if (RM == 1) m[u] = op.mask[row * op.cw + cc];
+            }
+            __builtin_amdgcn_sched_barrier(0);       // every load of the four rows is in flight before the first use (hipcc sinks them to their uses)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) fold(r + u * rpp, qa[u], HAS2 ? qa2[u] : qa[u], qx[u], RM == 3 ? qy[u] : qx[u], m[u]);
+        }
+        for (; r < L.r1; r += rpp) {
+            const long long row = r;
+            const Raw qa = S::ldraw(op.dy + row * op.lddy + c0);
+            const Raw qa2 = HAS2 ? S::ldraw(op.dy2 + row * op.lddy2 + c0) : qa;
+            const Raw qx = S::ldraw(op.x + row * op.ldx + c0);
+            const Raw qy = RM == 3 ? S::ldraw(op.y + row * op.ldy + c0) : qx;
+            fold(row, qa, qa2, qx, qy, RM == 1 ? op.mask[row * op.cw + cc] : 0u);
+        }
+    }
+    red_fold<W, false>(sh, L, acc, c, sums);
+    if (MAXIMA && cmax) {
+        __syncthreads();
+        red_fold<W, true>(sh, L, top, c, cmax);
+    }
+}
+// one dispatch ladder for both storages: cmax and dres are fp32-storage extras (null for bf16)
+template <class T>
+int launch_bnbwd_reduce(const BnBwdIn<T>& op, int rows, int c, double* sums, float* cmax, T* dres, int lddres, hipStream_t s, const char* what) {
+    constexpr int W = 16 / sizeof(T);
+    const RedGeom g = red_geom<W>(rows, c);
+    const int rm = !op.relu ? 0 : (op.mask ? 1 : (op.y ? 3 : 2));
+#define GLF_BNR(H2, RM_, WR) hipLaunchKernelGGL((bnbwd_reduce_atomic_kernel<T, H2, RM_, WR>), red_grid(g), dim3(RT), 0, s, op, rows, c, g.slices, sums, cmax, dres, lddres)
+#define GLF_BNR_RM(H2, WR) do { if (rm == 0) GLF_BNR(H2, 0, WR); else if (rm == 1) GLF_BNR(H2, 1, WR); else if (rm == 2) GLF_BNR(H2, 2, WR); \
+                                else if constexpr (W == 4) GLF_BNR(H2, 3, WR); } while (0)
+    if constexpr (W == 4) { if (dres) { GLF_BNR_RM(true, true); return glf::check_launch(what); } }
+    if (op.dy2) GLF_BNR_RM(true, false); else GLF_BNR_RM(false, false);
+#undef GLF_BNR_RM
+#undef GLF_BNR
+    return glf::check_launch(what);
 }
 
 // stage 2: fold the per-slice partials.  One workgroup = 16 channels x 16 slice lanes (a serial loop over
@@ -355,6 +352,22 @@ __device__ __forceinline__ void fold_partials(const double* __restrict__ partial
     }
 }
 
+// Finishing a batch statistic, written ONCE: every kernel that turns (sum x, sum x^2) of a channel into mean / invstd -- the
+// finalize kernel here and the prologues of bn_apply_sums_kernel and s16_bn_apply_kernel -- calls these, so their results are
+// bit-identical by construction (-ffp-contract=fast chooses contractions per context).
+struct BnStat { float mean, invstd; double var; };      // var: the biased batch variance, clamped at 0
+__device__ __forceinline__ BnStat bn_finish(double sum, double sumsq, int rows, float eps) {
+    const double m = sum / rows;
+    double var = sumsq / rows - m * m;
+    if (var < 0) var = 0;
+    return {(float)m, (float)(1.0 / sqrt(var + (double)eps)), var};
+}
+__device__ __forceinline__ void bn_running_update(const BnStat& st, int rows, float momentum, float& rmean, float& rvar) {
+    const double unb = rows > 1 ? st.var * rows / (rows - 1) : st.var;
+    rmean = (1.f - momentum) * rmean + momentum * st.mean;
+    rvar = (1.f - momentum) * rvar + momentum * (float)unb;
+}
+
 __global__ __launch_bounds__(256) void bn_stats_finalize(const double* __restrict__ partial, int slices, int c, int rows, float eps,
                                                          float momentum, float* mean, float* invstd, float* rmean, float* rvar, long long* nbt) {
     __shared__ double sh[512];
@@ -364,16 +377,10 @@ __global__ __launch_bounds__(256) void bn_stats_finalize(const double* __restric
     fold_partials(partial, slices, c, ch, lane, s, q, sh);
     if (lane != 0 || ch >= c) return;
     if (ch == 0 && nbt) *nbt += 1;
-    const double m = s / rows;
-    double var = q / rows - m * m;
-    if (var < 0) var = 0;
-    mean[ch] = (float)m;
-    invstd[ch] = (float)(1.0 / sqrt(var + (double)eps));
-    if (rmean) {
-        const double unb = rows > 1 ? var * rows / (rows - 1) : var;
-        rmean[ch] = (1.f - momentum) * rmean[ch] + momentum * (float)m;
-        rvar[ch] = (1.f - momentum) * rvar[ch] + momentum * (float)unb;
-    }
+    const BnStat st = bn_finish(s, q, rows, eps);
+    mean[ch] = st.mean;
+    invstd[ch] = st.invstd;
+    if (rmean) bn_running_update(st, rows, momentum, rmean[ch], rvar[ch]);
 }
 
 // out_a[ch] = sum of first partial, out_b[ch] = sum of second (either may be NULL)
@@ -575,7 +582,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
 
 // BatchNorm apply with the statistics FINISHED IN THE KERNEL: the producing contraction's epilogue left (sum x, sum x^2) per
 // channel in `sums` (glf_gemm_params.colstats); every workgroup turns them into mean / invstd for the channels of ITS column
-// block in LDS (the same double-precision expressions as bn_stats_finalize: results are bit-identical to glf_bn_stats_from_sums +
+// block in LDS (bn_finish, as bn_stats_finalize does: results are bit-identical to glf_bn_stats_from_sums +
 // glf_bn_apply), the workgroup of row slice 0 also writes them out for the backward pass and updates the running statistics of
 // its block.  One launch instead of two per BatchNorm, and no tiny kernel on the dependent chain conv -> statistics -> apply ->
 // next conv.
@@ -599,20 +606,13 @@ __global__ __launch_bounds__(256) void bn_apply_sums_kernel(const float* __restr
     const int base = L.cb * tpr * 4, top = min(c, base + tpr * 4);
     float bound = 0.f;
     for (int ch = (colmax ? 0 : base) + threadIdx.x; ch < (colmax ? c : top); ch += blockDim.x) {
-        const double m = sums[ch] / rows;
-        double var = sums[c + ch] / rows - m * m;
-        if (var < 0) var = 0;
-        const float mf = (float)m, isf = (float)(1.0 / sqrt(var + (double)eps));
-        if (colmax) bound = fmaxf(bound, fabsf(gamma[ch]) * isf * (colmax[ch] + fabsf(mf)) + fabsf(beta[ch]));
+        const BnStat st = bn_finish(sums[ch], sums[c + ch], rows, eps);
+        if (colmax) bound = fmaxf(bound, fabsf(gamma[ch]) * st.invstd * (colmax[ch] + fabsf(st.mean)) + fabsf(beta[ch]));
         if (ch >= base && ch < top) {
-            s_mean[ch - base] = mf; s_is[ch - base] = isf;
+            s_mean[ch - base] = st.mean; s_is[ch - base] = st.invstd;
             if (L.slice == 0) {
-                mean_out[ch] = mf; invstd_out[ch] = isf;
-                if (rmean) {
-                    const double unb = rows > 1 ? var * rows / (rows - 1) : var;
-                    rmean[ch] = (1.f - momentum) * rmean[ch] + momentum * (float)m;
-                    rvar[ch] = (1.f - momentum) * rvar[ch] + momentum * (float)unb;
-                }
+                mean_out[ch] = st.mean; invstd_out[ch] = st.invstd;
+                if (rmean) bn_running_update(st, rows, momentum, rmean[ch], rvar[ch]);
             }
         }
     }
@@ -773,6 +773,124 @@ int launch_bwd_apply(const BwdApply& p, int relu, hipStream_t s) {
 #undef GLF_BNA_RM
 #undef GLF_BNA
     return glf::check_launch("bn_bwd_apply");
+}
+
+// ---- the applies of bf16 storage: the remaining PAIR.  Flat grid-stride passes over 16-byte accesses (eight channels per lane)
+// with the coefficients of ALL channels in LDS, fp32 arithmetic, one rounding to bf16 at the store -- not the column-owning
+// bodies above.  (Moving them there changes their speed, their column-block tuning and, rarely, the last bf16 bit of the training
+// dx, which they evaluate with 1 / n folded into the sums: a change with its own measurements.)
+__global__ __launch_bounds__(256) void s16_bn_apply_kernel(const u16* __restrict__ x, int ldx, const u16* __restrict__ res, int ldr,
+                                                           u16* __restrict__ y, int ldy, const double* __restrict__ sums, int rows, int c,
+                                                           float eps, float momentum, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float* __restrict__ mean_io, float* __restrict__ invstd_io, float* rmean, float* rvar,
+                                                           long long* nbt, long long total8, int c8, int relu, unsigned char* __restrict__ mask) {
+    // sums != null (train): every workgroup turns (sum x, sum x^2) into mean / invstd for all channels in LDS; workgroup 0 writes
+    // them to mean_io / invstd_io for the backward pass and updates the running statistics.  sums == null (eval): mean_io /
+    // invstd_io are inputs (glf_bn_eval_coeffs).
+    extern __shared__ __attribute__((aligned(16))) float s_coef[];       // [2][c]: mean, invstd
+    float* s_mu = s_coef;
+    float* s_is = s_coef + c;
+    for (int ch = threadIdx.x; ch < c; ch += blockDim.x) {
+        float mf, isf;
+        if (sums) {
+            const BnStat st = bn_finish(sums[ch], sums[c + ch], rows, eps);
+            mf = st.mean; isf = st.invstd;
+            if (blockIdx.x == 0) {
+                mean_io[ch] = mf; invstd_io[ch] = isf;
+                if (rmean) bn_running_update(st, rows, momentum, rmean[ch], rvar[ch]);
+            }
+        } else {
+            mf = mean_io[ch]; isf = invstd_io[ch];
+        }
+        s_mu[ch] = mf; s_is[ch] = isf;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && nbt && sums) *nbt += 1;
+    __syncthreads();
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / c8;
+        const int cc = (int)(i - r * c8) * 8;
+        const F8 xx = ld8(x + r * ldx + cc);
+        const F8 mu = ldf8(s_mu + cc), is = ldf8(s_is + cc), ga = ldf8(gamma + cc), be = ldf8(beta + cc);
+        F8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o.v[j] = bn_val(xx.v[j], mu.v[j], is.v[j], ga.v[j], be.v[j]);
+        if (res) {
+            const F8 rr = ld8(res + r * ldr + cc);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o.v[j] += rr.v[j];
+        }
+        if (mask) {
+            unsigned m = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) m |= (o.v[j] > 0.f ? 1u : 0u) << j;
+            mask[i] = (unsigned char)m;
+        }
+        if (relu) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o.v[j] = fmaxf(o.v[j], 0.f);
+        }
+        st8(y + r * ldy + cc, o);
+    }
+}
+
+// dx = gamma*invstd*(dy' - [sum_dy/n + xhat*sum_dyx/n]) ; dres = dy'.  The sums arrive unfinished (doubles [2][c] from the
+// reduction kernel's atomics); workgroup 0 also writes dgamma = sum dy' xhat and dbeta = sum dy'.
+__global__ __launch_bounds__(256) void s16_bnbwd_apply_kernel(const u16* __restrict__ dy, int lddy, const u16* __restrict__ dy2, int lddy2,
+                                                              const u16* __restrict__ x, int ldx, const float* __restrict__ mean,
+                                                              const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              const double* __restrict__ sums, u16* __restrict__ dx, int lddx, u16* __restrict__ dres,
+                                                              int lddres, float* __restrict__ dgamma, float* __restrict__ dbeta, long long total8, int c8, int c,
+                                                              int relu, int training, float inv_n, const unsigned char* __restrict__ mask) {
+    extern __shared__ __attribute__((aligned(16))) float s_k[];        // [2][c]: s1 / n, s2 / n
+    float* s_s1 = s_k;
+    float* s_s2 = s_k + c;
+    for (int ch = threadIdx.x; ch < c; ch += blockDim.x) {
+        const float a = (float)sums[ch], b = (float)sums[c + ch];
+        s_s1[ch] = a * inv_n; s_s2[ch] = b * inv_n;
+        if (blockIdx.x == 0) { if (dbeta) dbeta[ch] = a; if (dgamma) dgamma[ch] = b; }
+    }
+    __syncthreads();
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / c8;
+        const int cc = (int)(i - r * c8) * 8;
+        F8 g = ld8(dy + r * lddy + cc);
+        if (dy2) {
+            const F8 g2 = ld8(dy2 + r * lddy2 + cc);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) g.v[j] += g2.v[j];
+        }
+        const F8 is = ldf8(invstd + cc), ga = ldf8(gamma + cc);
+        F8 xx, mu;
+        const bool need_x = training || (relu && !mask);
+        if (need_x) { xx = ld8(x + r * ldx + cc); mu = ldf8(mean + cc); }
+        unsigned m = 0xffu;
+        if (relu && mask) {
+            m = mask[i];
+        } else if (relu) {
+            const F8 be = ldf8(beta + cc);
+            m = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) m |= (bn_val(xx.v[j], mu.v[j], is.v[j], ga.v[j], be.v[j]) > 0.f ? 1u : 0u) << j;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) g.v[j] = ((m >> j) & 1u) ? g.v[j] : 0.f;
+        if (dres) st8(dres + r * lddres + cc, g);
+        F8 o;
+        if (training) {
+            const F8 s1 = ldf8(s_s1 + cc), s2 = ldf8(s_s2 + cc);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o.v[j] = ga.v[j] * is.v[j] * (g.v[j] - (s1.v[j] + (xx.v[j] - mu.v[j]) * is.v[j] * s2.v[j]));
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o.v[j] = g.v[j] * ga.v[j] * is.v[j];
+        }
+        st8(dx + r * lddx + cc, o);
+    }
+}
+
+__global__ void f64_to_f32_kernel(const double* __restrict__ src, float* __restrict__ dst, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = (float)src[i];
 }
 
 // ---- TPAVI tail: one wavefront per row ---------------------------------------------------
@@ -1063,8 +1181,14 @@ template <class Op>
 int launch_colreduce(Op op, int rows, int c, double* ws, hipStream_t s) {
     const int slices = n_slices_c(rows, c);
     const int c4 = c / 4, tpr = c4 < RT ? c4 : RT;
-    hipLaunchKernelGGL((colreduce_kernel<Op>), dim3(slices, (c4 + tpr - 1) / tpr), dim3(RT), 0, s, op, rows, c, slices, ws);
+    hipLaunchKernelGGL((colreduce_kernel<Op>), dim3(slices, (c4 + tpr - 1) / tpr), dim3(RT), 0, s, op, rows, c, slices, ws, (float*)nullptr);
     return glf::check_launch("colreduce");
+}
+template <class Op>
+int launch_colreduce16(Op op, int rows, int c, double* sums, hipStream_t s) {
+    const RedGeom g = red_geom<8>(rows, c);
+    hipLaunchKernelGGL((s16_colreduce_kernel<Op>), red_grid(g), dim3(RT), 0, s, op, rows, c, g.slices, sums);
+    return glf::check_launch("s16_colreduce");
 }
 
 }  // namespace
@@ -1171,7 +1295,7 @@ extern "C" int glf_bn_bwd(const float* dy, int lddy, const float* x, int ldx, co
     if (relu && y) { REQ_AL(y, "y"); REQ_LD(ldy, "ldy"); }
     if (dres) { REQ_AL(dres, "dres"); REQ_LD(lddres, "lddres"); }
     if (dy2) { REQ_AL(dy2, "dy2"); REQ_LD(lddy2, "lddy2"); }
-    const OpBnBwd op{dy, lddy, x, ldx, y, ldy, mean, invstd, gamma, beta, relu, relu_mask, c / 4, dy2, lddy2};
+    const OpBnBwd op{{dy, lddy, x, ldx, y, ldy, mean, invstd, gamma, beta, relu, relu_mask, c / 4, dy2, lddy2}};
     const ColGrid ag = col_grid(rows, c);
     BwdApply ap{dy, lddy, x, ldx, y, ldy, Coef{mean, invstd, gamma, beta}, nullptr, nullptr, dx, lddx, dres, lddres,
                 rows, c, ag.tpr, ag.cblocks, ag.slices, training, 1.0f / (float)rows,
@@ -1191,22 +1315,12 @@ extern "C" int glf_bn_bwd(const float* dy, int lddy, const float* x, int ldx, co
     if (!phase && fused_sums && c <= APPLY_MAX_C) {
         // two launches: reduction with atomics into the caller's ZERO-FILLED buffer (2 c doubles, then 2 c floats of maxima), apply
         float* fmax = reinterpret_cast<float*>(fused_sums + (size_t)2 * c);
-        const int fs = fused_slices(rows, c);
-        const int c4 = c / 4, tpr = c4 < FUSED_TPR ? c4 : FUSED_TPR;
-        const dim3 rgrid(fs, (c4 + tpr - 1) / tpr);
-        float* rmax = packed_dx ? fmax : (float*)nullptr;
-        const int rm = !op.relu ? 0 : (op.mask ? 1 : (op.y ? 3 : 2));
         // a fan-in pair with a residual gradient wanted: the reduction stores the masked sum to dres, and the apply pass reads
         // it back as its (already masked) dy instead of dy, dy2 and the sign bytes -- 28.25 instead of 32.5 bytes per element
         const bool wres = dy2 && dres;
         GLF_REQUIRE(!wres || (dres != dy && dres != dy2 && dres != x), GLF_ERR_BAD_SHAPE, "bn_bwd: dres must not alias dy, dy2 or x");
-#define GLF_BNR(H2, RM_, WR) hipLaunchKernelGGL((bnbwd_reduce_atomic_kernel<H2, RM_, WR>), rgrid, dim3(RT), 0, glf::S(s), op, rows, c, fs, fused_sums, rmax, \
-                                                (WR) ? dres : (float*)nullptr, lddres)
-        if (wres) { if (rm == 0) GLF_BNR(true, 0, true); else if (rm == 1) GLF_BNR(true, 1, true); else if (rm == 2) GLF_BNR(true, 2, true); else GLF_BNR(true, 3, true); }
-        else if (op.dy2) { if (rm == 0) GLF_BNR(true, 0, false); else if (rm == 1) GLF_BNR(true, 1, false); else if (rm == 2) GLF_BNR(true, 2, false); else GLF_BNR(true, 3, false); }
-        else { if (rm == 0) GLF_BNR(false, 0, false); else if (rm == 1) GLF_BNR(false, 1, false); else if (rm == 2) GLF_BNR(false, 2, false); else GLF_BNR(false, 3, false); }
-#undef GLF_BNR
-        if (int rc = glf::check_launch("bn_bwd_reduce(fused)")) return rc;
+        if (int rc = launch_bnbwd_reduce<float>(op, rows, c, fused_sums, packed_dx ? fmax : (float*)nullptr, wres ? dres : (float*)nullptr, lddres,
+                                                glf::S(s), "bn_bwd_reduce(fused)")) return rc;
         ap.fsums = fused_sums; ap.fmax = fmax; ap.out_dbeta = dbeta; ap.out_dgamma = dgamma;
         if (wres) {
             ap.dy = dres; ap.lddy = lddres; ap.dy2 = nullptr; ap.mask = nullptr; ap.y = nullptr; ap.dres = nullptr;
@@ -1225,7 +1339,7 @@ extern "C" int glf_bn_bwd(const float* dy, int lddy, const float* x, int ldx, co
     } else if (packed_dx) {
         float* pmax = reinterpret_cast<float*>(workspace + (size_t)2 * slices * c + (size_t)2 * c);
         const int c4 = c / 4, tpr = c4 < RT ? c4 : RT;
-        hipLaunchKernelGGL(bnbwd_reduce_kernel, dim3(slices, (c4 + tpr - 1) / tpr), dim3(RT), 0, glf::S(s), op, rows, c, slices, workspace, pmax);
+        hipLaunchKernelGGL((colreduce_kernel<OpBnBwd, true>), dim3(slices, (c4 + tpr - 1) / tpr), dim3(RT), 0, glf::S(s), op, rows, c, slices, workspace, pmax);
         if (int rc = glf::check_launch("bn_bwd_reduce")) return rc;
         hipLaunchKernelGGL(bnbwd_finalize, dim3((c + FIN_CH - 1) / FIN_CH), dim3(256), 0, glf::S(s), workspace, pmax, slices, c, gamma, invstd,
                            1.0f / (float)rows, training, s_dy, s_dyx, amax_out, keep);
@@ -1247,6 +1361,69 @@ extern "C" int glf_colsum(const float* dy, int lddy, float* db, int rows, int c,
     if (int rc = launch_colreduce(OpColsum{dy, lddy}, rows, c, workspace, glf::S(s))) return rc;
     hipLaunchKernelGGL(sum_finalize, dim3((c + FIN_CH - 1) / FIN_CH), dim3(256), 0, glf::S(s), workspace, n_slices_c(rows, c), c, db, (float*)nullptr);
     return glf::check_launch("colsum_finalize");
+}
+
+// ---- bf16 storage: the same entry points over 16-byte accesses of eight bf16 (C % 8 == 0)
+extern "C" int glf_s16_colstats(const void* x, int ldx, int rows, int c, double* sums, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(x && sums, GLF_ERR_NULL, "s16_colstats: null argument");
+    GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "s16_colstats: rows must be > 0");
+    REQ_C8(c); REQ_AL(x, "x"); REQ_LD8(ldx, "ldx");
+    return launch_colreduce16(OpStats16{static_cast<const u16*>(x), ldx}, rows, c, sums, glf::S(s));
+}
+
+extern "C" int glf_s16_bn_apply(const void* x, int ldx, const void* residual, int ldr, void* y, int ldy, const double* sums,
+                                int rows, int c, float eps, float momentum, const float* gamma, const float* beta,
+                                float* mean, float* invstd, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                int relu, uint8_t* relu_mask, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(x && y && mean && invstd && gamma && beta, GLF_ERR_NULL, "s16_bn_apply: null argument");
+    GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "s16_bn_apply: rows must be > 0");
+    REQ_C8(c); REQ_AL(x, "x"); REQ_AL(y, "y"); REQ_LD8(ldx, "ldx"); REQ_LD8(ldy, "ldy");
+    GLF_REQUIRE(c <= APPLY_MAX_C, GLF_ERR_UNSUPPORTED, "s16_bn_apply: C must be <= %d", APPLY_MAX_C);
+    GLF_REQUIRE((running_mean == nullptr) == (running_var == nullptr), GLF_ERR_NULL, "s16_bn_apply: running_mean/var must both be set or both NULL");
+    if (residual) { REQ_AL(residual, "residual"); REQ_LD8(ldr, "ldr"); }
+    const long long total8 = (long long)rows * (c / 8);
+    hipLaunchKernelGGL(s16_bn_apply_kernel, dim3(stream_grid(total8, 256)), dim3(256), (size_t)2 * c * sizeof(float), glf::S(s),
+                       static_cast<const u16*>(x), ldx, static_cast<const u16*>(residual), ldr, static_cast<u16*>(y), ldy, sums, rows, c, eps, momentum,
+                       gamma, beta, mean, invstd, running_mean, running_var, reinterpret_cast<long long*>(num_batches_tracked), total8, c / 8, relu,
+                       relu_mask);
+    return glf::check_launch("s16_bn_apply");
+}
+
+extern "C" int glf_s16_bn_bwd(const void* dy, int lddy, const void* dy2, int lddy2, const void* x, int ldx,
+                              const float* mean, const float* invstd, const float* gamma, const float* beta,
+                              void* dx, int lddx, void* dres, int lddres, float* dgamma, float* dbeta,
+                              int rows, int c, int relu, int training, double* sums, const uint8_t* relu_mask, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(dy && x && mean && invstd && gamma && dx && sums, GLF_ERR_NULL, "s16_bn_bwd: null argument");
+    GLF_REQUIRE(!relu || beta || relu_mask, GLF_ERR_NULL, "s16_bn_bwd: relu != 0 needs relu_mask or beta (to recompute the sign from x)");
+    GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "s16_bn_bwd: rows must be > 0");
+    REQ_C8(c); REQ_AL(dy, "dy"); REQ_AL(x, "x"); REQ_AL(dx, "dx"); REQ_LD8(lddy, "lddy"); REQ_LD8(ldx, "ldx"); REQ_LD8(lddx, "lddx");
+    GLF_REQUIRE(c <= APPLY_MAX_C, GLF_ERR_UNSUPPORTED, "s16_bn_bwd: C must be <= %d", APPLY_MAX_C);
+    if (dres) { REQ_AL(dres, "dres"); REQ_LD8(lddres, "lddres"); }
+    if (dy2) { REQ_AL(dy2, "dy2"); REQ_LD8(lddy2, "lddy2"); }
+    const BnBwdIn<u16> op{static_cast<const u16*>(dy), lddy, static_cast<const u16*>(x), ldx, nullptr, 0, mean, invstd, gamma, beta,
+                          relu, relu_mask, c / 8, static_cast<const u16*>(dy2), lddy2};
+    if (int rc = launch_bnbwd_reduce<u16>(op, rows, c, sums, nullptr, nullptr, 0, glf::S(s), "s16_bn_bwd_reduce")) return rc;
+    const long long total8 = (long long)rows * (c / 8);
+    hipLaunchKernelGGL(s16_bnbwd_apply_kernel, dim3(stream_grid(total8, 256)), dim3(256), (size_t)2 * c * sizeof(float), glf::S(s),
+                       static_cast<const u16*>(dy), lddy, static_cast<const u16*>(dy2), lddy2, static_cast<const u16*>(x), ldx, mean, invstd, gamma, beta,
+                       sums, static_cast<u16*>(dx), lddx, static_cast<u16*>(dres), lddres, dgamma, dbeta, total8, c / 8, c, relu, training,
+                       1.0f / (float)rows, relu_mask);
+    return glf::check_launch("s16_bn_bwd_apply");
+}
+
+extern "C" int glf_s16_colsum(const void* dy, int lddy, float* db, int rows, int c, double* workspace, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    GLF_REQUIRE(dy && db && workspace, GLF_ERR_NULL, "s16_colsum: null argument");
+    GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "s16_colsum: rows must be > 0");
+    REQ_C8(c); REQ_AL(dy, "dy"); REQ_LD8(lddy, "lddy");
+    hipError_t e = hipMemsetAsync(workspace, 0, (size_t)2 * c * sizeof(double), glf::S(s));
+    if (e != hipSuccess) return glf::fail(GLF_ERR_LAUNCH, "s16_colsum: hipMemsetAsync: %s", hipGetErrorString(e));
+    if (int rc = launch_colreduce16(OpColsum16{static_cast<const u16*>(dy), lddy}, rows, c, workspace, glf::S(s))) return rc;
+    hipLaunchKernelGGL(f64_to_f32_kernel, dim3((c + 255) / 256), dim3(256), 0, glf::S(s), workspace, db, c);
+    return glf::check_launch("s16_colsum");
 }
 
 extern "C" int glf_bn_res_ln_fwd(const float* w, const float* x, const float* bn_mean, const float* bn_invstd,

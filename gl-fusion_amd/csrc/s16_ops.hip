@@ -1,385 +1,13 @@
-// 16-bit-storage ("S16") streaming kernels of the GL-Fusion path: everything between the contractions when activations,
-// saved tensors and activation gradients live in HBM as bf16 (BASELINE configs 3 / 5).  All HBM-bound: 16-byte accesses
-// (eight channels per lane), fp32 arithmetic in registers, one rounding to bf16 at the store.  Channels-last [rows][C],
-// C % 8 == 0.  Statistics (BatchNorm forward and backward sums) are accumulated in double and meet in ONE f64 atomic per
-// column and workgroup in a zero-filled [2][C] buffer -- the same contract as glf_gemm_params.colstats, so a BatchNorm takes
-// its sums from the producing contraction's epilogue or from s16_colstats_kernel alike, and every apply kernel finishes the
-// statistics itself (no finalize launches).
+// 16-bit-storage ("S16") streaming kernels of the GL-Fusion path that have no fp32-storage counterpart to share a body or a file
+// with: the TPAVI tail, the per-frame row sums, the casts and the softmax rows, when activations, saved tensors and activation
+// gradients live in HBM as bf16 (BASELINE configs 3 / 5).  All HBM-bound: 16-byte accesses (eight channels per lane), fp32
+// arithmetic in registers, one rounding to bf16 at the store.  Channels-last [rows][C], C % 8 == 0.
+// (BatchNorm and the column reductions of both storages: norm.hip; the pointwise ops of both: pointwise.hip.)
 #include "stream_common.h"
 
 using namespace glf;
 
 namespace {
-
-// the forward value of one BatchNorm element: ONE definition, so the ReLU mask recomputed in backward is the forward's
-__device__ __forceinline__ float bn_val(float x, float mu, float is, float ga, float be) { return (x - mu) * is * ga + be; }
-
-// ----------------------------------------------------------------------------------------------------------------------
-// column statistics: sums[c] += sum_r x[r][c], sums[C + c] += sum_r x[r][c]^2   (doubles, zero-filled by the caller)
-// ----------------------------------------------------------------------------------------------------------------------
-constexpr int RT = 256;
-
-// Grid shape of the column reductions (profiles/r04_bn_reduce_sweep.txt): a workgroup covers RED_TPR * 8 columns with 256 / RED_TPR row
-// lanes that are folded in LDS, 16 rows per thread, at most 1 024 workgroups.  What it optimises is the number of f64 atomics that
-// land on ONE address: same-address atomics are serialised by the L2 (~25-30 ns each; 1 024 workgroups adding to the same 512
-// doubles took longer than streaming the tensor), so narrow column blocks -- many blocks, few row slices per block -- beat whole
-// rows: 193 600 x 256: 37.8 -> 27.5 us, 50 176 x 1 024: 45.4 -> 20.3 us.  More, smaller workgroups only add atomics.
-constexpr int g_red_rpt = 16, g_red_cap = 1024, g_red_tpr = 16;
-inline void red_init() {}
-inline int red_slices(int rows, int c) {
-    // A workgroup streams `per` rows of all its channels; the grid must put enough loads in flight to reach the HBM rate (these
-    // reductions are latency-bound at low occupancy: 512 workgroups of 12 dependent iterations each ran at 1 TB/s), so: ~64 rows
-    // per row lane, at most 1 024 workgroups (one f64 atomic per column and slice).
-    const int c8 = c > 8 ? c / 8 : 1;
-    const int tpr = c8 < g_red_tpr ? c8 : g_red_tpr;
-    const int rpp = 256 / tpr;                        // rows per pass of a workgroup
-    int s = (rows + g_red_rpt * rpp - 1) / (g_red_rpt * rpp);
-    const int cblocks = (c8 + tpr - 1) / tpr;
-    int cap = g_red_cap / cblocks;
-    if (cap < 1) cap = 1;
-    return s < 1 ? 1 : (s > cap ? cap : s);
-}
-
-// generic two-value column reduction over rows: op(r, c8, a[8], b[8]); grid (slices, channel blocks).  Per thread: fp32 partial
-// sums over its <= ~16-64 rows, four rows' loads in flight at a time; the row lanes of a workgroup are folded in double through LDS
-// and ONE f64 atomic per column, statistic and workgroup reaches memory.
-template <class Op>
-__global__ __launch_bounds__(RT) void s16_colreduce_kernel(Op op, int rows, int c, int slices, double* __restrict__ sums, int tpr_max) {
-    __shared__ float sh[RT * 16];
-    const int tid = threadIdx.x;
-    const int c8 = c >> 3;
-    const int tpr = c8 < tpr_max ? c8 : tpr_max;  // threads per row
-    const int rpp = RT / tpr;                     // rows per pass
-    const int ct = tid % tpr, rl = tid / tpr;
-    const int slice = blockIdx.x;
-    const int per = (rows + slices - 1) / slices;
-    const int r0 = slice * per, r1 = min(rows, r0 + per);
-    for (int cb = blockIdx.y * tpr; cb < c8; cb += gridDim.y * tpr) {
-        const int cc = cb + ct;
-        float acc[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-        if (cc < c8 && rl < rpp) {
-            int r = r0 + rl;
-            for (; r + 3 * rpp < r1; r += 4 * rpp) {
-                float a0[8], b0[8], a1[8], b1[8], a2[8], b2[8], a3[8], b3[8];
-                op(r, cc * 8, a0, b0); op(r + rpp, cc * 8, a1, b1); op(r + 2 * rpp, cc * 8, a2, b2); op(r + 3 * rpp, cc * 8, a3, b3);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { acc[j] += (a0[j] + a1[j]) + (a2[j] + a3[j]); acc[8 + j] += (b0[j] + b1[j]) + (b2[j] + b3[j]); }
-            }
-            for (; r < r1; r += rpp) {
-                float a[8], b[8];
-                op(r, cc * 8, a, b);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { acc[j] += a[j]; acc[8 + j] += b[j]; }
-            }
-        }
-        // fold the row lanes through LDS ([statistic][row lane][column]) and let consecutive threads own consecutive COLUMNS: a wave's
-        // 64 atomics then cover 512 contiguous bytes (scattered f64 atomics -- one thread adding its 8 columns, lanes 64 bytes
-        // apart -- ran at a tenth of that rate and were most of this kernel's time)
-        const int ncol = tpr * 8;
-        if (rl < rpp) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { sh[(0 * rpp + rl) * ncol + ct * 8 + j] = acc[j]; sh[(1 * rpp + rl) * ncol + ct * 8 + j] = acc[8 + j]; }
-        }
-        __syncthreads();
-        for (int idx = tid; idx < 2 * ncol; idx += RT) {
-            const int st = idx / ncol, col = idx - st * ncol;
-            const int gc = cb * 8 + col;
-            if (gc < c) {
-                double d = 0;
-                for (int q = 0; q < rpp; ++q) d += sh[(st * rpp + q) * ncol + col];
-                atomicAdd(sums + st * c + gc, d);
-            }
-        }
-        __syncthreads();
-    }
-}
-
-struct OpStats16 {          // (x, x^2)
-    const u16* x; int ldx;
-    __device__ void operator()(int r, int c, float* a, float* b) const {
-        const F8 v = ld8(x + (long long)r * ldx + c);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { a[j] = v.v[j]; b[j] = v.v[j] * v.v[j]; }
-    }
-};
-
-struct OpBnBwd16 {          // (dy', dy' * xhat), dy' = (dy + dy2) * relu-mask
-    const u16* dy; int lddy; const u16* dy2; int lddy2; const u16* x; int ldx;
-    const float* mean; const float* invstd; const float* gamma; const float* beta; int relu;
-    const unsigned char* mask; int c8;          // relu with a residual: the forward's sign bits, one byte per 8 channels
-    __device__ void operator()(int r, int c, float* a, float* b) const {
-        F8 g = ld8(dy + (long long)r * lddy + c);
-        if (dy2) {
-            const F8 g2 = ld8(dy2 + (long long)r * lddy2 + c);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) g.v[j] += g2.v[j];
-        }
-        const F8 xx = ld8(x + (long long)r * ldx + c);
-        const F8 mu = ldf8(mean + c), is = ldf8(invstd + c);
-        unsigned m = 0xffu;
-        if (relu && mask) {
-            m = mask[(long long)r * c8 + (c >> 3)];
-        } else if (relu) {
-            const F8 ga = ldf8(gamma + c), be = ldf8(beta + c);
-            m = 0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) m |= (bn_val(xx.v[j], mu.v[j], is.v[j], ga.v[j], be.v[j]) > 0.f ? 1u : 0u) << j;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float gj = ((m >> j) & 1u) ? g.v[j] : 0.f;
-            a[j] = gj;
-            b[j] = gj * (xx.v[j] - mu.v[j]) * is.v[j];
-        }
-    }
-};
-
-// BatchNorm backward column reduce, the form that runs: the generic kernel above with OpBnBwd16 compiled into a chain of dependent
-// loads (dy -> wait -> dy2 -> wait -> x -> wait -> mask -> the four coefficient vectors again for every row: the ISA had five
-// s_waitcnt vmcnt(0) per row and 2.3 TB/s).  Here the coefficient vectors are loaded once per column block, the loads of FOUR rows
-// (8-12 x 16 bytes per lane) are issued back to back with nothing between them, and the arithmetic follows.
-// HAS2: a second gradient addend; RM: 0 = no ReLU, 1 = sign bytes, 2 = sign recomputed from x and the BatchNorm coefficients.
-template <bool HAS2, int RM>
-__global__ __launch_bounds__(RT) void s16_bnbwd_reduce_kernel(OpBnBwd16 op, int rows, int c, int slices, double* __restrict__ sums, int tpr_max) {
-    __shared__ float sh[RT * 16];
-    const int tid = threadIdx.x;
-    const int c8 = c >> 3;
-    const int tpr = c8 < tpr_max ? c8 : tpr_max;
-    const int rpp = RT / tpr;
-    const int ct = tid % tpr, rl = tid / tpr;
-    const int slice = blockIdx.x;
-    const int per = (rows + slices - 1) / slices;
-    const int r0 = slice * per, r1 = min(rows, r0 + per);
-    for (int cb = blockIdx.y * tpr; cb < c8; cb += gridDim.y * tpr) {
-        const int cc = cb + ct;
-        float acc[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-        if (cc < c8 && rl < rpp) {
-            const int c0 = cc * 8;
-            const F8 mu = ldf8(op.mean + c0), is = ldf8(op.invstd + c0);
-            F8 ga = mu, be = mu;
-            if (RM == 2) { ga = ldf8(op.gamma + c0); be = ldf8(op.beta + c0); }
-            auto fold = [&](const uint4 qg, const uint4 qg2, const uint4 qx, unsigned m) __attribute__((always_inline)) {
-                F8 g = unpack8(qg);
-                if (HAS2) {
-                    const F8 g2 = unpack8(qg2);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) g.v[j] += g2.v[j];
-                }
-                const F8 xx = unpack8(qx);
-                if (RM == 2) {
-                    m = 0;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) m |= (bn_val(xx.v[j], mu.v[j], is.v[j], ga.v[j], be.v[j]) > 0.f ? 1u : 0u) << j;
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float gj = (RM == 0 || ((m >> j) & 1u)) ? g.v[j] : 0.f;
-                    acc[j] += gj;
-                    acc[8 + j] += gj * (xx.v[j] - mu.v[j]) * is.v[j];
-                }
-            };
-            int r = r0 + rl;
-            for (; r + 3 * rpp < r1; r += 4 * rpp) {
-                uint4 qg[4], qg2[4], qx[4];
-                unsigned m[4] = {0xffu, 0xffu, 0xffu, 0xffu};
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const long long row = r + u * rpp;
-                    qg[u] = *reinterpret_cast<const uint4*>(op.dy + row * op.lddy + c0);
-                    if (HAS2) qg2[u] = *reinterpret_cast<const uint4*>(op.dy2 + row * op.lddy2 + c0);
-                    qx[u] = *reinterpret_cast<const uint4*>(op.x + row * op.ldx + c0);
-                    if (RM == 1) m[u] = op.mask[row * op.c8 + cc];
-                }
-                __builtin_amdgcn_sched_barrier(0);       // all loads of the four rows are in flight before the first use (hipcc sinks them to their uses)
-#pragma unroll
-                for (int u = 0; u < 4; ++u) fold(qg[u], HAS2 ? qg2[u] : qg[u], qx[u], m[u]);
-            }
-            for (; r < r1; r += rpp) {
-                const long long row = r;
-                const uint4 qg = *reinterpret_cast<const uint4*>(op.dy + row * op.lddy + c0);
-                const uint4 qg2 = HAS2 ? *reinterpret_cast<const uint4*>(op.dy2 + row * op.lddy2 + c0) : qg;
-                const uint4 qx = *reinterpret_cast<const uint4*>(op.x + row * op.ldx + c0);
-                const unsigned m = RM == 1 ? op.mask[row * op.c8 + cc] : 0xffu;
-                fold(qg, qg2, qx, m);
-            }
-        }
-        const int ncol = tpr * 8;
-        if (rl < rpp) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { sh[(0 * rpp + rl) * ncol + ct * 8 + j] = acc[j]; sh[(1 * rpp + rl) * ncol + ct * 8 + j] = acc[8 + j]; }
-        }
-        __syncthreads();
-        for (int idx = tid; idx < 2 * ncol; idx += RT) {
-            const int st = idx / ncol, col = idx - st * ncol;
-            const int gc = cb * 8 + col;
-            if (gc < c) {
-                double d = 0;
-                for (int q = 0; q < rpp; ++q) d += sh[(st * rpp + q) * ncol + col];
-                atomicAdd(sums + st * c + gc, d);
-            }
-        }
-        __syncthreads();
-    }
-}
-
-struct OpColsum16 {         // (dy, 0)
-    const u16* dy; int ld;
-    __device__ void operator()(int r, int c, float* a, float* b) const {
-        const F8 v = ld8(dy + (long long)r * ld + c);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { a[j] = v.v[j]; b[j] = 0.f; }
-    }
-};
-
-template <class Op>
-int launch_colreduce16(Op op, int rows, int c, double* sums, hipStream_t s) {
-    red_init();
-    const int slices = red_slices(rows, c);
-    const int c8 = c / 8, tpr = c8 < g_red_tpr ? c8 : g_red_tpr;
-    hipLaunchKernelGGL((s16_colreduce_kernel<Op>), dim3(slices, (c8 + tpr - 1) / tpr), dim3(RT), 0, s, op, rows, c, slices, sums, g_red_tpr);
-    return glf::check_launch("s16_colreduce");
-}
-
-int launch_bnbwd_reduce16(const OpBnBwd16& op, int rows, int c, double* sums, hipStream_t s) {
-    red_init();
-    const int slices = red_slices(rows, c);
-    const int c8 = c / 8, tpr = c8 < g_red_tpr ? c8 : g_red_tpr;
-    const dim3 grid(slices, (c8 + tpr - 1) / tpr), block(RT);
-    const int rm = !op.relu ? 0 : (op.mask ? 1 : 2);
-#define GLF_BNR(H2, RM_) hipLaunchKernelGGL((s16_bnbwd_reduce_kernel<H2, RM_>), grid, block, 0, s, op, rows, c, slices, sums, g_red_tpr)
-    if (op.dy2) { if (rm == 0) GLF_BNR(true, 0); else if (rm == 1) GLF_BNR(true, 1); else GLF_BNR(true, 2); }
-    else { if (rm == 0) GLF_BNR(false, 0); else if (rm == 1) GLF_BNR(false, 1); else GLF_BNR(false, 2); }
-#undef GLF_BNR
-    return glf::check_launch("s16_bn_bwd_reduce");
-}
-
-__global__ void f64_to_f32_kernel(const double* __restrict__ src, float* __restrict__ dst, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = (float)src[i];
-}
-
-// ----------------------------------------------------------------------------------------------------------------------
-// BatchNorm apply (+ residual, + ReLU), statistics finished in the kernel
-// ----------------------------------------------------------------------------------------------------------------------
-constexpr int APPLY_MAX_C = 4096;
-__global__ __launch_bounds__(256) void s16_bn_apply_kernel(const u16* __restrict__ x, int ldx, const u16* __restrict__ res, int ldr,
-                                                           u16* __restrict__ y, int ldy, const double* __restrict__ sums, int rows, int c,
-                                                           float eps, float momentum, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           float* __restrict__ mean_io, float* __restrict__ invstd_io, float* rmean, float* rvar,
-                                                           long long* nbt, long long total8, int c8, int relu, unsigned char* __restrict__ mask) {
-    // sums != null (train): every workgroup turns (sum x, sum x^2) into mean / invstd for all channels in LDS; workgroup 0 writes
-    // them to mean_io / invstd_io for the backward pass and updates the running statistics.  sums == null (eval): mean_io /
-    // invstd_io are inputs (glf_bn_eval_coeffs).
-    extern __shared__ __attribute__((aligned(16))) float s_coef[];       // [4][c]: scale, shift (y = x * scale + shift)
-    float* s_sc = s_coef;
-    float* s_sh = s_coef + c;
-    for (int ch = threadIdx.x; ch < c; ch += blockDim.x) {
-        float mf, isf;
-        if (sums) {
-            const double m = sums[ch] / rows;
-            double var = sums[c + ch] / rows - m * m;
-            if (var < 0) var = 0;
-            mf = (float)m; isf = (float)(1.0 / sqrt(var + (double)eps));
-            if (blockIdx.x == 0) {
-                mean_io[ch] = mf; invstd_io[ch] = isf;
-                if (rmean) {
-                    const double unb = rows > 1 ? var * rows / (rows - 1) : var;
-                    rmean[ch] = (1.f - momentum) * rmean[ch] + momentum * (float)m;
-                    rvar[ch] = (1.f - momentum) * rvar[ch] + momentum * (float)unb;
-                }
-            }
-        } else {
-            mf = mean_io[ch]; isf = invstd_io[ch];
-        }
-        s_sc[ch] = mf; s_sh[ch] = isf;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && nbt && sums) *nbt += 1;
-    __syncthreads();
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8; i += (long long)gridDim.x * blockDim.x) {
-        const long long r = i / c8;
-        const int cc = (int)(i - r * c8) * 8;
-        const F8 xx = ld8(x + r * ldx + cc);
-        const F8 mu = ldf8(s_sc + cc), is = ldf8(s_sh + cc), ga = ldf8(gamma + cc), be = ldf8(beta + cc);
-        F8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o.v[j] = bn_val(xx.v[j], mu.v[j], is.v[j], ga.v[j], be.v[j]);
-        if (res) {
-            const F8 rr = ld8(res + r * ldr + cc);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o.v[j] += rr.v[j];
-        }
-        if (mask) {
-            unsigned m = 0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) m |= (o.v[j] > 0.f ? 1u : 0u) << j;
-            mask[i] = (unsigned char)m;
-        }
-        if (relu) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o.v[j] = fmaxf(o.v[j], 0.f);
-        }
-        st8(y + r * ldy + cc, o);
-    }
-}
-
-// dx = gamma*invstd*(dy' - [sum_dy/n + xhat*sum_dyx/n]) ; dres = dy'.  The sums arrive unfinished (doubles [2][c] from the
-// reduction kernel's atomics); workgroup 0 also writes dgamma = sum dy' xhat and dbeta = sum dy'.
-__global__ __launch_bounds__(256) void s16_bnbwd_apply_kernel(const u16* __restrict__ dy, int lddy, const u16* __restrict__ dy2, int lddy2,
-                                                              const u16* __restrict__ x, int ldx, const float* __restrict__ mean,
-                                                              const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              const double* __restrict__ sums, u16* __restrict__ dx, int lddx, u16* __restrict__ dres,
-                                                              int lddres, float* __restrict__ dgamma, float* __restrict__ dbeta, long long total8, int c8, int c,
-                                                              int relu, int training, float inv_n, const unsigned char* __restrict__ mask) {
-    extern __shared__ __attribute__((aligned(16))) float s_k[];        // [2][c]: k1 = gamma invstd, (training) s1 / n, s2 / n packed below
-    float* s_s1 = s_k;
-    float* s_s2 = s_k + c;
-    for (int ch = threadIdx.x; ch < c; ch += blockDim.x) {
-        const float a = (float)sums[ch], b = (float)sums[c + ch];
-        s_s1[ch] = a * inv_n; s_s2[ch] = b * inv_n;
-        if (blockIdx.x == 0) { if (dbeta) dbeta[ch] = a; if (dgamma) dgamma[ch] = b; }
-    }
-    __syncthreads();
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total8; i += (long long)gridDim.x * blockDim.x) {
-        const long long r = i / c8;
-        const int cc = (int)(i - r * c8) * 8;
-        F8 g = ld8(dy + r * lddy + cc);
-        if (dy2) {
-            const F8 g2 = ld8(dy2 + r * lddy2 + cc);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) g.v[j] += g2.v[j];
-        }
-        const F8 is = ldf8(invstd + cc), ga = ldf8(gamma + cc);
-        F8 xx, mu;
-        const bool need_x = training || (relu && !mask);
-        if (need_x) { xx = ld8(x + r * ldx + cc); mu = ldf8(mean + cc); }
-        unsigned m = 0xffu;
-        if (relu && mask) {
-            m = mask[i];
-        } else if (relu) {
-            const F8 be = ldf8(beta + cc);
-            m = 0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) m |= (bn_val(xx.v[j], mu.v[j], is.v[j], ga.v[j], be.v[j]) > 0.f ? 1u : 0u) << j;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) g.v[j] = ((m >> j) & 1u) ? g.v[j] : 0.f;
-        if (dres) st8(dres + r * lddres + cc, g);
-        F8 o;
-        if (training) {
-            const F8 s1 = ldf8(s_s1 + cc), s2 = ldf8(s_s2 + cc);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o.v[j] = ga.v[j] * is.v[j] * (g.v[j] - (s1.v[j] + (xx.v[j] - mu.v[j]) * is.v[j] * s2.v[j]));
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o.v[j] = g.v[j] * ga.v[j] * is.v[j];
-        }
-        st8(dx + r * lddx + cc, o);
-    }
-}
 
 // ----------------------------------------------------------------------------------------------------------------------
 // TPAVI tail z = LayerNorm_C(BN(w) + x): one wavefront per row, C <= 2048
@@ -694,68 +322,6 @@ void softmax16_launch(const float* s, const float* dp, void* out, int64_t rows, 
 }
 
 }  // namespace
-
-extern "C" int glf_s16_colstats(const void* x, int ldx, int rows, int c, double* sums, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(x && sums, GLF_ERR_NULL, "s16_colstats: null argument");
-    GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "s16_colstats: rows must be > 0");
-    REQ_C8(c); REQ_AL(x, "x"); REQ_LD8(ldx, "ldx");
-    return launch_colreduce16(OpStats16{static_cast<const u16*>(x), ldx}, rows, c, sums, glf::S(s));
-}
-
-extern "C" int glf_s16_bn_apply(const void* x, int ldx, const void* residual, int ldr, void* y, int ldy, const double* sums,
-                                int rows, int c, float eps, float momentum, const float* gamma, const float* beta,
-                                float* mean, float* invstd, float* running_mean, float* running_var, int64_t* num_batches_tracked,
-                                int relu, uint8_t* relu_mask, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(x && y && mean && invstd && gamma && beta, GLF_ERR_NULL, "s16_bn_apply: null argument");
-    GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "s16_bn_apply: rows must be > 0");
-    REQ_C8(c); REQ_AL(x, "x"); REQ_AL(y, "y"); REQ_LD8(ldx, "ldx"); REQ_LD8(ldy, "ldy");
-    GLF_REQUIRE(c <= APPLY_MAX_C, GLF_ERR_UNSUPPORTED, "s16_bn_apply: C must be <= %d", APPLY_MAX_C);
-    GLF_REQUIRE((running_mean == nullptr) == (running_var == nullptr), GLF_ERR_NULL, "s16_bn_apply: running_mean/var must both be set or both NULL");
-    if (residual) { REQ_AL(residual, "residual"); REQ_LD8(ldr, "ldr"); }
-    const long long total8 = (long long)rows * (c / 8);
-    hipLaunchKernelGGL(s16_bn_apply_kernel, dim3(stream_grid(total8, 256)), dim3(256), (size_t)2 * c * sizeof(float), glf::S(s),
-                       static_cast<const u16*>(x), ldx, static_cast<const u16*>(residual), ldr, static_cast<u16*>(y), ldy, sums, rows, c, eps, momentum,
-                       gamma, beta, mean, invstd, running_mean, running_var, reinterpret_cast<long long*>(num_batches_tracked), total8, c / 8, relu,
-                       relu_mask);
-    return glf::check_launch("s16_bn_apply");
-}
-
-extern "C" int glf_s16_bn_bwd(const void* dy, int lddy, const void* dy2, int lddy2, const void* x, int ldx,
-                              const float* mean, const float* invstd, const float* gamma, const float* beta,
-                              void* dx, int lddx, void* dres, int lddres, float* dgamma, float* dbeta,
-                              int rows, int c, int relu, int training, double* sums, const uint8_t* relu_mask, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(dy && x && mean && invstd && gamma && dx && sums, GLF_ERR_NULL, "s16_bn_bwd: null argument");
-    GLF_REQUIRE(!relu || beta || relu_mask, GLF_ERR_NULL, "s16_bn_bwd: relu != 0 needs relu_mask or beta (to recompute the sign from x)");
-    GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "s16_bn_bwd: rows must be > 0");
-    REQ_C8(c); REQ_AL(dy, "dy"); REQ_AL(x, "x"); REQ_AL(dx, "dx"); REQ_LD8(lddy, "lddy"); REQ_LD8(ldx, "ldx"); REQ_LD8(lddx, "lddx");
-    GLF_REQUIRE(c <= APPLY_MAX_C, GLF_ERR_UNSUPPORTED, "s16_bn_bwd: C must be <= %d", APPLY_MAX_C);
-    if (dres) { REQ_AL(dres, "dres"); REQ_LD8(lddres, "lddres"); }
-    if (dy2) { REQ_AL(dy2, "dy2"); REQ_LD8(lddy2, "lddy2"); }
-    const OpBnBwd16 op{static_cast<const u16*>(dy), lddy, static_cast<const u16*>(dy2), lddy2, static_cast<const u16*>(x), ldx, mean, invstd, gamma, beta,
-                       relu, relu_mask, c / 8};
-    if (int rc = launch_bnbwd_reduce16(op, rows, c, sums, glf::S(s))) return rc;
-    const long long total8 = (long long)rows * (c / 8);
-    hipLaunchKernelGGL(s16_bnbwd_apply_kernel, dim3(stream_grid(total8, 256)), dim3(256), (size_t)2 * c * sizeof(float), glf::S(s),
-                       static_cast<const u16*>(dy), lddy, static_cast<const u16*>(dy2), lddy2, static_cast<const u16*>(x), ldx, mean, invstd, gamma, beta,
-                       sums, static_cast<u16*>(dx), lddx, static_cast<u16*>(dres), lddres, dgamma, dbeta, total8, c / 8, c, relu, training,
-                       1.0f / (float)rows, relu_mask);
-    return glf::check_launch("s16_bn_bwd_apply");
-}
-
-extern "C" int glf_s16_colsum(const void* dy, int lddy, float* db, int rows, int c, double* workspace, glf_stream_t s) {
-    if (int rc = glf::ensure_init()) return rc;
-    GLF_REQUIRE(dy && db && workspace, GLF_ERR_NULL, "s16_colsum: null argument");
-    GLF_REQUIRE(rows > 0, GLF_ERR_BAD_SHAPE, "s16_colsum: rows must be > 0");
-    REQ_C8(c); REQ_AL(dy, "dy"); REQ_LD8(lddy, "lddy");
-    hipError_t e = hipMemsetAsync(workspace, 0, (size_t)2 * c * sizeof(double), glf::S(s));
-    if (e != hipSuccess) return glf::fail(GLF_ERR_LAUNCH, "s16_colsum: hipMemsetAsync: %s", hipGetErrorString(e));
-    if (int rc = launch_colreduce16(OpColsum16{static_cast<const u16*>(dy), lddy}, rows, c, workspace, glf::S(s))) return rc;
-    hipLaunchKernelGGL(f64_to_f32_kernel, dim3((c + 255) / 256), dim3(256), 0, glf::S(s), workspace, db, c);
-    return glf::check_launch("s16_colsum");
-}
 
 extern "C" int glf_s16_bn_res_ln_fwd(const void* w, const void* x, const float* bn_mean, const float* bn_invstd, const float* bn_gamma,
                                      const float* bn_beta, const float* ln_gamma, const float* ln_beta, float ln_eps, void* z,

@@ -69,8 +69,13 @@ template <> struct Stream<float, 1> {
     static __device__ __forceinline__ FV<1> ld(const float* p) { return {{*p}}; }
     static __device__ __forceinline__ void st(float* p, const FV<1>& o) { *p = o.v[0]; }
 };
+// (The 16-byte forms also split a load into Raw ldraw(p) and unpack(Raw): a kernel that wants several rows' loads in flight issues
+// the raw loads back to back and unpacks behind them.)
 template <> struct Stream<float, 4> {
-    static __device__ __forceinline__ FV<4> ld(const float* p) { const float4 q = *reinterpret_cast<const float4*>(p); return {{q.x, q.y, q.z, q.w}}; }
+    typedef float4 Raw;
+    static __device__ __forceinline__ Raw ldraw(const float* p) { return *reinterpret_cast<const float4*>(p); }
+    static __device__ __forceinline__ FV<4> unpack(const Raw q) { return {{q.x, q.y, q.z, q.w}}; }
+    static __device__ __forceinline__ FV<4> ld(const float* p) { return unpack(ldraw(p)); }
     static __device__ __forceinline__ void st(float* p, const FV<4>& o) { *reinterpret_cast<float4*>(p) = make_float4(o.v[0], o.v[1], o.v[2], o.v[3]); }
 };
 template <> struct Stream<float, 8> {
@@ -81,6 +86,9 @@ template <> struct Stream<u16, 1> {
     static __device__ __forceinline__ void st(u16* p, const FV<1>& o) { *p = f2bf(o.v[0]); }
 };
 template <> struct Stream<u16, 8> {
+    typedef uint4 Raw;
+    static __device__ __forceinline__ Raw ldraw(const u16* p) { return *reinterpret_cast<const uint4*>(p); }
+    static __device__ __forceinline__ F8 unpack(const Raw q) { return unpack8(q); }
     static __device__ __forceinline__ F8 ld(const u16* p) { return ld8(p); }
     static __device__ __forceinline__ void st(u16* p, const F8& o) { st8(p, o); }
 };

@@ -1,5 +1,5 @@
 """Helpers of tests/test_gpu_s16_stream.py and tests/test_s16_stream_ref_cpu.py: guarded buffers, the two input families, and the
-float64 / magnitude references of the 16-bit-storage streaming kernels (csrc/s16_ops.hip).  A plain module, not a conftest.
+float64 / magnitude references of the 16-bit-storage streaming kernels (csrc/norm.hip and csrc/s16_ops.hip).  A plain module, not a conftest.
 
 Inputs are float64 tensors whose values bf16 holds exactly (vectors of coefficients: fp32).  Two families:
   integer -- x, w in {-3..3}; dy, dy2, dz, residual in {-2..2}; given mean in {-1, 0, 1}; given invstd, gamma, LN gamma in
@@ -13,7 +13,7 @@ every input and every partial sum replaced by its absolute value and k is the nu
 fp32 (and double) outputs: |got - ref| <= d; bf16 outputs: bf16_rne(ref - d) <= got <= bf16_rne(ref + d).  -ffp-contract=fast may
 fuse a multiply with the following add: that removes roundings, never adds one.  x and mean are exact fp32 operands of x - mean,
 so its one rounding is relative to |x - mean| (not to |x| + |mean|): that is the magnitude of this partial sum (with one row the
-batch mean IS x, the difference is zero, and BN(x) = beta without any error).  k per output, counted in s16_ops.hip:
+batch mean IS x, the difference is zero, and BN(x) = beta without any error).  k per output, counted in norm.hip / s16_ops.hip:
 
   colstats sum x       k = rpt                          x is exact in fp32; rpt adds of one thread (below); LDS fold and atomics in double
   colstats sum x^2     k = rpt                          a bf16 square has 16 bits: exact in fp32
@@ -42,7 +42,7 @@ batch mean IS x, the difference is zero, and BN(x) = beta without any error).  k
   tail dln_gamma       k = 8 + 16 + 3 + 1 = 28          dz * uhat (7 + 1); 16 rows of a wave; three LDS folds; (float) of the double slab sum
   tail dln_beta        k = 16 + 3 + 1 = 20              exact in the integer family
   sum_rows y           k = ceil(p / 8) + 7 + 1          a row lane's adds; seven LDS folds; * scale  (exact in the integer family, scale 0.5)
-rpt = rows one thread of a reduction adds = ceil(ceil(rows / slices) / (256 / threads-per-row)) (red_geometry mirrors red_slices).
+rpt = rows one thread of a reduction adds = ceil(ceil(rows / slices) / (256 / threads-per-row)) (red_geometry mirrors red_geom of csrc/col_reduce.h).
 
 ReLU signs: an element whose float64 pre-ReLU value v has |v| <= d(v) is "unsure": the fp32 sign may legitimately differ.  Mask
 bits and ReLU-dependent outputs are compared on the others; a column sum's d grows by the magnitude of its unsure terms.  A case
@@ -71,7 +71,7 @@ LN_NV, LN_ROWS, APPLY_MAX_C, LN_MAX_C = 4, 64, 4096, 2048
 ROWS = [1, 5, 70, 297, 1031, 4100]
 CHANNELS = [8, 24, 72, 128, 136, 2048, 4096]
 BN_SHAPES = [(r, c) for r in ROWS for c in CHANNELS if r * c <= 1031 * 4096 or (r, c) == (4100, 2048)]
-BIG_SHAPE = (8500, 4096)                                   # the slice cap of red_slices
+BIG_SHAPE = (8500, 4096)                                   # the slice cap of red_geom<8>
 # row-stride pads per strided operand, in argument order: none, all, and each operand alone -- every pair of operands has
 # different strides in some pattern, so a kernel that indexes one operand with another's stride cannot pass
 def _pad_patterns(names):
@@ -289,25 +289,26 @@ def close(a, b, tol_):
     return bool(((a - b).abs() <= tol_ + tol_ * b.abs()).all())
 
 
-def sign_bytes(positive):
-    """[rows][c] bool -> [rows][c / 8] bytes, bit j of byte i = channel 8 i + j"""
+def sign_bytes(positive, w=8):
+    """[rows][c] bool -> [rows][c / w] bytes, bit j of byte i = channel w i + j (w = 8: bf16 storage, w = 4: fp32 storage)"""
     rows, c = positive.shape
-    w = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32, device=positive.device)
-    return (positive.reshape(rows, c // 8, 8).to(torch.int32) * w).sum(-1).to(torch.uint8).contiguous()
+    bit = torch.tensor([1 << j for j in range(w)], dtype=torch.int32, device=positive.device)
+    return (positive.reshape(rows, c // w, w).to(torch.int32) * bit).sum(-1).to(torch.uint8).contiguous()
 
 
 def unsure_share(unsure):
     return float(unsure.double().mean())
 
 
-# ------------------------------------------------------------------------------------- reduction geometry (red_slices)
-def red_geometry(rows, c):
-    """(threads per row, rows per pass, slices, rows per slice, rows one thread adds) of the column reductions"""
-    c8 = c // 8 if c > 8 else 1
-    tpr = min(c8, 16)
+# --------------------------------------------------------------------------- reduction geometry (col_reduce.h: red_geom<W>)
+def red_geometry(rows, c, w=8):
+    """(threads per row, rows per pass, slices, rows per slice, rows one thread adds) of the single-stage column reductions at
+    access width w: 8 elements per 16-byte access for bf16 storage, 4 for fp32"""
+    cw = c // w if c > w else 1
+    tpr = min(cw, 16)
     rpp = 256 // tpr
     s = (rows + 16 * rpp - 1) // (16 * rpp)
-    cblocks = (c8 + tpr - 1) // tpr
+    cblocks = (cw + tpr - 1) // tpr
     cap = max(1, 1024 // cblocks)
     slices = max(1, min(s, cap))
     per = (rows + slices - 1) // slices

@@ -1,4 +1,4 @@
-"""GPU: the 16-bit-storage streaming kernels (csrc/s16_ops.hip) called through their C entry points and judged element by element
+"""GPU: the 16-bit-storage streaming kernels (csrc/norm.hip, csrc/s16_ops.hip) called through their C entry points and judged element by element
 against float64 on the same bf16 inputs, every output in a guarded buffer: glf_s16_colstats, glf_s16_colsum, glf_s16_bn_apply (train
 and eval), glf_s16_bn_bwd (all six reduce instantiations x training x dres), glf_s16_bn_res_ln_fwd / _bwd, glf_s16_sum_rows,
 glf_s16_cast, and their refusals.
@@ -253,7 +253,7 @@ def test_bn_bwd_all_reduce_instantiations(L, fam, rows, c, pads):
 
 
 def test_bn_bwd_and_colstats_at_the_slice_cap(L):
-    """8 500 x 4 096: red_slices caps the grid at 1 024 / 32 column blocks = 32 slices of 266 rows (17 rows per thread).  This case
+    """8 500 x 4 096: red_geom<8> caps the grid at 1 024 / 32 column blocks = 32 slices of 266 rows (17 rows per thread).  This case
     is about the reduce half: sums, dbeta, dgamma and dres are gated for equality; dx is held under guards (intact, written) and
     deliberately NOT compared here -- the apply half has no path that depends on the slice count, and the shapes above gate it."""
     lib, check = L
@@ -282,6 +282,76 @@ def test_bn_bwd_and_colstats_at_the_slice_cap(L):
     exact(dg.t[0], b.s2, False, "dgamma at the slice cap", "bn_bwd dgamma")
     exact(bs.t[0], torch.cat([b.s1, b.s2]), False, "sums at the slice cap", "bn_bwd sums")
     exact(dres.dense(), b.g, True, "dres at the slice cap", "bn_bwd dres")
+
+
+# ------------------------------------------------------------------- the same reduce body on fp32 storage (glf_bn_bwd, fused form)
+def _bwd_call32(lib, check, dy, dy2, x, V, rows, c, rm, training, want_dres, mask_bytes):
+    """glf_bn_bwd in its two-launch form (fused_sums: 2 c doubles of sums, then 2 c floats of maxima) on dense fp32 tensors"""
+    dx, dres = Guarded(rows, c), (Guarded(rows, c) if want_dres else None)
+    dg, db = Guarded(1, c), Guarded(1, c)
+    fs = Guarded(1, 3 * c, dtype=F64).fill(torch.zeros(1, 3 * c))
+    check(lib.glf_bn_bwd(ptr(dy), c, ptr(x), c, None, c, ptr(V.mean), ptr(V.invstd), ptr(V.gamma), ptr(V.beta), dx.ptr, c, ptr(dres), c,
+                         dg.ptr, db.ptr, rows, c, int(rm != 0), training, None, None, 0, ptr(mask_bytes) if rm == 1 else None, ptr(dy2), c,
+                         fs.ptr, None), "bn_bwd")
+    sync()
+    guards(dx, dres, dg, db, fs, what=f"fp32 bn_bwd has2 {dy2 is not None} rm {rm} training {training} dres {want_dres}")
+    assert not bool(fs.t[0, 2 * c:].any()), "the maxima were not asked for"
+    return dx, dres, dg, db, fs.t[0, :2 * c]
+
+
+def test_bn_bwd_fp32_storage_at_the_slice_cap(L):
+    """4 100 x 4 096 on fp32 storage: red_geom<4> caps the grid at 1 024 / 64 column blocks = 16 slices of 257 rows -- 17 rows per
+    thread, four unrolled trips and a one-row tail -- with the fan-in pair, the sign recomputed from x and dres written by the
+    reduce pass.  As at the bf16 cap, this is about the reduce half: sums, dbeta, dgamma and dres are gated for equality."""
+    lib, check = L
+    rows, c = 4100, 4096
+    assert R.red_geometry(rows, c, 4)[2:] == (16, 257, 17)
+    g = torch.Generator(device=DEV).manual_seed(72)
+    ri = lambda lo, hi: torch.randint(lo, hi + 1, (rows, c), generator=g, device=DEV).to(F32)
+    xf, dyf, dy2f = ri(-3, 3), ri(-2, 2), ri(-2, 2)
+    x, dy, dy2 = xf.double(), dyf.double(), dy2f.double()
+    I = R.bn_inputs("int", 5, c)                               # its coefficient vectors
+    v, vmag = R.bn_fwd_ref(x, I.mean, I.invstd, I.gamma, I.beta)
+    assert not bool(R.unsure_of(v, vmag, R.K_V_NORES).any())
+    b = R.bn_bwd_ref(dy, dy2, x, I.mean, I.invstd, (v > 0).double())
+    R.assert_exact(b.s1mag, 4 * b.s2mag)
+    V = R.Bag(mean=vec32(I.mean), invstd=vec32(I.invstd), gamma=vec32(I.gamma), beta=vec32(I.beta))
+    dx, dres, dg, db, sums = _bwd_call32(lib, check, dyf, dy2f, xf, V, rows, c, 2, 1, True, None)
+    exact(db.t[0], b.s1, False, "fp32 dbeta at the slice cap", "bn_bwd fp32 dbeta")
+    exact(dg.t[0], b.s2, False, "fp32 dgamma at the slice cap", "bn_bwd fp32 dgamma")
+    exact(sums, torch.cat([b.s1, b.s2]), False, "fp32 sums at the slice cap", "bn_bwd fp32 sums")
+    exact(dres.dense(), b.g, False, "fp32 dres at the slice cap", "bn_bwd fp32 dres")
+
+
+@pytest.mark.parametrize("rows,c", [(5, 8), (70, 72), (297, 136), (1031, 264)])
+def test_bn_bwd_reduce_is_one_body_for_both_storages(L, rows, c):
+    """The integer family (every value exact in bf16, every sum exact in fp32) through glf_bn_bwd's fused form and glf_s16_bn_bwd:
+    one reduce body at four and at eight elements per access, mask bytes built at four and at eight signs per byte.  (5, 8): one
+    lane per row at eight per access; (70, 72): nine column groups, fewer than a block; (297, 136): a second, ragged column block
+    at eight per access, three at four; (1031, 264).  sums, dbeta and dgamma are equal bit for bit across storages, dres after the
+    cast -- with and without dres, which on fp32 storage decides whether the reduce pass writes it."""
+    lib, check = L
+    I = R.bn_inputs("int", rows, c)
+    v, vmag = R.bn_fwd_ref(I.x, I.mean, I.invstd, I.gamma, I.beta)
+    assert not bool(R.unsure_of(v, vmag, R.K_V_NORES).any())
+    pos = {2: v > 0, 1: (v + I.res) > 0}
+    V = R.Bag(mean=vec32(I.mean), invstd=vec32(I.invstd), gamma=vec32(I.gamma), beta=vec32(I.beta))
+    B = R.Bag(V, rows=rows, c=c, pads=(0,) * 5, dyb=put16(I.dy), dy2b=put16(I.dy2), xb=put16(I.x))
+    x32, dy32, dy232 = I.x.float(), I.dy.float(), I.dy2.float()
+    for has2 in (False, True):
+        for rm in (0, 1, 2):
+            b = R.bn_bwd_ref(I.dy, I.dy2 if has2 else None, I.x, I.mean, I.invstd, None if rm == 0 else pos[rm].double())
+            R.assert_exact(b.s1mag, 4 * b.s2mag)
+            m8, m4 = (R.sign_bytes(pos[1], 8), R.sign_bytes(pos[1], 4)) if rm == 1 else (None, None)
+            for want_dres in (True, False):
+                what = f"{rows} x {c} has2 {has2} rm {rm} dres {want_dres}"
+                _, dres16, dg16, db16, s16 = _bwd_call(lib, check, B, has2, rm, 1, want_dres, m8)
+                _, dres32, dg32, db32, s32 = _bwd_call32(lib, check, dy32, dy232 if has2 else None, x32, V, rows, c, rm, 1, want_dres, m4)
+                assert torch.equal(s16.t[0], s32) and same_bits(dg16.t[0], dg32.t[0]) and same_bits(db16.t[0], db32.t[0]), what + ": sums across storages"
+                exact(s32, torch.cat([b.s1, b.s2]), False, what + " sums", "bn_bwd fp32 sums")
+                if want_dres:
+                    assert same_bits(dres32.dense().to(BF), dres16.dense()), what + ": dres across storages"
+                    exact(dres32.dense(), b.g, False, what + " dres", "bn_bwd fp32 dres")
 
 
 # -------------------------------------------------------------------------------------------------------------- TPAVI tail

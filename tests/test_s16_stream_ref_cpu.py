@@ -93,6 +93,10 @@ def test_reduction_geometry_covers_the_thread_mappings():
     assert R.red_geometry(*R.BIG_SHAPE)[2] == 32 and R.red_geometry(8500, 4096)[4] == 17     # the slice cap: 1 024 / 32 column blocks
     assert R.red_geometry(4100, 2048)[2] == 17 and R.red_geometry(1, 8)[2:] == (1, 1, 1)
     assert {R.red_geometry(r, 128)[2] for r in R.ROWS} == {1, 2, 5, 17}          # several slices with a ragged last one
+    # fp32 storage, four elements per access: 64 column blocks cap 4 100 rows at 16 slices of 257 rows -- 17 rows per thread, four
+    # unrolled trips and a one-row tail
+    assert R.red_geometry(4100, 4096, 4) == (16, 16, 16, 257, 17)
+    assert [R.red_geometry(297, c, 4)[0] for c in (4, 8, 72, 136)] == [1, 2, 16, 16]
     assert all(r * c <= 1031 * 4096 or (r, c) == (4100, 2048) for r, c in R.BN_SHAPES) and len(R.BN_SHAPES) == 41
 
 
