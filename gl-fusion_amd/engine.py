@@ -20,7 +20,11 @@ import torch
 from . import ops
 from .ddp import GradAllReducer, all_reduce_counts
 from .optim import SGD, Adam
-from .models import Global_and_Local
+from .models import Global_and_Local, baseline_unet, multiview_unet
+
+# config['net']['model'] -> class; the U-Net baselines return (mask, None, None, x5): no backbone mask, no fusion features
+MODELS = {"Global_and_Local": Global_and_Local, "baseline_unet": baseline_unet, "multiview_unet": multiview_unet}
+NO_FUSION_FEATURES = ("baseline_unet", "multiview_unet")
 
 
 class SyntheticClips:
@@ -177,7 +181,11 @@ class Trainer:
         self.fold_bn = bool(tr.get("fold_bn", False))
         # config['train']['fold_bn_s16'] (absent = False): the same for 16-bit storage (ops.set_fold_bn_s16; takes effect under "bf16" only)
         self.fold_bn_s16 = bool(tr.get("fold_bn_s16", False))
-        self.model = Global_and_Local(view_num=self.view_num).to(self.device)  # main.py:150
+        # config['net']['model'] (absent = "Global_and_Local", main.py:150): which of MODELS the Trainer builds
+        self.model_name = config["net"].get("model", "Global_and_Local")
+        if self.model_name not in MODELS:
+            raise ValueError(f"glfusion_amd: config['net']['model'] = {self.model_name!r}; the Trainer builds one of {sorted(MODELS)}")
+        self.model = MODELS[self.model_name](view_num=self.view_num).to(self.device)
         opt = config["net"]["opt"]
         name = opt.get("opt_name", "Adam")
         if name == "SGD":
@@ -216,6 +224,7 @@ class Trainer:
         """main.py:213-235: second forward on an unlabelled clip [T,1,H,W] per view, global-fusion features summed
         over (h, w), seg_cycle (or dense_seg_cycle) per view with target_region 16, cyc_off 2, chunk_size 3,
         temperature 10."""
+        self._require_fusion_features("cycle_loss")
         _, _, feat_out, _ = self.model(video)
         feats = ops.pooled_fusion_features(feat_out)
         total = None
@@ -277,7 +286,14 @@ class Trainer:
         self.optimizer.step()
         return loss.detach(), pred_frames
 
+    def _require_fusion_features(self, what: str) -> None:
+        if self.model_name in NO_FUSION_FEATURES:
+            raise ValueError(f"glfusion_amd: {what} needs the model's fusion features (its third output), and {self.model_name} "
+                             "returns none: train it with is_cycle=False")
+
     def train(self, is_backbone: bool = False, is_cycle: bool = True):
+        if is_cycle:
+            self._require_fusion_features("Trainer.train(is_cycle=True)")
         for epoch in range(self.latest_epoch, self.config["train"]["num_epochs"]):
             self.model.train()
             for imgs, masks in self.loader:
@@ -327,7 +343,7 @@ class Trainer:
             for v in self.view_num:
                 imgs[v], masks[v] = _data.prepare_frames(sample[v][0], sample[v][1], v, train=False)
             out = self.model(imgs)
-            pred = out[0] if is_fuse else out[1]
+            pred = out[0] if (is_fuse or out[1] is None) else out[1]     # the U-Net baselines have one mask only
             for v in self.test_view:
                 counts[v] += part_overlap_counts(pred[v], masks[v])
                 loss4view[v] += float(ops.bce_with_logits_sum(pred[v], masks[v]))
@@ -384,7 +400,7 @@ class Trainer:
             for v in self.view_num:
                 imgs[v], masks[v] = _data.prepare_frames(sample[v][0], sample[v][1], v, train=False)
             out = self.model(imgs)
-            pred = out[0] if is_fuse else out[1]
+            pred = out[0] if (is_fuse or out[1] is None) else out[1]     # the U-Net baselines have one mask only
             manifest[pid] = {}
             for v in self.test_view:
                 if on_clip is not None:
@@ -445,7 +461,7 @@ class Trainer:
                     imgs = {v: t[:frames] for v, t in imgs.items()}
                     masks = {v: t[:frames] for v, t in masks.items()}
                     out = self.model(imgs)
-                    pred = out[0] if is_fuse else out[1]
+                    pred = out[0] if (is_fuse or out[1] is None) else out[1]     # the U-Net baselines have one mask only
                     for v in self.test_view:
                         counts[v] += part_overlap_counts(pred[v], masks[v])
                         loss4view[v] += float(ops.bce_with_logits_sum(pred[v], masks[v]))

@@ -32,6 +32,8 @@ class Conv2d(nn.Conv2d):
         stride, pad, dil = self._geom()
         if self.in_channels == 1 and self.kernel_size == (7, 7) and stride == 1 and dil == 1:
             return ops.stem7x7(x, self.weight, self.bias, pad)          # models/_utils.py:192
+        if self.in_channels == 1 and self.kernel_size == (3, 3) and stride == 1 and pad == 1 and dil == 1:
+            return ops.conv3x3_c1(x, self.weight, self.bias)            # conv_block(1, 64).conv[0], ours.py:2389
         if self.in_channels % 4 != 0:
             raise RuntimeError(f"glfusion_amd: conv with Cin={self.in_channels} is not on the path")
         return ops.conv2d(x, self.weight, self.bias, stride, pad, dil, colstats)
@@ -55,9 +57,23 @@ class ReLU(nn.ReLU):
 
 class MaxPool2d(nn.MaxPool2d):
     def forward_nhwc(self, x):
-        if (_one(self.kernel_size), _one(self.stride), _one(self.padding), _one(self.dilation)) != (3, 2, 1, 1) or self.ceil_mode:
-            raise RuntimeError("glfusion_amd: only MaxPool2d(3, stride=2, padding=1) is on the path")
+        geom = (_one(self.kernel_size), _one(self.stride), _one(self.padding), _one(self.dilation))
+        if geom == (2, 2, 0, 1) and not self.ceil_mode:
+            return ops.maxpool2x2s2(x)                                  # the U-Net baselines, ours.py:2439
+        if geom != (3, 2, 1, 1) or self.ceil_mode:
+            raise RuntimeError("glfusion_amd: only MaxPool2d(3, stride=2, padding=1) and MaxPool2d(2, stride=2) are on the path")
         return ops.maxpool3x3s2(x)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return ops.from_nhwc(self.forward_nhwc(ops.to_nhwc(x)))
+
+
+class Upsample(nn.Upsample):
+    def forward_nhwc(self, x):
+        sf = self.scale_factor
+        if self.size is not None or sf is None or self.mode != "nearest" or any(float(e) != 2.0 for e in (sf if isinstance(sf, (tuple, list)) else (sf,))):
+            raise RuntimeError("glfusion_amd: only Upsample(scale_factor=2), nearest, is on the path")
+        return ops.upsample2x(x)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return ops.from_nhwc(self.forward_nhwc(ops.to_nhwc(x)))

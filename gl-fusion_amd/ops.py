@@ -2125,6 +2125,146 @@ def maxpool3x3s2(x):
     return MaxPool3x3s2Fn.apply(x)
 
 
+# ----------------------------------------------------------------------------------------
+# the streaming pieces of the U-Net baselines (ours.py:2385-2625; csrc/unet_ops.hip)
+# ----------------------------------------------------------------------------------------
+def _dense_act(x, name: str):
+    """A streaming node reads its input as values: a packed-only activation (a BatchNorm output written for ONE convolution) has none."""
+    if packed_only(x):
+        raise RuntimeError(f"glfusion_amd: a packed-only activation reached {name}, which cannot consume it")
+    return _contig(_chk(x, name + " input", None))
+
+
+class Conv3x3C1Fn(Function):
+    """Conv2d(1, 64, 3, stride 1, padding 1) + bias on an fp32 [N,H,W,1] image; the result is fp32, or bf16 under 16-bit storage
+    (the entry into the 16-bit domain, as for the stem)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, out16: bool):
+        _chk(x, "conv3x3_c1 input"); _chk(weight, "conv3x3_c1 weight")
+        x = _contig(x)                                  # [N,H,W,1]
+        n, h, w, _ = x.shape
+        cout = weight.shape[0]
+        y = torch.empty(n, h, w, cout, dtype=BF if out16 else torch.float32, device=x.device)
+        _launch("conv3x3_c1_fwd", y, x, _contig(weight.detach()), bias, y, n, h, w, cout)
+        ctx.save_for_backward(x)
+        ctx.cfg = (n, h, w, cout, tuple(weight.shape), bias is not None)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        n, h, w, cout, wshape, has_bias = ctx.cfg
+        if ctx.needs_input_grad[0]:
+            raise RuntimeError("glfusion_amd: gradient w.r.t. the input image is not on the path (stem dgrad not built)")
+        dy = _contig(dy)
+        dw = torch.empty(wshape, dtype=torch.float32, device=dy.device)
+        db = torch.empty(cout, dtype=torch.float32, device=dy.device) if has_bias else None
+        part = torch.empty(int(lib.glf_conv3x3_c1_wgrad_workspace(n, h, w, cout)), dtype=torch.float32, device=dy.device)
+        _launch("conv3x3_c1_wgrad", dy, x, dy, dw, db, part, part.numel(), n, h, w, cout)
+        return None, dw, db, None
+
+
+def conv3x3_c1(x, weight, bias):
+    return Conv3x3C1Fn.apply(x, weight, bias, _S16[0])
+
+
+class MaxPool2x2s2Fn(Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = _dense_act(x, "maxpool2x2s2")
+        n, h, w, c = x.shape
+        y = torch.empty(n, h // 2, w // 2, c, dtype=x.dtype, device=x.device)
+        idx = torch.empty(n, h // 2, w // 2, c, dtype=torch.uint8, device=x.device)
+        _launch("maxpool2x2s2_fwd", x, x, y, idx, n, h, w, c)
+        amax_bound(y, [x])                                  # a window maximum never exceeds the input's largest magnitude
+        ctx.save_for_backward(idx)
+        ctx.cfg = (n, h, w, c)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        n, h, w, c = ctx.cfg
+        dy = _contig(dy)
+        dx = torch.empty(n, h, w, c, dtype=dy.dtype, device=dy.device)      # the kernel writes every element, zeros included
+        _launch("maxpool2x2s2_bwd", dy, dy, idx, dx, n, h, w, c)
+        return dx
+
+
+def maxpool2x2s2(x):
+    return MaxPool2x2s2Fn.apply(x)
+
+
+class Upsample2xFn(Function):
+    """nn.Upsample(scale_factor=2), nearest."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _dense_act(x, "upsample2x")
+        n, h, w, c = x.shape
+        y = torch.empty(n, 2 * h, 2 * w, c, dtype=x.dtype, device=x.device)
+        _launch("upsample2x_fwd", x, x, y, n, h, w, c)
+        amax_bound(y, [x])                                  # the same values, four times
+        ctx.cfg = (n, h, w, c)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        n, h, w, c = ctx.cfg
+        dy = _contig(dy)
+        dx = torch.empty(n, h, w, c, dtype=dy.dtype, device=dy.device)
+        _launch("upsample2x_bwd", dy, dy, dx, n, h, w, c)
+        return dx
+
+
+def upsample2x(x):
+    return Upsample2xFn.apply(x)
+
+
+class ConcatChannelsFn(Function):
+    """torch.cat((a, b), dim=1) on channels-last tensors [..., Ca], [..., Cb] -> [..., Ca + Cb]; a source may be a column slice of a
+    wider channels-last buffer."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        for t in (a, b):
+            if packed_only(t):
+                raise RuntimeError("glfusion_amd: a packed-only activation reached concat_channels, which cannot consume it")
+        _chk(a, "concat input", None); _chk(b, "concat input", a.dtype)
+        if a.shape[:-1] != b.shape[:-1]:
+            raise RuntimeError(f"concat_channels: leading extents differ ({tuple(a.shape)} vs {tuple(b.shape)})")
+        am = [getattr(a, "_glf_amax", None), getattr(b, "_glf_amax", None)]
+        (ar, lda), (br, ldb) = _rows_view(a), _rows_view(b)
+        for t, src, h in ((ar, a, am[0]), (br, b, am[1])):          # a copy made for the kernel keeps the source's known maximum
+            if t is not src and h is not None and h[0] == src._version:
+                set_amax(t, h[2])
+        ca, cb = int(a.shape[-1]), int(b.shape[-1])
+        rows = a.numel() // ca
+        y = torch.empty(tuple(a.shape[:-1]) + (ca + cb,), dtype=a.dtype, device=a.device)
+        _launch("concat2_fwd", y, ar, lda, br, ldb, y, rows, ca, cb)
+        amax_bound(y, [ar, br])                             # the larger of the two sources' maxima
+        ctx.cfg = (tuple(a.shape), tuple(b.shape), rows, ca, cb)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        ashape, bshape, rows, ca, cb = ctx.cfg
+        dy = _contig(dy)
+        da = torch.empty(ashape, dtype=dy.dtype, device=dy.device)
+        db = torch.empty(bshape, dtype=dy.dtype, device=dy.device)
+        _launch("concat2_bwd", dy, dy, da, db, rows, ca, cb)
+        return da, db
+
+
+def concat_channels(a, b):
+    return ConcatChannelsFn.apply(a, b)
+
+
 class AvgPoolFn(Function):
     """AdaptiveAvgPool2d(1): [N,H,W,C] -> fp32 [N,1,1,C].  From a bf16 map too: the ASPP pooled branch (deeplabv3.py:123-135) stays
     fp32 up to its broadcast -- its BatchNorm normalises over the N per-frame averages, which differ by less than a few bf16 steps."""

@@ -734,6 +734,46 @@ int glf_bn_bwd(const float* dy, int lddy, const float* x, int ldx, const float* 
  * aligned here, 8-byte aligned for the glf_s16_* pair (forward and backward refuse anything else). */
 int glf_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* idx, int n, int h, int w, int c, glf_stream_t s);
 int glf_maxpool3x3s2_bwd(const float* dy, const uint8_t* idx, float* dx, int n, int h, int w, int c, glf_stream_t s);
+/* ---------------------------------------------------------------------------------------
+ * The streaming pieces of the U-Net baselines (ours.py:2385-2625; unet_ops.hip).  Channels-last, 16-byte accesses: every tensor
+ * 16-byte aligned, C % 4 == 0 (fp32) / C % 8 == 0 (the glf_s16_* forms, bf16 tensors).  fp32 arithmetic, bf16 rounded once at
+ * the store.  No atomics: results are bit-identical from call to call.  Arguments are checked before any launch: GLF_ERR_NULL,
+ * GLF_ERR_UNSUPPORTED (Cout), GLF_ERR_BAD_SHAPE (extents, channel counts, strides, alignment), GLF_ERR_WORKSPACE.
+ *
+ * Conv2d(1, 64, 3, stride 1, padding 1) + bias (conv_block(1, 64).conv[0], ours.py:2389): x [N][H][W] fp32, w [Cout][9],
+ * bias [Cout] or NULL, y [N][H][W][Cout] (fp32, or bf16 for glf_s16_*: the entry into the 16-bit domain).  Cout must be 64.
+ * wgrad: dW [Cout][9] and db [Cout] (db may be NULL) from dy [N][H][W][Cout]; `partial` is a workspace of partial_floats >=
+ * glf_conv3x3_c1_wgrad_workspace() floats (one [10][Cout] block of partial sums per 1024 pixels, folded in a fixed order).
+ * There is no dgrad: the gradient with respect to the image is not on the path. */
+int glf_conv3x3_c1_fwd(const float* x, const float* w, const float* bias, float* y, int n, int h, int wdt, int cout, glf_stream_t s);
+int glf_s16_conv3x3_c1_fwd(const float* x, const float* w, const float* bias, void* y, int n, int h, int wdt, int cout, glf_stream_t s);
+size_t glf_conv3x3_c1_wgrad_workspace(int n, int h, int wdt, int cout);
+int glf_conv3x3_c1_wgrad(const float* x, const float* dy, float* dw, float* db, float* partial, size_t partial_floats,
+                         int n, int h, int wdt, int cout, glf_stream_t s);
+int glf_s16_conv3x3_c1_wgrad(const float* x, const void* dy, float* dw, float* db, float* partial, size_t partial_floats,
+                             int n, int h, int wdt, int cout, glf_stream_t s);
+/* nn.MaxPool2d(2, 2), floor mode: x [N][H][W][C] -> y [N][H/2][W/2][C], H, W >= 2; a trailing odd row / column is not read.
+ * idx (uint8, shape of y; 4-byte aligned, 8-byte for glf_s16_*) records the winner 2 * ky + kx: the first maximum in row-major
+ * window order (ATen's choice on ties), a NaN wins.  Backward writes EVERY element of dx [N][H][W][C] exactly once -- the gradient
+ * at the winner, zero elsewhere and in the trailing row / column: dx needs no clearing. */
+int glf_maxpool2x2s2_fwd(const float* x, float* y, uint8_t* idx, int n, int h, int w, int c, glf_stream_t s);
+int glf_maxpool2x2s2_bwd(const float* dy, const uint8_t* idx, float* dx, int n, int h, int w, int c, glf_stream_t s);
+int glf_s16_maxpool2x2s2_fwd(const void* x, void* y, uint8_t* idx, int n, int h, int w, int c, glf_stream_t s);
+int glf_s16_maxpool2x2s2_bwd(const void* dy, const uint8_t* idx, void* dx, int n, int h, int w, int c, glf_stream_t s);
+/* nn.Upsample(scale_factor=2) (nearest): y [N][2H][2W][C], y[n][2i+a][2j+b][c] = x[n][i][j][c]; n, h, w, c describe x / dx.
+ * Backward: dx = (dy00 + dy01) + (dy10 + dy11) of each 2x2 block, in that order. */
+int glf_upsample2x_fwd(const float* x, float* y, int n, int h, int w, int c, glf_stream_t s);
+int glf_upsample2x_bwd(const float* dy, float* dx, int n, int h, int w, int c, glf_stream_t s);
+int glf_s16_upsample2x_fwd(const void* x, void* y, int n, int h, int w, int c, glf_stream_t s);
+int glf_s16_upsample2x_bwd(const void* dy, void* dx, int n, int h, int w, int c, glf_stream_t s);
+/* torch.cat((a, b), dim=1) on channels-last rows: y [rows][ca + cb] (contiguous), y[r][0..ca) = a[r * lda + .],
+ * y[r][ca..ca+cb) = b[r * ldb + .] (row strides in elements, multiples of the access width: a source may be a column slice of a
+ * wider buffer).  Backward: the two column slices of dy into the contiguous da [rows][ca] and db [rows][cb], one launch. */
+int glf_concat2_fwd(const float* a, int64_t lda, const float* b, int64_t ldb, float* y, int64_t rows, int ca, int cb, glf_stream_t s);
+int glf_concat2_bwd(const float* dy, float* da, float* db, int64_t rows, int ca, int cb, glf_stream_t s);
+int glf_s16_concat2_fwd(const void* a, int64_t lda, const void* b, int64_t ldb, void* y, int64_t rows, int ca, int cb, glf_stream_t s);
+int glf_s16_concat2_bwd(const void* dy, void* da, void* db, int64_t rows, int ca, int cb, glf_stream_t s);
+
 /* AdaptiveAvgPool2d(1) (deeplabv3.py:126): x [N][P][C] -> y [N][C], and its backward. */
 int glf_avgpool_fwd(const float* x, float* y, int n, int p, int c, glf_stream_t s);
 /* broadcast rows: y[n][p][0..c) (row stride ldy) = x[n][0..c) -- the "bilinear from 1x1"

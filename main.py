@@ -35,7 +35,12 @@ def main(rank, config):
     parser.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
                         help="clip every step by the global gradient norm X and skip steps with a non-finite one, on the device "
                              "(config['train']['clip_grad_norm']; inf = the guard alone); default: off")
+    parser.add_argument("--model", type=str, default=None, choices=("Global_and_Local", "baseline_unet", "multiview_unet"),
+                        help="the network (config['net']['model']); default: the config's, else Global_and_Local.  The U-Net "
+                             "baselines (ours.py:2416-2625) return no fusion features and train without the cycle loss")
     args = parser.parse_args()
+    if args.model:
+        config["net"]["model"] = args.model
     if args.opt:
         config["net"]["opt"]["opt_name"] = args.opt
     if args.clip_grad_norm is not None:
@@ -51,7 +56,8 @@ def main(rank, config):
     from glfusion_amd.engine import Trainer
     trainer = Trainer(config)
     if args.mode == "train":
-        trainer.train(is_backbone=False, is_cycle=True)
+        from glfusion_amd.engine import NO_FUSION_FEATURES
+        trainer.train(is_backbone=False, is_cycle=trainer.model_name not in NO_FUSION_FEATURES)
     elif args.mode == "val":
         print(trainer.eval(net_path="./path/to/ckpt", is_fuse=True, raw_data=True))
     elif args.mode == "visual":
