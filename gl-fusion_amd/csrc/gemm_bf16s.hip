@@ -15,6 +15,7 @@
 // Same gather / tap_mask / rect semantics, epilogues and XCD-aware tile order as gemm_f32.hip.  Only the aligned
 // fast path is built (K % 32 == 0, 16-byte aligned rows); everything else stays on the exact-fp32 kernels.
 #include "gemm_rows_walk.h"
+#include "gemm_tn_walk.h"
 
 namespace {
 
@@ -354,38 +355,17 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_bf16s_kernel(const GemmAr
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int tn = bid % p_tiles_n, tm = bid / p_tiles_n;
-    int tap;
-    {
-        unsigned mm = p_tap_mask;
-        for (int i = 0; i < (int)blockIdx.y; ++i) mm &= mm - 1;
-        tap = __ffs(mm) - 1;
-    }
-    const int bz = blockIdx.z / p_split, sl = blockIdx.z - bz * p_split;
-    const float* __restrict__ A = p_A + (long long)bz * p_bsa;
-    const float* __restrict__ B = p_B + (long long)bz * p_bsb;
-    // two-stage split-K: with a partial-sum workspace every (batch, slice, tap) block row stores its own [M][N] slab
-    // (plain stores, no atomics, no zero fill); tn_reduce_kernel sums the slabs in a fixed order
-    float* __restrict__ C = args.partial ? args.partial + ((long long)blockIdx.z * gridDim.y + blockIdx.y) * ((long long)pM * pN)
-                                         : p_C + (long long)bz * p_bsc + (long long)tap * p_tsb;
-    const int ldc_e = args.partial ? pN : p_ldc;
-
-    int r_y0 = 0, r_x0 = 0, r_h = g_hd, r_w = g_wd, pKe = pK;
-    if (p_rect) {
-        int y0, y1, x0, x1;
-        tap_rect(1, tap, g_kw, g_pad, g_dil, g_hs, g_ws, g_hd, g_wd, y0, y1, x0, x1);
-        r_y0 = y0; r_x0 = x0; r_h = y1 - y0; r_w = x1 - x0;
-        pKe = g_nimg * r_h * r_w;
-    }
-    int chunk = (pK + p_split - 1) / p_split;       // slices are cut from the FULL reduction length: a tap with a short rectangle uses fewer of them
-    chunk = ((chunk + BK - 1) / BK) * BK;
-    const int r0 = sl * chunk;
-    const int r1 = min(pKe, r0 + chunk);
-    if (r0 >= r1) return;
+    const int tap = tn_tap(p_tap_mask, blockIdx.y);
+    TnSlice ts;
+    if (!tn_slice<BK, false>(ts, blockIdx.z, p_split, pK, p_rect, tap, Geo{g_nimg, g_hs, g_ws, g_hd, g_wd, 0, g_kw, g_stride, g_pad, g_dil})) return;
+    const int r_y0 = ts.y0, r_x0 = ts.x0, r_w = ts.w, r0 = ts.r0, r1 = ts.r1;
+    const float* __restrict__ A = p_A + (long long)ts.bz * p_bsa;
+    const float* __restrict__ B = p_B + (long long)ts.bz * p_bsb;
 
     const int c4 = tid & 31, rr = tid >> 5;
     const int m0 = tm * BM + 4 * c4, n0 = tn * BN + 4 * c4;
     const int m0c = min(m0, pM - 4), n0c = min(n0, pN - 4);
-    const int hw = GATHER ? r_h * r_w : 1;
+    const int hw = GATHER ? ts.h * r_w : 1;
 
     f32x16 c00 = {0}, c01 = {0}, c10 = {0}, c11 = {0};
     float4 ra[4], rb[4];
@@ -474,22 +454,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_bf16s_kernel(const GemmAr
         __syncthreads();
     }
 
-    const bool atomic = !args.partial && ((p_split > 1) || p_accumulate);
-    const int col_l = lane & 31, row_l = 4 * (lane >> 5);
-    auto emit = [&](const f32x16& acc, int ti, int tj) {
-        const int col = tn * BN + wn + 32 * tj + col_l;
-        if (col >= pN) return;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = tm * BM + wm + 32 * ti + (r & 3) + 8 * (r >> 2) + row_l;
-            if (row < pM) {
-                float* dst = C + (long long)row * ldc_e + col;
-                const float v = p_alpha * acc[r];
-                if (atomic) atomicAdd(dst, v); else *dst = v;
-            }
-        }
-    };
-    emit(c00, 0, 0); emit(c01, 0, 1); emit(c10, 1, 0); emit(c11, 1, 1);
+    const TnOut out = tn_out(args.partial, p_C, nullptr, pM, pN, p_ldc, p_bsc, p_tsb, ts.bz, tap, p_split, p_accumulate, tm, tn, p_alpha);
+    float cmax = 0.f;                      // (no amax_c in this kernel: never read, the compiler drops the maxima)
+    tn_emit<BM, BN>(out, c00, wm, wn, cmax); tn_emit<BM, BN>(out, c01, wm, wn + 32, cmax);
+    tn_emit<BM, BN>(out, c10, wm + 32, wn, cmax); tn_emit<BM, BN>(out, c11, wm + 32, wn + 32, cmax);
 }
 
 }  // namespace

@@ -19,6 +19,7 @@
 // gemm_bf16s.hip, with two planes per operand instead of three (96 KB of LDS).  Only the aligned fast path is
 // built; everything else stays on the exact-fp32 kernels.
 #include "gemm_rows_walk.h"
+#include "gemm_tn_walk.h"
 #include "split_f16.h"
 #include <cstdlib>
 #include <cstring>
@@ -545,64 +546,29 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_f16s_kernel(const GemmArg
     const int wm = (wave >> 1) * WT, wn = (wave & 1) * WT;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int tn = bid % p_tiles_n, tm = bid / p_tiles_n;
-    int tap;
-    {
-        unsigned mm = p_tap_mask;
-        for (int i = 0; i < (int)blockIdx.y; ++i) mm &= mm - 1;
-        tap = __ffs(mm) - 1;
-    }
-    int tap_cy = 0, tap_cx = 0;  // gathered B rows: source pixel = (y * stride + tap_cy, x * stride + tap_cx)
-    if (GATHER) {
-        int ky = 0, kx = tap;
-        while (kx >= args.g.kw) { kx -= args.g.kw; ++ky; }
-        tap_cy = ky * args.g.dil - args.g.pad; tap_cx = kx * args.g.dil - args.g.pad;
-    }
-    const int bz = blockIdx.z / p_split, sl = blockIdx.z - bz * p_split;
-    const float* __restrict__ A = p_A + (long long)bz * p_bsa;
-    const float* __restrict__ B = p_B + (long long)bz * p_bsb;
-    // two-stage split-K: with a partial-sum workspace every (batch, slice, tap) block row stores its own [M][N] slab
-    // (plain stores, no atomics, no zero fill); tn_reduce_kernel sums the slabs in a fixed order
-    float* __restrict__ C = args.partial ? args.partial + ((long long)blockIdx.z * gridDim.y + blockIdx.y) * ((long long)pM * pN)
-                                         : p_C + (long long)bz * p_bsc + (long long)tap * p_tsb;
-    const int ldc_e = args.partial ? pN : p_ldc;
-
-    int r_y0 = 0, r_x0 = 0, r_h = g_hd, r_w = g_wd, pKe = pK;
-    if (p_rect) {
-        int y0, y1, x0, x1;
-        tap_rect(1, tap, g_kw, g_pad, g_dil, g_hs, g_ws, g_hd, g_wd, y0, y1, x0, x1);
-        r_y0 = y0; r_x0 = x0; r_h = y1 - y0; r_w = x1 - x0;
-        pKe = g_nimg * r_h * r_w;
-    }
-    int chunk = (pK + p_split - 1) / p_split;       // slices are cut from the FULL reduction length: a tap with a short rectangle uses fewer of them
-    chunk = ((chunk + BK - 1) / BK) * BK;
-    const int r0 = sl * chunk;
-    const int r1 = min(pKe, r0 + chunk);
-    if (r0 >= r1) return;
+    const int tap = tn_tap(p_tap_mask, blockIdx.y);
+    TnSlice ts;
+    if (!tn_slice<BK, false>(ts, blockIdx.z, p_split, pK, p_rect, tap, Geo{g_nimg, g_hs, g_ws, g_hd, g_wd, 0, g_kw, g_stride, g_pad, g_dil})) return;
+    const int r0 = ts.r0, r1 = ts.r1;
+    int tap_cy = 0, tap_cx = 0;  // (a const TnGather from offsets computed first: filling cy / cx in afterwards cost the 64 x 64 form two VGPRs)
+    if (GATHER) tn_tap_offsets(tap, g_kw, g_pad, g_dil, tap_cy, tap_cx);
+    const TnGather tg{ts.y0, ts.x0, ts.h, ts.w, g_hs, g_ws, g_hd, g_wd, g_stride, tap_cy, tap_cx};
+    const float* __restrict__ A = p_A + (long long)ts.bz * p_bsa;
+    const float* __restrict__ B = p_B + (long long)ts.bz * p_bsb;
 
     // staging map: a row of the tile is TBM (= TBN) floats = TBM / 4 threads; NTHREADS / (TBM / 4) rows per pass, 32 rows per tile
     constexpr int TPR = TBM / 4, RPP = NTHREADS / TPR, NPASS = 32 / RPP;          // 32 threads x 8 rows x 4 passes | 16 x 16 x 2
     const int c4 = tid % TPR, rr = tid / TPR;
     const int m0 = tm * TBM + 4 * c4, n0 = tn * TBN + 4 * c4;
     const int m0c = min(m0, pM - 4), n0c = min(n0, pN - 4);
-    const int hw = GATHER ? r_h * r_w : 1;
 
     f32x16 c00 = {0}, c01 = {0}, c10 = {0}, c11 = {0};
     f32x16 m00 = {0}, m01 = {0}, m10 = {0}, m11 = {0};
     float4 ra[NPASS], rb[NPASS];
     int rvalid[NPASS];
 
-    // pixel coordinates (inside the tap's rectangle) of this thread's four rows of the NEXT tile to load: set once by
-    // division, advanced by 32 rows per tile by carrying (tiles are loaded in order)
-    int gn[NPASS] = {0}, gy[NPASS] = {0}, gx[NPASS] = {0};
-    if (GATHER) {
-#pragma unroll
-        for (int j = 0; j < NPASS; ++j) {
-            const int r = r0 + rr + RPP * j;
-            gn[j] = r / hw;
-            const int rem = r - gn[j] * hw;
-            gy[j] = rem / r_w; gx[j] = rem - gy[j] * r_w;
-        }
-    }
+    TnRows<NPASS> gs = {};       // this thread's rows of the NEXT tile to load
+    if (GATHER) tn_rows_init<NPASS, RPP>(gs, r0 + rr, tg);
     auto load_tile = [&](int rbase) __attribute__((always_inline)) {
         long long src[NPASS], arow[NPASS];
 #pragma unroll
@@ -611,15 +577,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_f16s_kernel(const GemmArg
             src[j] = -1;
             arow[j] = min(r, r1 - 1);
             if (GATHER) {
-                if (r < r1) {          // (the tap is fixed for the workgroup: constant source offsets, no division for it)
-                    const int y = r_y0 + gy[j], x = r_x0 + gx[j];
-                    arow[j] = ((long long)gn[j] * g_hd + y) * g_wd + x;
-                    const int sy = y * g_stride + tap_cy, sx = x * g_stride + tap_cx;
-                    if ((unsigned)sy < (unsigned)g_hs && (unsigned)sx < (unsigned)g_ws) src[j] = (gn[j] * g_hs + sy) * g_ws + sx;
+                if (r < r1) {
+                    int sr;
+                    arow[j] = tn_row_dst(gs, j, tg);
+                    if (tn_row_src(gs, j, tg, sr)) src[j] = sr;
                 }
-                gx[j] += BK;
-                while (gx[j] >= r_w) { gx[j] -= r_w; ++gy[j]; }
-                while (gy[j] >= r_h) { gy[j] -= r_h; ++gn[j]; }
+                tn_row_step<BK>(gs, j, tg);
             } else if (r < r1) {
                 src[j] = r;
             }
@@ -692,33 +655,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_f16s_kernel(const GemmArg
         __syncthreads();
     }
 
-    const bool atomic = !args.partial && ((p_split > 1) || p_accumulate);
-    const int col_l = lane & 31, row_l = 4 * (lane >> 5);
+    const TnOut out = tn_out(args.partial, p_C, args.amax_c, pM, pN, p_ldc, p_bsc, p_tsb, ts.bz, tap, p_split, p_accumulate, tm, tn, p_alpha);
     float cmax = 0.f;
-    auto emit = [&](const f32x16& acc, int ti, int tj) {
-        const int col = tn * TBN + wn + 32 * tj + col_l;
-        if (col >= pN) return;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = tm * TBM + wm + 32 * ti + (r & 3) + 8 * (r >> 2) + row_l;
-            if (row < pM) {
-                float* dst = C + (long long)row * ldc_e + col;
-                const float v = p_alpha * acc[r];
-                if (atomic) atomicAdd(dst, v); else { *dst = v; cmax = fmaxf(cmax, fabsf(v)); }
-            }
-        }
-    };
-    emit(c00 + m00 * 0x1p-11f, 0, 0);
+    tn_emit<TBM, TBN>(out, c00 + m00 * 0x1p-11f, wm, wn, cmax);
     if constexpr (!SMALL) {
-        emit(c01 + m01 * 0x1p-11f, 0, 1);
-        emit(c10 + m10 * 0x1p-11f, 1, 0); emit(c11 + m11 * 0x1p-11f, 1, 1);
+        tn_emit<TBM, TBN>(out, c01 + m01 * 0x1p-11f, wm, wn + 32, cmax);
+        tn_emit<TBM, TBN>(out, c10 + m10 * 0x1p-11f, wm + 32, wn, cmax); tn_emit<TBM, TBN>(out, c11 + m11 * 0x1p-11f, wm + 32, wn + 32, cmax);
     }
-    if (args.amax_c && !atomic && !args.partial) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cmax = fmaxf(cmax, __shfl_xor(cmax, o, 64));
-        if (lane == 0 && cmax > *reinterpret_cast<volatile float*>(args.amax_c))      // thousands of waves, ONE address: only a wave that raises it
-            atomicMax(reinterpret_cast<unsigned*>(args.amax_c), __float_as_uint(cmax));
-    }
+    tn_amax<true>(out.amax_c, cmax);
 }
 
 // ----------------------------------------------------------------------------------------------------------
@@ -765,33 +709,16 @@ __global__ __launch_bounds__(NT8, 2) void gemm_tn_f16s8_kernel(const GemmArgs ar
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int tn = bid % p_tiles_n, tm = bid / p_tiles_n;
-    int tap;
-    {
-        unsigned mm = p_tap_mask;
-        for (int i = 0; i < (int)blockIdx.y; ++i) mm &= mm - 1;
-        tap = __ffs(mm) - 1;
-    }
-    const int bz = blockIdx.z / p_split, sl = blockIdx.z - bz * p_split;
-    const float* __restrict__ A = p_A + (long long)bz * p_bsa;
-    const float* __restrict__ B = p_B + (long long)bz * p_bsb;
-    // two-stage split-K: with a partial-sum workspace every (batch, slice, tap) block row stores its own [M][N] slab
-    // (plain stores, no atomics, no zero fill); tn_reduce_kernel sums the slabs in a fixed order
-    float* __restrict__ C = args.partial ? args.partial + ((long long)blockIdx.z * gridDim.y + blockIdx.y) * ((long long)pM * pN)
-                                         : p_C + (long long)bz * p_bsc + (long long)tap * p_tsb;
-    const int ldc_e = args.partial ? pN : p_ldc;
-
-    int r_y0 = 0, r_x0 = 0, r_h = g_hd, r_w = g_wd, pKe = pK;
-    if (p_rect) {
-        int y0, y1, x0, x1;
-        tap_rect(1, tap, g_kw, g_pad, g_dil, g_hs, g_ws, g_hd, g_wd, y0, y1, x0, x1);
-        r_y0 = y0; r_x0 = x0; r_h = y1 - y0; r_w = x1 - x0;
-        pKe = g_nimg * r_h * r_w;
-    }
-    int chunk = (pK + p_split - 1) / p_split;       // slices are cut from the FULL reduction length: a tap with a short rectangle uses fewer of them
-    chunk = ((chunk + BK - 1) / BK) * BK;
-    const int r0 = sl * chunk;
-    const int r1 = min(pKe, r0 + chunk);
-    if (r0 >= r1) return;
+    const int tap = tn_tap(p_tap_mask, blockIdx.y);
+    TnSlice ts;
+    if (!tn_slice<BK, false>(ts, blockIdx.z, p_split, pK, p_rect, tap, Geo{g_nimg, g_hs, g_ws, g_hd, g_wd, 0, g_kw, g_stride, g_pad, g_dil})) return;
+    const TnOut out = tn_out(args.partial, p_C, args.amax_c, pM, pN, p_ldc, p_bsc, p_tsb, ts.bz, tap, p_split, p_accumulate, tm, tn, p_alpha);      // (here, not at the stores: one VGPR less)
+    const int r0 = ts.r0, r1 = ts.r1;
+    int tap_cy = 0, tap_cx = 0;
+    if (GATHER) tn_tap_offsets(tap, g_kw, g_pad, g_dil, tap_cy, tap_cx);
+    const TnGather tg{ts.y0, ts.x0, ts.h, ts.w, g_hs, g_ws, g_hd, g_wd, g_stride, tap_cy, tap_cx};
+    const float* __restrict__ A = p_A + (long long)ts.bz * p_bsa;
+    const float* __restrict__ B = p_B + (long long)ts.bz * p_bsb;
     const int ntiles = (r1 - r0 + BK - 1) / BK;
 
     // staging map: A tile 32 x 256 floats = 4 float4 per thread (rows ra0 + 8 j, column ca), B tile 32 x 128 = 2 (rows rb0 + 16 j).
@@ -807,71 +734,42 @@ __global__ __launch_bounds__(NT8, 2) void gemm_tn_f16s8_kernel(const GemmArgs ar
     const float* __restrict__ Bc = B + (b_col_ok ? n0 : 0);
     const float* __restrict__ zb = p_zero + (b_col_ok ? n0 : 0);
 
-    // current row index and (for conv gathers) its pixel coordinates inside the rectangle, per staged row
-    int ar[4], an[4], ay[4], ax[4];
-    int br[2], bn[2], by[2], bx[2];
+    // current row index and (for conv gathers) its pixel coordinates inside the rectangle, per staged row.  The A rows start at
+    // r0 + wave: their state is wave-uniform (outside rect mode row r of A is pixel r: no state at all)
+    int ar[4], br[2];
+    TnRows<4> as = {};
+    TnRows<2> bs = {};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        ar[j] = r0 + ra0 + 8 * j;
-        an[j] = 0; ay[j] = 0; ax[j] = 0;
-        if (GATHER && p_rect) {
-            const int hw = r_h * r_w;
-            const int n = ar[j] / hw, rem = ar[j] - n * hw;
-            const int yy = rem / r_w;
-            an[j] = n; ay[j] = yy; ax[j] = rem - yy * r_w;
-        }
-    }
+    for (int j = 0; j < 4; ++j) ar[j] = r0 + ra0 + 8 * j;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        br[j] = r0 + rb0 + 16 * j;
-        bn[j] = 0; by[j] = 0; bx[j] = 0;
-        if (GATHER) {
-            const int hw = r_h * r_w;
-            const int n = br[j] / hw, rem = br[j] - n * hw;
-            const int yy = rem / r_w;
-            bn[j] = n; by[j] = yy; bx[j] = rem - yy * r_w;
-        }
-    }
+    for (int j = 0; j < 2; ++j) br[j] = r0 + rb0 + 16 * j;
+    if (GATHER && p_rect) tn_rows_init<4, 8>(as, r0 + ra0, tg);
+    if (GATHER) tn_rows_init<2, 16>(bs, r0 + rb0, tg);
     const float* pa[4];          // row bases (uniform); the lane's column offset a_col is added at the load
     const float* pb[2];
-    int tap_cy = 0, tap_cx = 0;  // gathered B rows: source pixel = (y * stride + tap_cy, x * stride + tap_cx)
-    if (GATHER) {
-        int ky = 0, kx = tap;
-        while (kx >= g_kw) { kx -= g_kw; ++ky; }
-        tap_cy = ky * g_dil - g_pad; tap_cx = kx * g_dil - g_pad;
-    }
     // pointers of the NEXT tile to load, then step every row by 32
     auto advance = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const bool ok = ar[j] < r1;
             long long arow = ar[j];
-            if (GATHER && p_rect) arow = ((long long)an[j] * g_hd + r_y0 + ay[j]) * g_wd + r_x0 + ax[j];
+            if (GATHER && p_rect) arow = tn_row_dst(as, j, tg);
             pa[j] = ok ? A + arow * p_lda : p_zero;
             ar[j] += BK;
-            if (GATHER && p_rect) {
-                ax[j] += BK;
-                while (ax[j] >= r_w) { ax[j] -= r_w; ++ay[j]; }
-                while (ay[j] >= r_h) { ay[j] -= r_h; ++an[j]; }
-            }
+            if (GATHER && p_rect) tn_row_step<BK>(as, j, tg);
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             long long src = br[j];
             bool ok = br[j] < r1 && b_col_ok;
             if (GATHER) {
-                // (the tap is fixed for the workgroup: its source offsets are two constants -- no per-row division, see map_src)
-                const int sy = (r_y0 + by[j]) * g_stride + tap_cy, sx = (r_x0 + bx[j]) * g_stride + tap_cx;
-                ok = ok && (unsigned)sy < (unsigned)g_hs && (unsigned)sx < (unsigned)g_ws;
-                src = (bn[j] * g_hs + sy) * g_ws + sx;
+                int sr;
+                ok = tn_row_src(bs, j, tg, sr) && ok;
+                src = sr;
             }
             pb[j] = ok ? Bc + src * p_ldb : zb;
             br[j] += BK;
-            if (GATHER) {
-                bx[j] += BK;
-                while (bx[j] >= r_w) { bx[j] -= r_w; ++by[j]; }
-                while (by[j] >= r_h) { by[j] -= r_h; ++bn[j]; }
-            }
+            if (GATHER) tn_row_step<BK>(bs, j, tg);
         }
     };
 
@@ -1027,30 +925,10 @@ __global__ __launch_bounds__(NT8, 2) void gemm_tn_f16s8_kernel(const GemmArgs ar
     wg_t2 = __builtin_amdgcn_s_memtime();
 #endif
 
-    const bool atomic = !args.partial && ((p_split > 1) || p_accumulate);
-    const int col_l = lane & 31, row_l = 4 * (lane >> 5);
     float cmax = 0.f;
-    auto emit = [&](const f32x16& acc, int ti, int tj) {
-        const int col = tn * BN + wn + 32 * tj + col_l;
-        if (col >= pN) return;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = tm * TM8 + wm + 32 * ti + (r & 3) + 8 * (r >> 2) + row_l;
-            if (row < pM) {
-                float* dst = C + (long long)row * ldc_e + col;
-                const float v = p_alpha * acc[r];
-                if (atomic) atomicAdd(dst, v); else { *dst = v; cmax = fmaxf(cmax, fabsf(v)); }
-            }
-        }
-    };
-    emit(c00 + m00 * 0x1p-11f, 0, 0); emit(c01 + m01 * 0x1p-11f, 0, 1);
-    emit(c10 + m10 * 0x1p-11f, 1, 0); emit(c11 + m11 * 0x1p-11f, 1, 1);
-    if (args.amax_c && !atomic && !args.partial) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cmax = fmaxf(cmax, __shfl_xor(cmax, o, 64));
-        if (lane == 0 && cmax > *reinterpret_cast<volatile float*>(args.amax_c))      // thousands of waves, ONE address: only a wave that raises it
-            atomicMax(reinterpret_cast<unsigned*>(args.amax_c), __float_as_uint(cmax));
-    }
+    tn_emit<TM8, BN>(out, c00 + m00 * 0x1p-11f, wm, wn, cmax); tn_emit<TM8, BN>(out, c01 + m01 * 0x1p-11f, wm, wn + 32, cmax);
+    tn_emit<TM8, BN>(out, c10 + m10 * 0x1p-11f, wm + 32, wn, cmax); tn_emit<TM8, BN>(out, c11 + m11 * 0x1p-11f, wm + 32, wn + 32, cmax);
+    tn_amax<true>(out.amax_c, cmax);
 #if defined(GLF_STAMPS) && GLF_STAMPS == 2
     if (args.stamps != nullptr && blockIdx.x == gridDim.x / 2 && blockIdx.z == 0 && blockIdx.y == 0) {
         __builtin_amdgcn_s_waitcnt(0);

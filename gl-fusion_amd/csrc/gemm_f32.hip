@@ -19,6 +19,7 @@
 //   gemm_rows_kernel<1>  A[m][k] (gathered rows) x B[k][n]   -> conv dgrad, y = theta @ M
 //   gemm_tn_kernel       sum_r A[r][m] * B[src(r)][n]        -> conv wgrad, M = phi^T g
 #include "gemm_rows_walk.h"
+#include "gemm_tn_walk.h"
 
 namespace {
 
@@ -422,40 +423,18 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_kernel(const GemmArgs arg
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int tn = bid % p_tiles_n, tm = bid / p_tiles_n;
-    // nth set bit of the tap mask
-    int tap;
-    {
-        unsigned mm = p_tap_mask;
-        for (int i = 0; i < (int)blockIdx.y; ++i) mm &= mm - 1;
-        tap = __ffs(mm) - 1;
-    }
-    const int bz = blockIdx.z / p_split, sl = blockIdx.z - bz * p_split;
-    const float* __restrict__ A = p_A + (long long)bz * p_bsa;
-    const float* __restrict__ B = p_B + (long long)bz * p_bsb;
-    // two-stage split-K: with a partial-sum workspace every (batch, slice, tap) block row stores its own [M][N] slab
-    // (plain stores, no atomics, no zero fill); tn_reduce_kernel sums the slabs in a fixed order
-    float* __restrict__ C = args.partial ? args.partial + ((long long)blockIdx.z * gridDim.y + blockIdx.y) * ((long long)pM * pN)
-                                         : p_C + (long long)bz * p_bsc + (long long)tap * p_tsb;
-    const int ldc_e = args.partial ? pN : p_ldc;
-
+    const int tap = tn_tap(p_tap_mask, blockIdx.y);
     // rect mode: the reduction runs over this tap's rectangle of output pixels only (see tap_rect)
-    int r_y0 = 0, r_x0 = 0, r_h = g_hd, r_w = g_wd, pKe = pK;
-    if (p_rect) {
-        int y0, y1, x0, x1;
-        tap_rect(1, tap, g_kw, g_pad, g_dil, g_hs, g_ws, g_hd, g_wd, y0, y1, x0, x1);
-        r_y0 = y0; r_x0 = x0; r_h = y1 - y0; r_w = x1 - x0;
-        pKe = g_nimg * r_h * r_w;
-    }
-    int chunk = (pK + p_split - 1) / p_split;       // slices are cut from the FULL reduction length: a tap with a short rectangle uses fewer of them
-    chunk = ((chunk + BK - 1) / BK) * BK;
-    const int r0 = sl * chunk;
-    const int r1 = min(pKe, r0 + chunk);
-    if (r0 >= r1) return;                                      // block-uniform
+    TnSlice ts;
+    if (!tn_slice<BK, false>(ts, blockIdx.z, p_split, pK, p_rect, tap, Geo{g_nimg, g_hs, g_ws, g_hd, g_wd, 0, g_kw, g_stride, g_pad, g_dil})) return;
+    const int r_y0 = ts.y0, r_x0 = ts.x0, r_w = ts.w, r0 = ts.r0, r1 = ts.r1;
+    const float* __restrict__ A = p_A + (long long)ts.bz * p_bsa;
+    const float* __restrict__ B = p_B + (long long)ts.bz * p_bsb;
 
     const int c4 = tid & 31, rr = tid >> 5;
     const int m0 = tm * BM + 4 * c4, n0 = tn * BN + 4 * c4;
     const bool vec_a = p_vec_a, vec_b = p_vec_b;
-    const int hw = GATHER ? r_h * r_w : 1;
+    const int hw = GATHER ? ts.h * r_w : 1;
 
     f32x16 c00 = {0}, c01 = {0}, c10 = {0}, c11 = {0};
     float4 ra[4], rb[4];
@@ -558,46 +537,24 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_kernel(const GemmArgs arg
         __syncthreads();
     }
 
-    const bool atomic = !args.partial && ((p_split > 1) || p_accumulate);
-    const int col_l = lane & 31, row_l = 4 * (lane >> 5);
-    auto emit = [&](const f32x16& acc, int ti, int tj) {
-        const int col = tn * BN + wn + 32 * tj + col_l;
-        if (col >= pN) return;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = tm * BM + wm + 32 * ti + (r & 3) + 8 * (r >> 2) + row_l;
-            if (row < pM) {
-                float* dst = C + (long long)row * ldc_e + col;
-                const float v = p_alpha * acc[r];
-                if (atomic) atomicAdd(dst, v); else *dst = v;
-            }
-        }
-    };
-    emit(c00, 0, 0); emit(c01, 0, 1); emit(c10, 1, 0); emit(c11, 1, 1);
+    const TnOut out = tn_out(args.partial, p_C, nullptr, pM, pN, p_ldc, p_bsc, p_tsb, ts.bz, tap, p_split, p_accumulate, tm, tn, p_alpha);
+    float cmax = 0.f;                      // (no amax_c in this kernel: never read, the compiler drops the maxima)
+    tn_emit<BM, BN>(out, c00, wm, wn, cmax); tn_emit<BM, BN>(out, c01, wm, wn + 32, cmax);
+    tn_emit<BM, BN>(out, c10, wm + 32, wn, cmax); tn_emit<BM, BN>(out, c11, wm + 32, wn + 32, cmax);
 }
 
 // ----------------------------------------------------------------------------------------
 // second stage of the two-stage split-K reduction of glf_gemm_tn: C_tap = (accumulate ? C_tap : 0) + sum over the valid
-// slices of their partial slabs, in slice order (bitwise reproducible).  grid: x over M*N, y = kept-tap ordinal, z = batch.
+// slices of their partial slabs, in slice order (bitwise reproducible; tn_sum_slabs).  grid: x over M*N, y = kept-tap ordinal,
+// z = batch.  vec = 0: the scalar fallback (N, ldc or C not 4-element aligned).
 // ----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict__ partial, float* __restrict__ Cb, int M, int N, int ldc,
                                                         long long tsb, long long bsc, int split, unsigned tap_mask, int accumulate,
                                                         int K, int rect, Geo g, int vec, float* __restrict__ amax_c) {
-    unsigned mm = tap_mask;
-    for (int i = 0; i < (int)blockIdx.y; ++i) mm &= mm - 1;
-    const int tap = __ffs(mm) - 1;
-    const int ntap = gridDim.y, bz = blockIdx.z;
-    int pKe = K;
-    if (rect) {
-        int y0, y1, x0, x1;
-        tap_rect(1, tap, g.kw, g.pad, g.dil, g.hs, g.ws, g.hd, g.wd, y0, y1, x0, x1);
-        pKe = g.n_img * (y1 - y0) * (x1 - x0);
-    }
-    int chunk = (K + split - 1) / split;                // as in the kernels: from the full reduction length
-    chunk = ((chunk + BK - 1) / BK) * BK;
-    const int nvalid = chunk > 0 ? min(split, (pKe + chunk - 1) / chunk) : 0;       // slices that ran (the others returned early)
+    const int tap = tn_tap(tap_mask, blockIdx.y), ntap = gridDim.y, bz = blockIdx.z;
+    const int nvalid = tn_valid_slices(tn_tap_row_count<false>(rect, tap, K, g), K, split, BK);
     const long long mn = (long long)M * N;
-    const float* __restrict__ src = partial + ((long long)bz * split * ntap + blockIdx.y) * mn;
+    const float* __restrict__ src = tn_slab(partial, bz * split, ntap, blockIdx.y, mn);
     const long long slice_stride = (long long)ntap * mn;
     float* __restrict__ C = Cb + (long long)bz * bsc + (long long)tap * tsb;
     float cmax = 0.f;
@@ -607,17 +564,10 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict_
             const long long row = i / n4;
             const int c4 = (int)(i - row * n4) * 4;
             float* dst = C + row * ldc + c4;
-            // (the slabs are added in double: the second stage must not add a rounding walk of its own to the slices' fp32 chains)
-            double ax = 0, ay = 0, az = 0, aw = 0;
-            if (accumulate) { const float4 o = *reinterpret_cast<const float4*>(dst); ax = o.x; ay = o.y; az = o.z; aw = o.w; }
-            const float* sp = src + row * N + c4;
-            for (int sl = 0; sl < nvalid; ++sl) {
-                const float4 v = *reinterpret_cast<const float4*>(sp + sl * slice_stride);
-                ax += v.x; ay += v.y; az += v.z; aw += v.w;
-            }
-            const float4 acc = make_float4((float)ax, (float)ay, (float)az, (float)aw);
+            const float4 acc = tn_sum_slabs<1, false>(src + row * N + c4, slice_stride, nvalid, true, accumulate,
+                                                      [&] { return *reinterpret_cast<const float4*>(dst); }, nullptr);
             *reinterpret_cast<float4*>(dst) = acc;
-            cmax = fmaxf(fmaxf(cmax, fmaxf(fabsf(acc.x), fabsf(acc.y))), fmaxf(fabsf(acc.z), fabsf(acc.w)));
+            cmax = amax4(cmax, acc);
         }
     } else {
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < mn; i += (long long)gridDim.x * blockDim.x) {
@@ -631,37 +581,20 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict_
             cmax = fmaxf(cmax, fabsf(acc));
         }
     }
-    if (amax_c) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cmax = fmaxf(cmax, __shfl_xor(cmax, o, 64));
-        if ((threadIdx.x & 63) == 0 && cmax > 0.f) atomicMax(reinterpret_cast<unsigned*>(amax_c), __float_as_uint(cmax));
-    }
+    tn_amax<false>(amax_c, cmax);
 }
 
-// the vector form with SL slice lanes per output (lane l adds slices l, l + SL, ... in double; the lanes meet in LDS in lane order):
-// with one thread per float4 a layer-1 gradient (64 x 256 outputs, hundreds of slices) was a few thousand threads walking hundreds
-// of loads one after the other -- ~100 us for 24 MB
+// the vector form with SL = 4 / 16 slice lanes per output
 template <int SL>
 __global__ __launch_bounds__(256) void tn_reduce_lanes_kernel(const float* __restrict__ partial, float* __restrict__ Cb, int M, int N, int ldc,
                                                               long long tsb, long long bsc, int split, unsigned tap_mask, int accumulate,
                                                               int K, int rect, Geo g, float* __restrict__ amax_c) {
     constexpr int OG = 256 / SL;
     __shared__ double sh[4][256];
-    unsigned mm = tap_mask;
-    for (int i = 0; i < (int)blockIdx.y; ++i) mm &= mm - 1;
-    const int tap = __ffs(mm) - 1;
-    const int ntap = gridDim.y, bz = blockIdx.z;
-    int pKe = K;
-    if (rect) {
-        int y0, y1, x0, x1;
-        tap_rect(1, tap, g.kw, g.pad, g.dil, g.hs, g.ws, g.hd, g.wd, y0, y1, x0, x1);
-        pKe = g.n_img * (y1 - y0) * (x1 - x0);
-    }
-    int chunk = (K + split - 1) / split;
-    chunk = ((chunk + BK - 1) / BK) * BK;
-    const int nvalid = chunk > 0 ? min(split, (pKe + chunk - 1) / chunk) : 0;
+    const int tap = tn_tap(tap_mask, blockIdx.y), ntap = gridDim.y, bz = blockIdx.z;
+    const int nvalid = tn_valid_slices(tn_tap_row_count<false>(rect, tap, K, g), K, split, BK);
     const long long mn = (long long)M * N;
-    const float* __restrict__ src = partial + ((long long)bz * split * ntap + blockIdx.y) * mn;
+    const float* __restrict__ src = tn_slab(partial, bz * split, ntap, blockIdx.y, mn);
     const long long slice_stride = (long long)ntap * mn;
     float* __restrict__ C = Cb + (long long)bz * bsc + (long long)tap * tsb;
     const int n4 = N >> 2;
@@ -673,61 +606,23 @@ __global__ __launch_bounds__(256) void tn_reduce_lanes_kernel(const float* __res
         const bool live = i < total;
         const long long row = live ? i / n4 : 0;
         const int c4 = (int)((live ? i : 0) - row * n4) * 4;
-        double ax = 0, ay = 0, az = 0, aw = 0;
-        if (live) {
-            const float* sp = src + row * N + c4;
-            int s_ = sl;
-            for (; s_ + SL < nvalid; s_ += 2 * SL) {
-                const float4 v0 = *reinterpret_cast<const float4*>(sp + (long long)s_ * slice_stride);
-                const float4 v1 = *reinterpret_cast<const float4*>(sp + (long long)(s_ + SL) * slice_stride);
-                ax += (double)v0.x + (double)v1.x; ay += (double)v0.y + (double)v1.y;
-                az += (double)v0.z + (double)v1.z; aw += (double)v0.w + (double)v1.w;
-            }
-            for (; s_ < nvalid; s_ += SL) {
-                const float4 v = *reinterpret_cast<const float4*>(sp + (long long)s_ * slice_stride);
-                ax += v.x; ay += v.y; az += v.z; aw += v.w;
-            }
-        }
-        sh[0][threadIdx.x] = ax; sh[1][threadIdx.x] = ay; sh[2][threadIdx.x] = az; sh[3][threadIdx.x] = aw;
-        __syncthreads();
+        float* dst = C + row * ldc + c4;
+        const float4 acc = tn_sum_slabs<SL>(src + row * N + c4, slice_stride, nvalid, live, accumulate,
+                                            [&] { return *reinterpret_cast<const float4*>(dst); }, sh);
         if (sl == 0 && live) {
-#pragma unroll
-            for (int l = 1; l < SL; ++l) { ax += sh[0][l * OG + ol]; ay += sh[1][l * OG + ol]; az += sh[2][l * OG + ol]; aw += sh[3][l * OG + ol]; }
-            float* dst = C + row * ldc + c4;
-            if (accumulate) { const float4 o = *reinterpret_cast<const float4*>(dst); ax += o.x; ay += o.y; az += o.z; aw += o.w; }
-            const float4 acc = make_float4((float)ax, (float)ay, (float)az, (float)aw);
             *reinterpret_cast<float4*>(dst) = acc;
-            cmax = fmaxf(fmaxf(cmax, fmaxf(fabsf(acc.x), fabsf(acc.y))), fmaxf(fabsf(acc.z), fabsf(acc.w)));
+            cmax = amax4(cmax, acc);
         }
-        __syncthreads();
     }
-    if (amax_c) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cmax = fmaxf(cmax, __shfl_xor(cmax, o, 64));
-        if ((threadIdx.x & 63) == 0 && cmax > 0.f) atomicMax(reinterpret_cast<unsigned*>(amax_c), __float_as_uint(cmax));
-    }
-}
-
-// slices of `tap` that ran (the others returned early): cut from the FULL reduction length, as in the kernels
-__device__ __forceinline__ int tn_valid_slices(int tap, int K, int split, int rect, const Geo& g) {
-    int pKe = K;
-    if (rect) {
-        int y0, y1, x0, x1;
-        tap_rect(1, tap, g.kw, g.pad, g.dil, g.hs, g.ws, g.hd, g.wd, y0, y1, x0, x1);
-        pKe = g.n_img * (y1 - y0) * (x1 - x0);
-    }
-    int chunk = (K + split - 1) / split;
-    chunk = ((chunk + BK - 1) / BK) * BK;
-    return chunk > 0 ? min(split, (pKe + chunk - 1) / chunk) : 0;
+    tn_amax<false>(amax_c, cmax);
 }
 
 // The second stage storing the PARAMETER layout (glf_gemm_params.c_oihw): out[m][n][tap], the taps of an output element side by
 // side, so that a k x k weight's gradient needs neither the tap-major intermediate nor the pass that re-lays it out.  A workgroup
 // owns 4 * OG consecutive elements of the [M][N] plane (OG = 256 / SL float4 groups, SL slice lanes per group) for ALL taps.  It
-// sums tap after tap with the expressions of the two kernels above -- SL = 1: tn_reduce_kernel's walk, SL = 4 / 16: the lane walk
-// of tn_reduce_lanes_kernel, the stored bits are the same -- into an LDS tile laid out as the destination is, and stores the
-// tile's 4 * OG * taps floats as one contiguous run of float4 (144 B per float4 group of a 3x3 kernel; a tap per blockIdx.y would
-// write 4-byte pieces 36 B apart).  Taps outside tap_mask store 0 (the caller fills nothing), tap `ftap` is copied from fsrc
+// sums tap after tap with tn_sum_slabs, as the two kernels above do, into an LDS tile laid out as the destination is, and stores
+// the tile's 4 * OG * taps floats as one contiguous run of float4 (144 B per float4 group of a 3x3 kernel; a tap per blockIdx.y
+// would write 4-byte pieces 36 B apart).  Taps outside tap_mask store 0 (the caller fills nothing), tap `ftap` is copied from fsrc
 // [M][fld] when that is given; accumulate adds to what the destination holds.  partial may be null when tap_mask is empty.
 template <int SL>
 __global__ __launch_bounds__(256) void tn_reduce_oihw_kernel(const float* __restrict__ partial, float* __restrict__ C, int M, int N, int taps, int split,
@@ -735,7 +630,7 @@ __global__ __launch_bounds__(256) void tn_reduce_oihw_kernel(const float* __rest
                                                              const float* __restrict__ fsrc, long long fld, int ftap, float* __restrict__ amax_c) {
     constexpr int OG = 256 / SL;
     extern __shared__ __attribute__((aligned(16))) float tile[];          // [4 * OG][taps]
-    __shared__ double sh[SL > 1 ? 4 : 1][SL > 1 ? 256 : 1];
+    __shared__ double sh[SL > 1 ? 4 : 1][256];                            // (SL = 1 sums without meeting anybody: never touched, dropped by the compiler)
     const long long mn = (long long)M * N, slice_stride = (long long)__popc(tap_mask) * mn;
     const int n4 = N >> 2;
     const long long total = (long long)M * n4;
@@ -754,74 +649,26 @@ __global__ __launch_bounds__(256) void tn_reduce_oihw_kernel(const float* __rest
     float* to = tile + 4 * ol * taps;                                     // element j of the group, tap t: to[j * taps + t]
     int ord = 0;                                                          // ordinal of tap t among the kept ones (its slab)
     for (int t = 0; t < taps; ++t) {
+        auto prev = [&] { return make_float4(to[t], to[taps + t], to[2 * taps + t], to[3 * taps + t]); };
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if ((tap_mask >> t) & 1u) {
-            const int nvalid = tn_valid_slices(t, K, split, rect, g);
-            const float* sp = partial + (long long)ord * mn + row * N + c4;
+            const int nvalid = tn_valid_slices(tn_tap_row_count<false>(rect, t, K, g), K, split, BK);
+            v = tn_sum_slabs<SL>(partial + (long long)ord * mn + row * N + c4, slice_stride, nvalid, live, accumulate, prev, SL > 1 ? sh : nullptr);
             ++ord;
-            double ax = 0, ay = 0, az = 0, aw = 0;
-            if (SL == 1) {
-                if (live) {
-                    if (accumulate) { ax = to[t]; ay = to[taps + t]; az = to[2 * taps + t]; aw = to[3 * taps + t]; }
-                    int s_ = 0;
-                    for (; s_ + 4 <= nvalid; s_ += 4) {                   // four loads in flight, added in slice order
-                        const float4 v0 = *reinterpret_cast<const float4*>(sp + (long long)s_ * slice_stride);
-                        const float4 v1 = *reinterpret_cast<const float4*>(sp + (long long)(s_ + 1) * slice_stride);
-                        const float4 v2 = *reinterpret_cast<const float4*>(sp + (long long)(s_ + 2) * slice_stride);
-                        const float4 v3 = *reinterpret_cast<const float4*>(sp + (long long)(s_ + 3) * slice_stride);
-                        ax += v0.x; ay += v0.y; az += v0.z; aw += v0.w;
-                        ax += v1.x; ay += v1.y; az += v1.z; aw += v1.w;
-                        ax += v2.x; ay += v2.y; az += v2.z; aw += v2.w;
-                        ax += v3.x; ay += v3.y; az += v3.z; aw += v3.w;
-                    }
-                    for (; s_ < nvalid; ++s_) {
-                        const float4 v = *reinterpret_cast<const float4*>(sp + (long long)s_ * slice_stride);
-                        ax += v.x; ay += v.y; az += v.z; aw += v.w;
-                    }
-                    to[t] = (float)ax; to[taps + t] = (float)ay; to[2 * taps + t] = (float)az; to[3 * taps + t] = (float)aw;
-                }
-            } else {
-                if (live) {
-                    int s_ = sl;
-                    for (; s_ + SL < nvalid; s_ += 2 * SL) {
-                        const float4 v0 = *reinterpret_cast<const float4*>(sp + (long long)s_ * slice_stride);
-                        const float4 v1 = *reinterpret_cast<const float4*>(sp + (long long)(s_ + SL) * slice_stride);
-                        ax += (double)v0.x + (double)v1.x; ay += (double)v0.y + (double)v1.y;
-                        az += (double)v0.z + (double)v1.z; aw += (double)v0.w + (double)v1.w;
-                    }
-                    for (; s_ < nvalid; s_ += SL) {
-                        const float4 v = *reinterpret_cast<const float4*>(sp + (long long)s_ * slice_stride);
-                        ax += v.x; ay += v.y; az += v.z; aw += v.w;
-                    }
-                }
-                sh[0][threadIdx.x] = ax; sh[1][threadIdx.x] = ay; sh[2][threadIdx.x] = az; sh[3][threadIdx.x] = aw;
-                __syncthreads();
-                if (sl == 0 && live) {
-#pragma unroll
-                    for (int l = 1; l < SL; ++l) { ax += sh[0][l * OG + ol]; ay += sh[1][l * OG + ol]; az += sh[2][l * OG + ol]; aw += sh[3][l * OG + ol]; }
-                    if (accumulate) { ax += to[t]; ay += to[taps + t]; az += to[2 * taps + t]; aw += to[3 * taps + t]; }
-                    to[t] = (float)ax; to[taps + t] = (float)ay; to[2 * taps + t] = (float)az; to[3 * taps + t] = (float)aw;
-                }
-                __syncthreads();
-            }
         } else if (sl == 0 && live) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (fsrc && t == ftap) v = *reinterpret_cast<const float4*>(fsrc + row * fld + c4);
-            if (accumulate) { v.x += to[t]; v.y += to[taps + t]; v.z += to[2 * taps + t]; v.w += to[3 * taps + t]; }
-            to[t] = v.x; to[taps + t] = v.y; to[2 * taps + t] = v.z; to[3 * taps + t] = v.w;
+            if (accumulate) { const float4 o = prev(); v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
         }
+        if (sl == 0 && live) { to[t] = v.x; to[taps + t] = v.y; to[2 * taps + t] = v.z; to[3 * taps + t] = v.w; }
     }
     __syncthreads();
     float cmax = 0.f;
     for (int i = 4 * threadIdx.x; i < nfl; i += 1024) {
         const float4 v = *reinterpret_cast<const float4*>(tile + i);
         *reinterpret_cast<float4*>(dst + i) = v;
-        cmax = fmaxf(fmaxf(cmax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+        cmax = amax4(cmax, v);
     }
-    if (amax_c) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cmax = fmaxf(cmax, __shfl_xor(cmax, o, 64));
-        if ((threadIdx.x & 63) == 0 && cmax > 0.f) atomicMax(reinterpret_cast<unsigned*>(amax_c), __float_as_uint(cmax));
-    }
+    tn_amax<false>(amax_c, cmax);
 }
 
 constexpr size_t SMEM_ROWS_NT = (2 * BK * LD_T + 2 * BK * LD_T) * sizeof(float) + 16;
@@ -1122,18 +969,16 @@ extern "C" int glf_gemm_tn(const float* A, const float* B, float* C,
     } else {
         GLF_REQUIRE(!p->foreign_src, GLF_ERR_UNSUPPORTED, "gemm_tn: a foreign tap needs c_oihw");
     }
-    auto store_oihw = [&](int lanes) {
-        const long long work = (long long)p->M * (p->N / 4);
-        const size_t lds = (size_t)(1024 / lanes) * p->taps * sizeof(float);
-        const dim3 gr((unsigned)((work * lanes + 255) / 256));
-#define GLF_OIHW(SL_)                                                                                                                          \
-        hipLaunchKernelGGL((tn_reduce_oihw_kernel<SL_>), gr, dim3(256), lds, glf::S(stream), a.partial, C, p->M, p->N, p->taps, a.split, p->tap_mask, \
-                           p->accumulate, p->K, a.rect, a.g, p->foreign_src, (long long)p->foreign_ld, p->foreign_tap, p->amax_c);
-        if (lanes == 16) { GLF_OIHW(16) } else if (lanes == 4) { GLF_OIHW(4) } else { GLF_OIHW(1) }
-#undef GLF_OIHW
+    auto store_oihw = [&](const TnReducePlan& plan) {
+        const size_t lds = (size_t)(1024 / plan.lanes) * p->taps * sizeof(float);
+        const dim3 gr((unsigned)plan.blocks);
+        tn_by_lanes(plan.lanes, [&](auto sl) {
+            hipLaunchKernelGGL((tn_reduce_oihw_kernel<sl()>), gr, dim3(256), lds, glf::S(stream), a.partial, C, p->M, p->N, p->taps, a.split, p->tap_mask,
+                               p->accumulate, p->K, a.rect, a.g, p->foreign_src, (long long)p->foreign_ld, p->foreign_tap, p->amax_c);
+        });
         return glf::check_launch("gemm_tn(reduce, oihw)");
     };
-    if (ntap == 0) return oihw ? store_oihw(1) : GLF_OK;       // every tap in the padding: dW stays as the caller left it (c_oihw: zeros + the foreign tap)
+    if (ntap == 0) return oihw ? store_oihw(tn_reduce_plan((long long)p->M * (p->N / 4), 1, true)) : GLF_OK;       // every tap in the padding: dW stays as the caller left it (c_oihw: zeros + the foreign tap)
     GLF_REQUIRE((long long)p->batch * a.split <= 65535, GLF_ERR_BAD_SHAPE, "gemm_tn: batch*split too large");
     a.vec_a = aligned16(A) && (p->lda % 4 == 0) && (p->batch_stride_a % 4 == 0);
     a.vec_b = aligned16(B) && (p->ldb % 4 == 0) && (p->batch_stride_b % 4 == 0);
@@ -1170,26 +1015,18 @@ extern "C" int glf_gemm_tn(const float* A, const float* B, float* C,
     }
     if (rc != GLF_OK || !two_stage) return rc;
     const int vec = (p->N % 4 == 0) && (p->ldc % 4 == 0) && aligned16(C) && (p->tap_stride_b % 4 == 0) && (p->batch_stride_c % 4 == 0);
-    const long long work = vec ? (long long)p->M * (p->N / 4) : (long long)p->M * p->N;
-    long long bx = (work + 255) / 256;
-    if (bx > 2048) bx = 2048;
-    int lanes = 1;
-    while (vec && lanes < 16 && lanes * 4 <= a.split && work * lanes < 65536) lanes *= 4;
-    if (oihw) return store_oihw(lanes);          // (vec holds: N % 4 == 0 and the alignment of C were required above)
-    if (lanes > 1) {
-        long long bl = (work * lanes + 255) / 256;
-        if (bl > 4096) bl = 4096;
-        if (lanes == 16)
-            hipLaunchKernelGGL((tn_reduce_lanes_kernel<16>), dim3((unsigned)bl, ntap, p->batch), dim3(256), 0, glf::S(stream), a.partial, C, p->M, p->N,
-                               p->ldc, (long long)p->tap_stride_b, (long long)p->batch_stride_c, a.split, p->tap_mask, p->accumulate, p->K, a.rect, a.g, p->amax_c);
+    const TnReducePlan plan = tn_reduce_plan(vec ? (long long)p->M * (p->N / 4) : (long long)p->M * p->N, a.split, vec != 0);
+    if (oihw) return store_oihw(plan);           // (vec holds: N % 4 == 0 and the alignment of C were required above)
+    const long long cap = plan.lanes > 1 ? 4096 : 2048;
+    const dim3 gr((unsigned)(plan.blocks < cap ? plan.blocks : cap), ntap, p->batch);
+    tn_by_lanes(plan.lanes, [&](auto sl) {
+        if constexpr (sl() == 1)
+            hipLaunchKernelGGL(tn_reduce_kernel, gr, dim3(256), 0, glf::S(stream), a.partial, C, p->M, p->N, p->ldc, (long long)p->tap_stride_b,
+                               (long long)p->batch_stride_c, a.split, p->tap_mask, p->accumulate, p->K, a.rect, a.g, vec, p->amax_c);
         else
-            hipLaunchKernelGGL((tn_reduce_lanes_kernel<4>), dim3((unsigned)bl, ntap, p->batch), dim3(256), 0, glf::S(stream), a.partial, C, p->M, p->N,
-                               p->ldc, (long long)p->tap_stride_b, (long long)p->batch_stride_c, a.split, p->tap_mask, p->accumulate, p->K, a.rect, a.g, p->amax_c);
-        return glf::check_launch("gemm_tn(reduce)");
-    }
-    hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)bx, ntap, p->batch), dim3(256), 0, glf::S(stream), a.partial, C, p->M, p->N, p->ldc,
-                       (long long)p->tap_stride_b, (long long)p->batch_stride_c, a.split, p->tap_mask, p->accumulate, p->K, a.rect, a.g, vec,
-                       p->amax_c);
+            hipLaunchKernelGGL((tn_reduce_lanes_kernel<sl()>), gr, dim3(256), 0, glf::S(stream), a.partial, C, p->M, p->N, p->ldc, (long long)p->tap_stride_b,
+                               (long long)p->batch_stride_c, a.split, p->tap_mask, p->accumulate, p->K, a.rect, a.g, p->amax_c);
+    });
     return glf::check_launch("gemm_tn(reduce)");
 }
 

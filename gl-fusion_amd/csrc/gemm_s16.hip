@@ -20,6 +20,7 @@
 //     chunks XORed with r & 3) and fragments are transposed on the way out by ds_read_b64_tr_b16; split-K slices store
 //     partial slabs that s16_tn_reduce_kernel folds in slice order (no atomics: bitwise reproducible gradients).
 #include "gemm_rows_walk.h"
+#include "gemm_tn_walk.h"
 #include <type_traits>
 
 namespace {
@@ -392,34 +393,14 @@ __global__ __launch_bounds__(NTH, TK_ == 64 ? 2 : 4) void s16_rows_kernel(const 
 // ----------------------------------------------------------------------------------------------------------------------
 // tn kernel
 // ----------------------------------------------------------------------------------------------------------------------
-// output pixels y (of hd) whose source pixel y * stride + o lies inside [0, hs): the band [lo, hi)
-__host__ __device__ inline void tap_band(int o, int stride, int hs, int hd, int& lo, int& hi) {
-    lo = o < 0 ? (-o + stride - 1) / stride : 0;
-    const int top = hs - 1 - o;
-    hi = top < 0 ? 0 : (top / stride + 1 < hd ? top / stride + 1 : hd);
-    if (lo > hi) lo = hi;
-}
-// reduction rows of tap `tap` of a gathered TN contraction in rectangle mode (rect = 1): only the output pixels whose source pixel
-// is inside the map, enumerated image by image, row by row: n_img * (yhi - ylo) * (xhi - xlo)
-__host__ __device__ inline int tn_rect_rows(const Geo& g, int tap, int K) {
-    const int ky = tap / g.kw, kx = tap - ky * g.kw;
-    int ylo, yhi, xlo, xhi;
-    tap_band(ky * g.dil - g.pad, g.stride, g.hs, g.hd, ylo, yhi);
-    tap_band(kx * g.dil - g.pad, g.stride, g.ws, g.wd, xlo, xhi);
-    return (K / (g.hd * g.wd)) * (yhi - ylo) * (xhi - xlo);
-}
 // rectangle mode keeps only the slabs of slices that run, tap after tap: first slab of `tap` (its number of slices in nvalid);
 // tap = -1: the total number of slabs
-__host__ __device__ inline int tn_rect_slab(const Geo& g, unsigned tap_mask, int tap, int K, int split, int& nvalid) {
-    int chunk = (K + split - 1) / split;
-    chunk = ((chunk + TK - 1) / TK) * TK;
+__host__ __device__ inline int tn_rect_slab(const Geo& g, unsigned tap_mask, int tap, int K, int split, int ktile, int& nvalid) {
     int prefix = 0;
     nvalid = 0;
     for (unsigned mm = tap_mask; mm; mm &= mm - 1) {
         const int t = __builtin_ctz(mm);
-        const int rows = tn_rect_rows(g, t, K);
-        int nv = (rows + chunk - 1) / chunk;
-        if (nv > split) nv = split;
+        const int nv = tn_valid_slices(tn_tap_row_count<true>(1, t, K, g), K, split, ktile);
         if (t == tap) { nvalid = nv; return prefix; }
         prefix += nv;
     }
@@ -460,36 +441,17 @@ __global__ __launch_bounds__(NTH, 2) void s16_tn_kernel(const S16Args args) {
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     const int tn = bid % p_tiles_n, tm = bid / p_tiles_n;
-    int tap;
-    {
-        unsigned mm = p_tap_mask;
-        for (int i = 0; i < (int)blockIdx.y; ++i) mm &= mm - 1;
-        tap = __ffs(mm) - 1;
-    }
-    const int bz = blockIdx.z / p_split, sl = blockIdx.z - bz * p_split;
-    const u16* __restrict__ A = args.A + (long long)bz * args.bsa;
-    const u16* __restrict__ B = args.B + (long long)bz * args.bsb;
-
+    const int tap = tn_tap(p_tap_mask, blockIdx.y);
     // rectangle mode (gathered taps that fall mostly into the padding: the ASPP rates): the reduction of a tap runs over ITS in-range
     // output pixels only, enumerated compactly; a slice is the same number of rows for every tap, so a tap with a small rectangle uses
     // fewer slices (the others return here) and all workgroups reduce equally long
     const bool RECT = GATHER && args.rect != 0;
-    int q_ylo = 0, q_xlo = 0, q_h = g_hd, q_w = g_wd;
-    if (RECT) {
-        const int ky = tap / g_kw, kx = tap - ky * g_kw;
-        int yhi_, xhi_;
-        tap_band(ky * g_dil - g_pad, g_stride, g_hs, g_hd, q_ylo, yhi_);
-        tap_band(kx * g_dil - g_pad, g_stride, g_ws, g_wd, q_xlo, xhi_);
-        q_h = yhi_ - q_ylo; q_w = xhi_ - q_xlo;
-    }
-    const int q_hw = q_h * q_w;
-    const int k_rows = RECT ? (pK / (g_hd * g_wd)) * q_hw : pK;
+    TnSlice ts;
+    if (!tn_slice<TK, true>(ts, blockIdx.z, p_split, pK, RECT, tap, Geo{0, g_hs, g_ws, g_hd, g_wd, 0, g_kw, g_stride, g_pad, g_dil})) return;
+    const int bz = ts.bz, sl = ts.sl, q_ylo = ts.y0, q_xlo = ts.x0, q_w = ts.w, q_hw = ts.h * ts.w, r0 = ts.r0, r1 = ts.r1;
     const float q_inv_hw = 1.0f / (float)(q_hw > 0 ? q_hw : 1), q_inv_w = 1.0f / (float)(q_w > 0 ? q_w : 1);
-    int chunk = (pK + p_split - 1) / p_split;
-    chunk = ((chunk + TK - 1) / TK) * TK;
-    const int r0 = sl * chunk;
-    const int r1 = min(k_rows, r0 + chunk);
-    if (r0 >= r1) return;
+    const u16* __restrict__ A = args.A + (long long)bz * args.bsa;
+    const u16* __restrict__ B = args.B + (long long)bz * args.bsb;
 
     // staging: A instruction j of this wave holds reduction rows wave * 8 + 2 j + (lane >> 5), 16-byte piece lane & 31 of the
     // 512-byte row; B instruction j rows wave * 8 + 4 j + (lane >> 4), piece lane & 15.  Source-side swizzle: the 64-byte chunk
@@ -511,10 +473,7 @@ __global__ __launch_bounds__(NTH, 2) void s16_tn_kernel(const S16Args args) {
     }
     const int hw = GATHER ? g_hd * g_wd : 1;
     int oy = 0, ox = 0;
-    if (GATHER) {
-        const int ky = tap / g_kw, kx = tap - ky * g_kw;
-        oy = ky * g_dil - g_pad; ox = kx * g_dil - g_pad;
-    }
+    if (GATHER) tn_tap_offsets(tap, g_kw, g_pad, g_dil, oy, ox);
     // per-lane element offsets of its rows relative to the tile's first row (the tile base is wave-uniform: scalar arithmetic)
     long long a_base[AJ], b_base[BJ];
 #pragma unroll
@@ -642,12 +601,7 @@ __global__ __launch_bounds__(NTH, 2) void s16_tn_kernel(const S16Args args) {
     // of the nine taps -- K-tiles outside it would multiply zero-page rows, so the cursor jumps over them (wave-uniform scalar
     // arithmetic, two divisions per tile).
     int ylo = 0, yhi = g_hd;
-    if (GATHER) {
-        ylo = oy < 0 ? (-oy + g_stride - 1) / g_stride : 0;
-        const int ymax = (g_hs - 1 - oy) / g_stride;           // largest y with y * stride + oy <= hs - 1 (oy <= hs - 1 for a kept tap)
-        yhi = (g_hs - 1 - oy) < 0 ? 0 : (ymax + 1 < g_hd ? ymax + 1 : g_hd);
-        if (ylo > yhi) ylo = yhi;
-    }
+    if (GATHER) tap_band(oy, g_stride, g_hs, g_hd, ylo, yhi);
     const bool banded = GATHER && !RECT && (ylo > 0 || yhi < g_hd);
     auto next_valid = [&](int r) __attribute__((always_inline)) -> int {
         if (!banded || r >= r1) return r;
@@ -695,12 +649,9 @@ __global__ __launch_bounds__(NTH, 2) void s16_tn_kernel(const S16Args args) {
     u16* __restrict__ Ch = nullptr;
     int ldc_e;
     if (args.partial) {
-        if (RECT) {
-            int nv;
-            Cf = args.partial + (long long)(tn_rect_slab(args.g, p_tap_mask, tap, pK, p_split, nv) + sl) * ((long long)pM * pN);
-        } else {
-            Cf = args.partial + ((long long)blockIdx.z * gridDim.y + blockIdx.y) * ((long long)pM * pN);
-        }
+        int nv;
+        Cf = RECT ? tn_slab(args.partial, tn_rect_slab(args.g, p_tap_mask, tap, pK, p_split, TK, nv) + sl, 1, 0, (long long)pM * pN)
+                  : tn_slab(args.partial, blockIdx.z, gridDim.y, blockIdx.y, (long long)pM * pN);
         ldc_e = pN;
     } else {
         Cf = reinterpret_cast<float*>(args.C) + (long long)bz * args.bsc + (long long)tap * p_tsb;
@@ -735,18 +686,13 @@ __global__ __launch_bounds__(256) void s16_tn_reduce_kernel(const float* __restr
                                                             long long tsb, long long bsc, int split, unsigned tap_mask, int K, int rect, Geo g) {
     constexpr int OG = 256 / SL;                                      // outputs (float4) per block
     __shared__ float4 sh[SL > 1 ? 256 : 1];
-    unsigned mm = tap_mask;
-    for (int i = 0; i < (int)blockIdx.y; ++i) mm &= mm - 1;
-    const int tap = __ffs(mm) - 1;
-    const int ntap = gridDim.y, bz = blockIdx.z;
-    int chunk = (K + split - 1) / split;
-    chunk = ((chunk + TK - 1) / TK) * TK;
+    const int tap = tn_tap(tap_mask, blockIdx.y), ntap = gridDim.y, bz = blockIdx.z;
     const long long mn = (long long)M * N;
-    int nvalid = min(split, (K + chunk - 1) / chunk);                 // slices that ran (the others returned early)
-    const float* __restrict__ src = partial + ((long long)bz * split * ntap + blockIdx.y) * mn;
+    int nvalid = tn_valid_slices(K, K, split, TK);                    // slices that ran (the others returned early)
+    const float* __restrict__ src = tn_slab(partial, bz * split, ntap, blockIdx.y, mn);
     long long slice_stride = (long long)ntap * mn;
     if (rect) {                                                       // compact slabs, tap after tap (batch 1)
-        src = partial + (long long)tn_rect_slab(g, tap_mask, tap, K, split, nvalid) * mn;
+        src = tn_slab(partial, tn_rect_slab(g, tap_mask, tap, K, split, TK, nvalid), 1, 0, mn);
         slice_stride = mn;
     }
     const int n4 = N >> 2;
@@ -952,7 +898,7 @@ extern "C" size_t glf_s16_gemm_tn_workspace_bytes(const glf_gemm_params* p) {
     if (p->rect == 1 && p->gather == 1 && p->batch == 1 && p->hd > 0 && p->wd > 0 && p->kw > 0 && p->stride > 0) {
         const Geo g{p->n_img, p->hs, p->ws, p->hd, p->wd, p->kh, p->kw, p->stride, p->pad, p->dil};
         int nv;
-        return (size_t)tn_rect_slab(g, p->tap_mask, -1, p->K, p->split, nv) * (size_t)p->M * (size_t)p->N * sizeof(float);
+        return (size_t)tn_rect_slab(g, p->tap_mask, -1, p->K, p->split, TK, nv) * (size_t)p->M * (size_t)p->N * sizeof(float);
     }
     return (size_t)p->batch * (size_t)p->split * ntap * (size_t)p->M * (size_t)p->N * sizeof(float);
 }
@@ -987,18 +933,11 @@ extern "C" int glf_s16_gemm_tn(const void* A, const void* B, void* C, const glf_
     else hipLaunchKernelGGL((s16_tn_kernel<false>), grid, dim3(NTH), SMEM_TN16, glf::S(stream), a);
     if (int rc = glf::check_launch("s16_gemm_tn")) return rc;
     if (!two_stage) return GLF_OK;
-    const long long work = (long long)p->M * (p->N / 4);
-    // slice lanes per output: enough threads to keep the slabs' loads in flight (work x lanes >= ~64 k threads), at most 16
-    int lanes = 1;
-    while (lanes < 16 && lanes * 4 <= a.split && work * lanes < 65536) lanes *= 4;
-#define GLF_S16_REDUCE(SL_)                                                                                                          \
-    {                                                                                                                                \
-        long long bx = (work + (256 / SL_) - 1) / (256 / SL_);                                                                       \
-        if (bx > 4096) bx = 4096;                                                                                                    \
-        hipLaunchKernelGGL((s16_tn_reduce_kernel<SL_>), dim3((unsigned)bx, ntap, p->batch), dim3(256), 0, glf::S(stream), a.partial, C, a.c_bf16, \
-                           p->M, p->N, p->ldc, (long long)p->tap_stride_b, (long long)p->batch_stride_c, a.split, p->tap_mask, p->K, a.rect, a.g); \
-    }
-    if (lanes == 16) GLF_S16_REDUCE(16) else if (lanes == 4) GLF_S16_REDUCE(4) else GLF_S16_REDUCE(1)
-#undef GLF_S16_REDUCE
+    const TnReducePlan plan = tn_reduce_plan((long long)p->M * (p->N / 4), a.split, true);
+    const dim3 gr((unsigned)(plan.blocks < 4096 ? plan.blocks : 4096), ntap, p->batch);
+    tn_by_lanes(plan.lanes, [&](auto sl) {
+        hipLaunchKernelGGL((s16_tn_reduce_kernel<sl()>), gr, dim3(256), 0, glf::S(stream), a.partial, C, a.c_bf16, p->M, p->N, p->ldc,
+                           (long long)p->tap_stride_b, (long long)p->batch_stride_c, a.split, p->tap_mask, p->K, a.rect, a.g);
+    });
     return glf::check_launch("s16_gemm_tn(reduce)");
 }
