@@ -231,6 +231,43 @@ __global__ __launch_bounds__(1024) void stem_wgrad_finalize(const float* __restr
         if (t < 49) dw[co * 49 + t] = (float)s; else if (db) db[co] = (float)s;
     }
 }
+// stem dgrad (early_fusion: the stem's input is the learned mix of the views' images, ours.py:2299-2304):
+// dx[n][iy][ix] = sum_taps sum_co dy[n][iy - ky + pad][ix - kx + pad][co] * w[co][ky][kx].  One workgroup = 16x16 input pixels, one
+// pixel per thread; the weights sit in LDS as [tap][co] and are read at wavefront-uniform addresses (broadcast), the 64 gradients of
+// a tap's pixel in 16-byte pieces (neighbouring threads share them through the cache).  Four partial sums, folded (a0 + a1) + (a2 + a3).
+template <bool DY16>
+__global__ __launch_bounds__(256) void stem_dgrad_kernel(const void* __restrict__ dyv, const float* __restrict__ w, float* __restrict__ dx,
+                                                         int h, int wd, int ho, int wo, int pad) {
+    const float* __restrict__ dy = static_cast<const float*>(dyv);
+    const unsigned short* __restrict__ dy16 = static_cast<const unsigned short*>(dyv);
+    __shared__ __attribute__((aligned(16))) float wt[49 * STEM_CO];    // [tap][co]
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 49 * STEM_CO; i += 256) { const int co = i / 49, t = i - co * 49; wt[t * STEM_CO + co] = w[i]; }
+    __syncthreads();
+    const int n = blockIdx.z, iy = blockIdx.y * ST + (tid >> 4), ix = blockIdx.x * ST + (tid & 15);
+    if (iy >= h || ix >= wd) return;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll 1
+    for (int ky = 0; ky < 7; ++ky) {
+        const int oy = iy - ky + pad;
+        if (oy < 0 || oy >= ho) continue;
+#pragma unroll 1
+        for (int kx = 0; kx < 7; ++kx) {
+            const int ox = ix - kx + pad;
+            if (ox < 0 || ox >= wo) continue;
+            const long long p = (((long long)n * ho + oy) * wo + ox) * STEM_CO;
+            const float* wr = wt + (ky * 7 + kx) * STEM_CO;
+#pragma unroll
+            for (int c0 = 0; c0 < STEM_CO; c0 += 8) {
+                const F8 g = DY16 ? ld8(dy16 + p + c0) : ldf8(dy + p + c0);
+                const float4 w0 = *reinterpret_cast<const float4*>(wr + c0), w1 = *reinterpret_cast<const float4*>(wr + c0 + 4);
+                a0 = fmaf(g.v[0], w0.x, a0); a1 = fmaf(g.v[1], w0.y, a1); a2 = fmaf(g.v[2], w0.z, a2); a3 = fmaf(g.v[3], w0.w, a3);
+                a0 = fmaf(g.v[4], w1.x, a0); a1 = fmaf(g.v[5], w1.y, a1); a2 = fmaf(g.v[6], w1.z, a2); a3 = fmaf(g.v[7], w1.w, a3);
+            }
+        }
+    }
+    dx[((long long)n * h + iy) * wd + ix] = (a0 + a1) + (a2 + a3);
+}
 
 // ---------------------------------------------------------------------------------------
 // maxpool 3x3 stride 2 pad 1
@@ -993,6 +1030,25 @@ extern "C" int glf_s16_stem7x7_wgrad(const float* x, const void* dy, float* dw, 
     const long long nblk = (long long)grid.x * grid.y * grid.z;
     hipLaunchKernelGGL(stem_wgrad_finalize, dim3(50), dim3(1024), 0, glf::S(s), partial, nblk, dw, db);
     return glf::check_launch("s16_stem7x7_wgrad_finalize");
+}
+#define REQ_STEM_DGRAD(what) \
+    GLF_REQUIRE(dy && w && dx, GLF_ERR_NULL, what ": null argument"); \
+    GLF_REQUIRE(cout == STEM_CO, GLF_ERR_UNSUPPORTED, "stem7x7: Cout must be 64 (got %d)", cout); \
+    const int ho = h + 2 * pad - 6, wo = wdt + 2 * pad - 6; \
+    GLF_REQUIRE(n > 0 && n <= 65535 && ho > 0 && wo > 0 && pad >= 0 && pad <= 3, GLF_ERR_BAD_SHAPE, what ": bad shape"); \
+    GLF_REQUIRE(al16(dy), GLF_ERR_BAD_SHAPE, what ": dy must be 16-byte aligned"); \
+    dim3 grid((wdt + ST - 1) / ST, (h + ST - 1) / ST, n)
+extern "C" int glf_stem7x7_dgrad(const float* dy, const float* w, float* dx, int n, int h, int wdt, int cout, int pad, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    REQ_STEM_DGRAD("stem7x7_dgrad");
+    hipLaunchKernelGGL(stem_dgrad_kernel<false>, grid, dim3(256), 0, glf::S(s), dy, w, dx, h, wdt, ho, wo, pad);
+    return glf::check_launch("stem7x7_dgrad");
+}
+extern "C" int glf_s16_stem7x7_dgrad(const void* dy, const float* w, float* dx, int n, int h, int wdt, int cout, int pad, glf_stream_t s) {
+    if (int rc = glf::ensure_init()) return rc;
+    REQ_STEM_DGRAD("s16_stem7x7_dgrad");
+    hipLaunchKernelGGL(stem_dgrad_kernel<true>, grid, dim3(256), 0, glf::S(s), dy, w, dx, h, wdt, ho, wo, pad);
+    return glf::check_launch("s16_stem7x7_dgrad");
 }
 
 extern "C" int glf_maxpool3x3s2_fwd(const float* x, float* y, uint8_t* idx, int n, int h, int w, int c, glf_stream_t s) {

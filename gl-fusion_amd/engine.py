@@ -20,11 +20,13 @@ import torch
 from . import ops
 from .ddp import GradAllReducer, all_reduce_counts
 from .optim import SGD, Adam
-from .models import Global_and_Local, baseline_unet, multiview_unet
+from .models import Global_and_Local, MLP_fusion, baseline_unet, early_fusion, late_fusion, multiview_unet
 
-# config['net']['model'] -> class; the U-Net baselines return (mask, None, None, x5): no backbone mask, no fusion features
-MODELS = {"Global_and_Local": Global_and_Local, "baseline_unet": baseline_unet, "multiview_unet": multiview_unet}
-NO_FUSION_FEATURES = ("baseline_unet", "multiview_unet")
+# config['net']['model'] -> class; the U-Net baselines return (mask, None, None, x5) and the fusion baselines (mask, f4, None, None):
+# no backbone mask, no fusion features
+MODELS = {"Global_and_Local": Global_and_Local, "baseline_unet": baseline_unet, "multiview_unet": multiview_unet,
+          "early_fusion": early_fusion, "late_fusion": late_fusion, "MLP_fusion": MLP_fusion}
+NO_FUSION_FEATURES = ("baseline_unet", "multiview_unet", "early_fusion", "late_fusion", "MLP_fusion")
 
 
 class SyntheticClips:
@@ -286,6 +288,14 @@ class Trainer:
         self.optimizer.step()
         return loss.detach(), pred_frames
 
+    def _prediction(self, out, is_fuse: bool):
+        """The mask a scoring pass takes from the model's outputs: the fused one, or with is_fuse False the backbone mask out[1] --
+        where the model has one.  The U-Net baselines return None there, and the fusion baselines their layer-4 features (the
+        model says so: second_output_is_features): their one mask is scored whatever is_fuse says."""
+        if is_fuse or out[1] is None or getattr(self.model, "second_output_is_features", False):
+            return out[0]
+        return out[1]
+
     def _require_fusion_features(self, what: str) -> None:
         if self.model_name in NO_FUSION_FEATURES:
             raise ValueError(f"glfusion_amd: {what} needs the model's fusion features (its third output), and {self.model_name} "
@@ -343,7 +353,7 @@ class Trainer:
             for v in self.view_num:
                 imgs[v], masks[v] = _data.prepare_frames(sample[v][0], sample[v][1], v, train=False)
             out = self.model(imgs)
-            pred = out[0] if (is_fuse or out[1] is None) else out[1]     # the U-Net baselines have one mask only
+            pred = self._prediction(out, is_fuse)
             for v in self.test_view:
                 counts[v] += part_overlap_counts(pred[v], masks[v])
                 loss4view[v] += float(ops.bce_with_logits_sum(pred[v], masks[v]))
@@ -400,7 +410,7 @@ class Trainer:
             for v in self.view_num:
                 imgs[v], masks[v] = _data.prepare_frames(sample[v][0], sample[v][1], v, train=False)
             out = self.model(imgs)
-            pred = out[0] if (is_fuse or out[1] is None) else out[1]     # the U-Net baselines have one mask only
+            pred = self._prediction(out, is_fuse)
             manifest[pid] = {}
             for v in self.test_view:
                 if on_clip is not None:
@@ -461,7 +471,7 @@ class Trainer:
                     imgs = {v: t[:frames] for v, t in imgs.items()}
                     masks = {v: t[:frames] for v, t in masks.items()}
                     out = self.model(imgs)
-                    pred = out[0] if (is_fuse or out[1] is None) else out[1]     # the U-Net baselines have one mask only
+                    pred = self._prediction(out, is_fuse)
                     for v in self.test_view:
                         counts[v] += part_overlap_counts(pred[v], masks[v])
                         loss4view[v] += float(ops.bce_with_logits_sum(pred[v], masks[v]))

@@ -606,3 +606,113 @@ class multiview_unet(baseline_unet):
         fused = ops.split_views(self.global_attn.forward_nvhwc(ops.stack_views([e[1] for e in enc])))   # ours.py:2598-2602
         d1 = ops.parallel_sections([lambda i=i, v=v: self._decode_view(v, enc[i][0], fused[i]) for i, v in enumerate(views)])
         return dict(zip(views, d1)), None, None, {v: ops.from_nhwc(f) for v, f in zip(views, fused)}
+
+
+# ------------------------------------------------------------------------------------------
+# the classical multi-view fusion baselines (ours.py:1044-1107, 2251-2383)
+# ------------------------------------------------------------------------------------------
+class _FusionBaseline(nn.Module):
+    """The constructor early_fusion, late_fusion and MLP_fusion share in the reference: the per-view ResNet-50 stacks and 5-class
+    heads of _PerViewNetworks without centre-ness heads, one per-view 1x1 convolution `fc[view]` over the channel concatenation of
+    all views (`_fc_channels` channels per view) registered between the stacks and the heads, and a TPAVIModule `non_local` that no
+    forward calls (`non_local.*` and the template `network.*` are in the state_dict and never get a gradient).
+    forward(x {view: [N,1,H,W]}) -> (mask {view: [N,5,H,W] logits}, f4 {view: [N,2048,h,w] layer-4 features}, None, None)."""
+    _fc_channels = 0
+    second_output_is_features = True          # out[1] is f4, not a backbone mask: the Trainer scores out[0] whatever is_fuse says
+
+    def __init__(self, view_num: Sequence[str], test_view: Sequence[str] = ("1", "2", "3", "4")) -> None:
+        super().__init__()
+        self.outchannel_list = {"1": 2, "2": 1, "3": 2, "4": 4}
+        self.view_num = view_num
+        self.test_view = test_view
+        self.network = deeplabv3_resnet50_iekd(pretrained=False, aux_loss=False)
+        for name in ("init_block", "layer1", "layer2", "layer3", "layer4", "fc", "classifier"):      # the reference's registration order
+            setattr(self, name, nn.ModuleDict())
+        bb = self.network.backbone
+        last = self.network.classifier[-1]
+        ch = self._fc_channels
+        for view in self.view_num:
+            self.init_block[view] = copy.deepcopy(nn.Sequential(bb["conv1"], bb["bn1"], bb["relu"], bb["maxpool"]))
+            for l in ("layer1", "layer2", "layer3", "layer4"):
+                getattr(self, l)[view] = copy.deepcopy(bb[l])
+            self.fc[view] = Conv2d(ch * len(self.view_num), ch, kernel_size=1)
+            self.classifier[view] = copy.deepcopy(self.network.classifier)
+            self.classifier[view][-1] = Conv2d(last.in_channels, 5, kernel_size=last.kernel_size)
+        self.non_local = TPAVIModule(in_channels=2048, mode="dot")
+
+    _encode_view = _PerViewNetworks._encode_view
+
+    def _mix(self, xs):
+        """fc[v] over the concatenation of the V tensors xs, for every view, in one launch (ops.view_mix)."""
+        views = list(self.view_num)
+        return ops.view_mix(xs, [self.fc[v].weight for v in views], [self.fc[v].bias for v in views])
+
+    def _head(self, v: str, f: torch.Tensor, ho: int, wo: int) -> torch.Tensor:
+        return ops.bilinear_up(self.classifier[v].forward_nhwc(f), ho, wo)
+
+
+class early_fusion(_FusionBaseline):
+    """ours.py:2251-2315: fc[view] = Conv2d(V, 1, 1) mixes the V input images; every view's network then runs on its own mix.
+    The reference writes the mixed image back into the caller's dict (`x[view] = self.fc[view](concat_input)`, a side effect of
+    reusing the name); this forward does NOT: the caller's dict and tensors are left as they were."""
+    _fc_channels = 1
+
+    def forward(self, x: Dict[str, torch.Tensor]):
+        views = list(self.view_num)
+        ho, wo = int(x[views[0]].shape[-2]), int(x[views[0]].shape[-1])
+        ops.begin_step(x[views[0]].device)
+        mixed = self._mix([ops.to_nhwc(x[v]) for v in views])            # [N,H,W,1]: free for one channel
+
+        def view_section(i, v):
+            fa, fr = ops.fan_out(self._encode_view(v, ops.from_nhwc(mixed[i])), 2)       # head / returned f4
+            return self._head(v, fa, ho, wo), ops.from_nhwc(fr)
+
+        secs = ops.parallel_sections([lambda i=i, v=v: view_section(i, v) for i, v in enumerate(views)])
+        return {v: s[0] for v, s in zip(views, secs)}, {v: s[1] for v, s in zip(views, secs)}, None, None
+
+
+class late_fusion(_FusionBaseline):
+    """ours.py:2317-2383: fc[view] = Conv2d(5 V, 5, 1) mixes the V heads' logits (at feature resolution, before the up-sampling)."""
+    _fc_channels = 5
+
+    def forward(self, x: Dict[str, torch.Tensor]):
+        views = list(self.view_num)
+        ho, wo = int(x[views[0]].shape[-2]), int(x[views[0]].shape[-1])
+        ops.begin_step(x[views[0]].device)
+
+        def view_section(v):
+            fa, fr = ops.fan_out(self._encode_view(v, x[v]), 2)           # head / returned f4
+            return self.classifier[v].forward_nhwc(fa), ops.from_nhwc(fr)  # fp32 [N,h,w,5] under every precision
+
+        secs = ops.parallel_sections([lambda v=v: view_section(v) for v in views])
+        mixed = self._mix([s[0] for s in secs])
+        masks = [ops.bilinear_up(m, ho, wo) for m in mixed]
+        return dict(zip(views, masks)), {v: s[1] for v, s in zip(views, secs)}, None, None
+
+
+class MLP_fusion(_FusionBaseline):
+    """ours.py:1044-1107: fc[view] = Conv2d(2048 V, 2048, 1) mixes the V layer-4 feature maps.  With fp32 storage the
+    concatenation is never made (ops.conv1x1_cat: V accumulated K = 2048 contractions per view, as
+    Global_and_Local_conv_merge.merge).  The 16-bit contractions do not accumulate into their output, so under bf16 storage the V
+    maps are concatenated once (ops.concat_channels, V - 1 passes over a bf16 tensor) and every fc[view] is one K = 2048 V
+    contraction over that."""
+    _fc_channels = 2048
+
+    def forward(self, x: Dict[str, torch.Tensor]):
+        views = list(self.view_num)
+        nv = len(views)
+        ho, wo = int(x[views[0]].shape[-2]), int(x[views[0]].shape[-1])
+        ops.begin_step(x[views[0]].device)
+        if ops.s16():
+            secs = ops.parallel_sections([lambda v=v: ops.fan_out(self._encode_view(v, x[v]), 2) for v in views])      # concatenation / returned f4
+            cat = secs[0][0]
+            for s in secs[1:]:
+                cat = ops.concat_channels(cat, s[0])
+            cats = ops.fan_out(cat, nv)
+            mixed = lambda i, v: self.fc[v].forward_nhwc(cats[i])
+        else:
+            # every f4[u] has V + 1 readers: the V mixing convolutions and the returned features
+            secs = ops.parallel_sections([lambda v=v: ops.fan_out(self._encode_view(v, x[v]), nv + 1) for v in views])
+            mixed = lambda i, v: ops.conv1x1_cat(self.fc[v].weight, [s[i] for s in secs], self.fc[v].bias)
+        masks = ops.parallel_sections([lambda i=i, v=v: self._head(v, mixed(i, v), ho, wo) for i, v in enumerate(views)])
+        return dict(zip(views, masks)), {v: ops.from_nhwc(s[-1]) for v, s in zip(views, secs)}, None, None

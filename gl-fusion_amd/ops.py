@@ -1611,23 +1611,25 @@ class StemFn(Function):
         cout = weight.shape[0]
         y = torch.empty(n, h + 2 * pad - 6, w + 2 * pad - 6, cout, dtype=torch.float32, device=x.device)
         check(lib.glf_stem7x7_fwd(_p(x), _p(_contig(weight.detach())), _p(bias), _p(y), n, h, w, cout, pad, _stream()), "stem7x7_fwd")
-        ctx.save_for_backward(x)
+        ctx.save_for_backward(x, weight)
         ctx.cfg = (n, h, w, cout, pad, tuple(weight.shape), bias is not None)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
+        x, weight = ctx.saved_tensors
         n, h, w, cout, pad, wshape, has_bias = ctx.cfg
-        if ctx.needs_input_grad[0]:
-            raise RuntimeError("glfusion_amd: gradient w.r.t. the input image is not on the path (stem dgrad not built)")
         dy = _contig(dy)
+        dx = None
+        if ctx.needs_input_grad[0]:                     # the image is itself computed: early_fusion's learned mix of the views
+            dx = torch.empty_like(x)
+            check(lib.glf_stem7x7_dgrad(_p(dy), _p(_contig(weight.detach())), _p(dx), n, h, w, cout, pad, _stream()), "stem7x7_dgrad")
         dw = torch.empty(wshape, dtype=torch.float32, device=dy.device)
         db = torch.empty(cout, dtype=torch.float32, device=dy.device) if has_bias else None
         part = torch.empty(int(lib.glf_stem7x7_wgrad_workspace(n, h, w, cout, pad)), dtype=torch.float32, device=dy.device)
         check(lib.glf_stem7x7_wgrad(_p(x), _p(dy), _p(dw), _p(db), _p(part), n, h, w, cout, pad, _stream()), "stem7x7_wgrad")
-        return None, dw, db, None
+        return dx, dw, db, None
 
 
 def stem7x7(x, weight, bias, pad: int):
@@ -2263,6 +2265,125 @@ class ConcatChannelsFn(Function):
 
 def concat_channels(a, b):
     return ConcatChannelsFn.apply(a, b)
+
+
+# ----------------------------------------------------------------------------------------
+# the view mix of the classical fusion baselines (ours.py:2251-2383; csrc/view_mix.hip)
+# ----------------------------------------------------------------------------------------
+VIEW_MIX_MAX_V, VIEW_MIX_MAX_C, VIEW_MIX_MAX_VC = 8, 8, 40
+VIEW_MIX_WGRAD_ROWS = 1024             # VM_WGRAD_ROWS: consecutive rows one workgroup reduces in wgrad
+_view_mix_cache = {}
+
+
+def view_mix_stack(weights, biases):
+    """The operands of glf_view_mix_*: the V Conv2d weights [c, V c, 1, 1] stacked by rows into Wm [V c][V c]
+    (Wm[v c + o][u c + i] = W_v[o][u c + i]) and the V biases into bm [V c].  A pure index permutation, on any device."""
+    c, vc = int(weights[0].shape[0]), int(weights[0].shape[1])
+    if len(weights) != len(biases) or len(weights) * c != vc or any(tuple(w.shape) != (c, vc, 1, 1) for w in weights) \
+            or any(tuple(b.shape) != (c,) for b in biases):
+        raise RuntimeError(f"view_mix: {len(weights)} weights of shape [c, V c, 1, 1] and as many biases [c] expected "
+                           f"(got {[tuple(w.shape) for w in weights]}, {[tuple(b.shape) for b in biases]})")
+    return torch.cat([w.detach().reshape(c, vc) for w in weights], dim=0), torch.cat([b.detach() for b in biases], dim=0)
+
+
+def _view_mix_images(weights, biases):
+    """view_mix_stack on the device as registered weight images, like fusion._qkv_weights: the two buffers live as long as the first
+    weight, every row block is a GLF_WJ_COPY image of its parameter -- rebuilt when that parameter's version moved, or by
+    refresh_weights().  The blocks are c * V c (and c) floats long, in general no multiple of the 16 bytes glf_copy_frames moves: a
+    stale block is brought up to date by a device-to-device copy."""
+    w0 = weights[0]
+    c, vc = int(w0.shape[0]), int(w0.shape[1])
+    key = id(w0)
+    params = list(weights) + list(biases)
+    hit = _view_mix_cache.get(key)
+    if (hit is None or hit[0]() is not w0 or hit[1].device != w0.device or tuple(hit[1].shape) != (vc, vc)
+            or any(r() is not t for r, t in zip(hit[1]._glf_sources, params))):
+        view_mix_stack(weights, biases)                                  # the shape checks
+        Wm = torch.empty(vc, vc, dtype=torch.float32, device=w0.device)
+        bm = torch.empty(vc, dtype=torch.float32, device=w0.device)
+        Wm._glf_sources = [weakref.ref(t) for t in params]
+        hit = _view_mix_cache[key] = (weakref.ref(w0, lambda _r, k=key: _view_mix_cache.pop(k, None)), Wm, bm)
+    _, Wm, bm = hit
+    for i, (w, b) in enumerate(zip(weights, biases)):
+        for t, dst, n in ((w, Wm[i * c:(i + 1) * c], c * vc), (b, bm[i * c:(i + 1) * c], c)):
+            src = _contig(_chk(t, "view_mix weight").detach())
+            im, fresh = _wimage(t, "viewmix", WJ_COPY, src, (n, 0, 0), lambda dst=dst: dst)
+            if im.dst.data_ptr() != dst.data_ptr():       # the stacked buffers were re-created: re-register
+                _registry(t.device).drop(im.key)
+                im, fresh = _wimage(t, "viewmix", WJ_COPY, src, (n, 0, 0), lambda dst=dst: dst)
+            if fresh:
+                im.dst.copy_(src.view(im.dst.shape))
+    return Wm, bm
+
+
+def _ptr_table(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _view_mix_operand(t: torch.Tensor, name: str, shape=None) -> torch.Tensor:
+    _chk(t, name)
+    if not t.is_contiguous():
+        raise RuntimeError(f"glfusion_amd: {name} must be contiguous (got strides {tuple(t.stride())} for shape {tuple(t.shape)})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"glfusion_amd: {name} has shape {tuple(t.shape)}, the first view {tuple(shape)}")
+    return t if t.data_ptr() % 16 == 0 else t.clone()      # a slice that starts inside a 16-byte piece
+
+
+class ViewMixFn(Function):
+    """y_v = fc[v](torch.cat(xs, dim=1)) for every view v in ONE launch (glf_view_mix_fwd); the concatenation is never made.
+    apply(V, x_0 .. x_{V-1}, W_0 .. W_{V-1}, b_0 .. b_{V-1}) -> V outputs."""
+
+    @staticmethod
+    def forward(ctx, v: int, *args):
+        xs, weights, biases = args[:v], args[v:2 * v], args[2 * v:]
+        c = int(weights[0].shape[0])
+        if v > VIEW_MIX_MAX_V or c > VIEW_MIX_MAX_C or v * c > VIEW_MIX_MAX_VC:
+            raise RuntimeError(f"view_mix: the limit is c <= {VIEW_MIX_MAX_C}, V <= {VIEW_MIX_MAX_V}, V * c <= {VIEW_MIX_MAX_VC} (got V = {v}, c = {c})")
+        xs = [_view_mix_operand(t, "view_mix input", xs[0].shape) for t in xs]
+        if c != 1 and int(xs[0].shape[-1]) != c:
+            raise RuntimeError(f"view_mix: channels-last inputs [..., {c}] expected, got shape {tuple(xs[0].shape)}")
+        Wm, bm = _view_mix_images(weights, biases)
+        rows = xs[0].numel() // c
+        ys = [torch.empty_like(xs[0]) for _ in range(v)]
+        check(lib.glf_view_mix_fwd(_ptr_table(xs), _p(Wm), _p(bm), _ptr_table(ys), rows, v, c, _stream()), "view_mix_fwd")
+        ctx.save_for_backward(*xs)
+        ctx.cfg = (v, c, rows, Wm)
+        return tuple(ys)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *dys):
+        xs = ctx.saved_tensors
+        v, c, rows, Wm = ctx.cfg
+        dev = xs[0].device
+        dys = [_view_mix_operand(_contig(d), "view_mix grad", xs[0].shape) if d is not None else zeros(xs[0].shape, device=dev) for d in dys]
+        need = ctx.needs_input_grad
+        dxs = [None] * v
+        if any(need[1:1 + v]):                              # early_fusion's inputs are data: no dgrad launch
+            dxs = [torch.empty_like(xs[0]) for _ in range(v)]
+            check(lib.glf_view_mix_dgrad(_ptr_table(dys), _p(Wm), _ptr_table(dxs), rows, v, c, _stream()), "view_mix_dgrad")
+            dxs = [d if n else None for d, n in zip(dxs, need[1:1 + v])]
+        dws, dbs = [None] * v, [None] * v
+        if any(need[1 + v:]):
+            vc = v * c
+            dw = torch.empty(vc, vc, dtype=torch.float32, device=dev)
+            db = torch.empty(vc, dtype=torch.float32, device=dev)
+            nbytes = int(lib.glf_view_mix_wgrad_workspace(rows, v, c))
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+            check(lib.glf_view_mix_wgrad(_ptr_table(xs), _ptr_table(dys), _p(dw), _p(db), _p(ws), nbytes, rows, v, c, _stream()), "view_mix_wgrad")
+            dws = [dw[i * c:(i + 1) * c].view(c, vc, 1, 1) if need[1 + v + i] else None for i in range(v)]
+            dbs = [db[i * c:(i + 1) * c] if need[1 + 2 * v + i] else None for i in range(v)]
+        return (None, *dxs, *dws, *dbs)
+
+
+def view_mix(xs: Sequence[torch.Tensor], weights: Sequence[torch.Tensor], biases: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+    """[fc_v(torch.cat(xs, dim=1)) for v] for V per-view Conv2d(V c, c, 1) with the weights [c, V c, 1, 1] and biases [c] as they sit
+    in the modules.  xs: V contiguous fp32 tensors of one shape with the c channels innermost ([N,h,w,c]; any shape for c = 1, as
+    an [N,1,H,W] image is its own channels-last form).  Limits: c <= 8, V <= 8, V c <= 40."""
+    v = len(xs)
+    if v == 0 or len(weights) != v or len(biases) != v:
+        raise RuntimeError(f"view_mix: {v} inputs, {len(weights)} weights, {len(biases)} biases")
+    return list(ViewMixFn.apply(v, *xs, *weights, *biases))
 
 
 class AvgPoolFn(Function):

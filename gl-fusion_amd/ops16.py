@@ -424,23 +424,25 @@ class Stem16Fn(Function):
         cout = weight.shape[0]
         y = torch.empty(n, h + 2 * pad - 6, w + 2 * pad - 6, cout, dtype=BF, device=x.device)
         check(lib.glf_s16_stem7x7_fwd(_p(x), _p(_contig(weight.detach())), _p(bias), _p(y), n, h, w, cout, pad, _stream()), "s16_stem7x7_fwd")
-        ctx.save_for_backward(x)
+        ctx.save_for_backward(x, weight)
         ctx.cfg = (n, h, w, cout, pad, tuple(weight.shape), bias is not None)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
+        x, weight = ctx.saved_tensors
         n, h, w, cout, pad, wshape, has_bias = ctx.cfg
-        if ctx.needs_input_grad[0]:
-            raise RuntimeError("glfusion_amd: gradient w.r.t. the input image is not on the path (stem dgrad not built)")
         dy = _contig(dy)
+        dx = None
+        if ctx.needs_input_grad[0]:                     # the image is itself computed: early_fusion's learned mix of the views
+            dx = torch.empty_like(x)
+            check(lib.glf_s16_stem7x7_dgrad(_p(dy), _p(_contig(weight.detach())), _p(dx), n, h, w, cout, pad, _stream()), "s16_stem7x7_dgrad")
         dw = torch.empty(wshape, dtype=torch.float32, device=dy.device)
         db = torch.empty(cout, dtype=torch.float32, device=dy.device) if has_bias else None
         part = torch.empty(int(lib.glf_stem7x7_wgrad_workspace(n, h, w, cout, pad)), dtype=torch.float32, device=dy.device)
         check(lib.glf_s16_stem7x7_wgrad(_p(x), _p(dy), _p(dw), _p(db), _p(part), n, h, w, cout, pad, _stream()), "s16_stem7x7_wgrad")
-        return None, dw, db, None
+        return dx, dw, db, None
 
 
 def stem7x7(x, weight, bias, pad: int):

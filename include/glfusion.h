@@ -546,6 +546,7 @@ int glf_s16_stem7x7_fwd(const float* x, const float* w, const float* bias, void*
                         int n, int h, int wdt, int cout, int pad, glf_stream_t s);
 int glf_s16_stem7x7_wgrad(const float* x, const void* dy, float* dw, float* db, float* partial,
                           int n, int h, int wdt, int cout, int pad, glf_stream_t s);
+int glf_s16_stem7x7_dgrad(const void* dy, const float* w, float* dx, int n, int h, int wdt, int cout, int pad, glf_stream_t s);
 int glf_s16_maxpool3x3s2_fwd(const void* x, void* y, uint8_t* idx, int n, int h, int w, int c, glf_stream_t s);
 int glf_s16_maxpool3x3s2_bwd(const void* dy, const uint8_t* idx, void* dx, int n, int h, int w, int c, glf_stream_t s);
 /* y[n][c] = scale * sum_p x[n][p][c] (x bf16, row stride ldx; y of y_dtype); y[n][p][c] (bf16, row stride ldy) = scale * x[n][c]
@@ -636,6 +637,11 @@ int glf_stem7x7_bn_relu_pool(const float* x, const float* w, const float* bias, 
 size_t glf_stem7x7_wgrad_workspace(int n, int h, int wdt, int cout, int pad);
 int glf_stem7x7_wgrad(const float* x, const float* dy, float* dw, float* db, float* partial,
                       int n, int h, int wdt, int cout, int pad, glf_stream_t s);
+/* The stem's input gradient, for a stem whose image is itself computed (early_fusion mixes the views' images by a learned 1x1
+ * convolution, ours.py:2299-2304): dx [N][H][W] fp32, dx[n][iy][ix] = sum_taps sum_co dy[n][iy - ky + pad][ix - kx + pad][co] *
+ * w[co][ky][kx] over the taps that land inside dy [N][H + 2 pad - 6][W + 2 pad - 6][Cout] (16-byte aligned; bf16 for glf_s16_*).
+ * Every element of dx is written once; no atomics. */
+int glf_stem7x7_dgrad(const float* dy, const float* w, float* dx, int n, int h, int wdt, int cout, int pad, glf_stream_t s);
 
 /* ---------------------------------------------------------------------------------------
  * BatchNorm (nn.BatchNorm2d / BatchNorm3d in train and eval mode), channels-last [rows][C].
@@ -824,6 +830,27 @@ int glf_add_frames(const float* a, int64_t a_fs, const float* b, int64_t b_fs, f
 /* out = sum of k (<= 8) same-sized tensors given as a HOST array of device pointers: the gradient fan-in of a
  * tensor that feeds several branches (f4 -> classifier / centerness / gate / fusion; ASPP input -> 5 branches). */
 int glf_add_n(const float* const* inputs, int k, float* out, int64_t numel, glf_stream_t s);
+/* ---------------------------------------------------------------------------------------
+ * The view mix of the classical fusion baselines (early_fusion, late_fusion; ours.py:2251-2383; view_mix.hip): V per-view 1x1
+ * convolutions over the channel concatenation of all V views, in one streaming pass that reads every view once and writes every
+ * view's output once:
+ *     y_v[r][o] = b_v[o] + sum_u sum_i W_v[o][u c + i] x_u[r][i]        (u c + i: the column order of torch.cat(dim=1))
+ * xs / ys / dys / dxs are HOST arrays of V device pointers (as glf_add_n's inputs), each a contiguous, 16-byte aligned fp32
+ * [rows][c] tensor; w is the V weights [c][V c] stacked by rows into one [V c][V c] matrix, bias the V biases stacked into [V c]
+ * (NULL: none).  All data is fp32 under every precision.  Limits: c <= 8, V <= 8, V c <= 40; anything else is
+ * GLF_ERR_UNSUPPORTED.  A null pointer, a misaligned tensor or a non-positive extent is GLF_ERR_BAD_SHAPE.  A thread moves the
+ * smallest run of rows whose bytes are a multiple of 16 (4 / gcd(c, 4) rows) with 16-byte accesses; the rows left over take a
+ * scalar path; every output element is written exactly once.
+ * dgrad: dx_u[r][i] = sum_v sum_o W_v[o][u c + i] dy_v[r][o] -- the same kernel on the transposed matrix, without the bias.
+ * wgrad: dW[v c + o][u c + i] = sum_r dy_v[r][o] x_u[r][i] (dw [V c][V c]) and db[v c + o] = sum_r dy_v[r][o] (db [V c], may be
+ * NULL).  No atomics: each workgroup reduces 1024 consecutive rows into a block of V c (V c + 1) partial sums in `workspace`
+ * (caller-owned, uninitialised, 16-byte aligned, `bytes` >= glf_view_mix_wgrad_workspace() BYTES; a smaller one is
+ * GLF_ERR_WORKSPACE), and a finalize folds the blocks in float64 in a fixed order: bit-identical from call to call. */
+int glf_view_mix_fwd(const float* const* xs, const float* w, const float* bias, float* const* ys, int64_t rows, int v, int c, glf_stream_t s);
+int glf_view_mix_dgrad(const float* const* dys, const float* w, float* const* dxs, int64_t rows, int v, int c, glf_stream_t s);
+size_t glf_view_mix_wgrad_workspace(int64_t rows, int v, int c);
+int glf_view_mix_wgrad(const float* const* xs, const float* const* dys, float* dw, float* db, void* workspace, size_t bytes,
+                       int64_t rows, int v, int c, glf_stream_t s);
 /* W_z tail of TPAVIModule (ours.py:908-915): z = LayerNorm_C( BN(w) + x ) with the BN already
  * folded into per-channel (bn_mean, bn_invstd, gamma, beta).  Saves row mean / rstd.  amax_out (may be NULL): as in
  * glf_bn_apply, receives max(*amax_out, max|z|). */

@@ -35,9 +35,10 @@ def main(rank, config):
     parser.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
                         help="clip every step by the global gradient norm X and skip steps with a non-finite one, on the device "
                              "(config['train']['clip_grad_norm']; inf = the guard alone); default: off")
-    parser.add_argument("--model", type=str, default=None, choices=("Global_and_Local", "baseline_unet", "multiview_unet"),
+    parser.add_argument("--model", type=str, default=None, choices=("Global_and_Local", "baseline_unet", "multiview_unet", "early_fusion", "late_fusion", "MLP_fusion"),
                         help="the network (config['net']['model']); default: the config's, else Global_and_Local.  The U-Net "
-                             "baselines (ours.py:2416-2625) return no fusion features and train without the cycle loss")
+                             "baselines (ours.py:2416-2625) and the fusion baselines early_fusion / late_fusion / MLP_fusion "
+                             "(ours.py:2251-2383, 1044-1107) return no fusion features and train without the cycle loss")
     args = parser.parse_args()
     if args.model:
         config["net"]["model"] = args.model
