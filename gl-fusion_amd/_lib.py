@@ -94,6 +94,16 @@ class WeightJob(C.Structure):
                 ("d0", C.c_int32), ("d1", C.c_int32), ("d2", C.c_int32), ("reserved", C.c_int32), ("first_wg", C.c_int64)]
 
 
+class FrameSrc(C.Structure):
+    """Mirror of glf_frame_src (include/glfusion.h)."""
+    _fields_ = [("img", C.c_void_p), ("lab", C.c_void_p), ("img_dtype", C.c_int32), ("lab_dtype", C.c_int32),
+                ("H0", C.c_int32), ("W0", C.c_int32), ("T", C.c_int32), ("t0", C.c_int32), ("nt", C.c_int32),
+                ("resize", C.c_int32), ("off_y", C.c_int32), ("off_x", C.c_int32), ("class_to_channel", C.c_int32 * 4),
+                ("img_div", C.c_float), ("reserved", C.c_int32)]
+
+
+SRC_F32, SRC_U8 = 0, 1        # GLF_SRC_F32, GLF_SRC_U8
+
 WJ_COPY, WJ_AMAX, WJ_TAP_MAJOR, WJ_TAP_MAJOR_T, WJ_TRANSPOSE, WJ_PACK, WJ_ZERO, WJ_CVT_BF16, WJ_PASSES = 0, 1, 2, 3, 4, 5, 6, 7, 4
 WJ_PASS_OF = {WJ_COPY: 0, WJ_ZERO: 0, WJ_AMAX: 1, WJ_TAP_MAJOR: 2, WJ_TAP_MAJOR_T: 2, WJ_TRANSPOSE: 2, WJ_PACK: 3, WJ_CVT_BF16: 3}
 

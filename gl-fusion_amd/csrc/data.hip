@@ -8,6 +8,9 @@
 //   * glf_render_labels / glf_restore_labels: the visual mode (main.py:546-648).  Label map = argmax over [0.5, on_0 .. on_{C-1}]
 //     (main.py:606-612), coloured through a palette (main.py:623-634) with an optional integer blend over the grey frame, and the
 //     way back from the 112 x 112 crop to the source volume's geometry (the inverse of glf_prepare_frames), [H0][W0][T] uint8.
+//   * glf_frame_label_sums / glf_prepare_batch: the training loaders (main.py:116-145, 185-218).  Per-frame sums of a resident label
+//     volume (input_select's masks.sum(dim=(0, 1)), loader.py:429-458), and the frames of MANY (volume, frame window, crop) sources in
+//     one call, from uint8 or float32 volumes, by glf_prepare_frames' arithmetic (one shared per-pixel body).
 // HBM-bound byte / index work: one thread per output pixel, coalesced along x.
 #include "glf_common.h"
 #include <cstdint>
@@ -25,27 +28,122 @@ __device__ __forceinline__ int nearest_src(int dst, float scale, int in) {
     return s < in - 1 ? s : in - 1;
 }
 
+// One output pixel of the data path, the body glf_prepare_frames and glf_prepare_batch share: output pixel (y, x) of a frame reads
+// voxel (ys, xs, t) of a [H0][W0][T] volume (T fastest) stored as TI / TL (float or uint8_t: a byte converts to float / int exactly,
+// so both storages give the same bits).  o_img: this pixel of the frame's image plane or null; o_mask: this pixel of the frame's
+// channel 0 plane or null, the 5 channel planes `plane` floats apart.
+template <typename TI, typename TL>
+__device__ __forceinline__ void prepare_pixel(const TI* __restrict__ img, const TL* __restrict__ lab, float* __restrict__ o_img,
+                                              float* __restrict__ o_mask, long long plane, int y, int x, int t, int H0, int W0, int T,
+                                              float sy, float sx, int oy, int ox, int4 chan, float img_div) {
+    const int ys = nearest_src(y + oy, sy, H0), xs = nearest_src(x + ox, sx, W0);
+    const long long src = ((long long)ys * W0 + xs) * T + t;
+    if (o_img) *o_img = (float)img[src] / img_div;              // a true division: bit-identical to `images / 255.0` (loader.py:327)
+    if (o_mask) {
+        const int cls = (int)lab[src];                          // 0 = background, 1..4 = parts of this view
+        const int ch = cls == 1 ? chan.x : cls == 2 ? chan.y : cls == 3 ? chan.z : cls == 4 ? chan.w : -1;
+#pragma unroll
+        for (int c = 0; c < 5; ++c) o_mask[(long long)c * plane] = (c == ch) ? 1.f : 0.f;
+    }
+}
+
 // img / lab: [H0][W0][T] (T fastest, the NIfTI volume order nibabel hands over); out_img [T][1][oh][ow]; out_mask [T][5][oh][ow]
 __global__ __launch_bounds__(256) void prepare_frames_kernel(const float* __restrict__ img, const float* __restrict__ lab,
                                                              float* __restrict__ out_img, float* __restrict__ out_mask, int H0, int W0, int T,
                                                              int rs, int oh, int ow, int oy, int ox, int4 chan_lo, int chan_4, float img_div) {
-    const long long total = (long long)T * oh * ow;
+    const long long total = (long long)T * oh * ow, plane = (long long)oh * ow;
     const float sy = (float)H0 / (float)rs, sx = (float)W0 / (float)rs;
+    (void)chan_4;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int x = (int)(i % ow);
         const int y = (int)((i / ow) % oh);
-        const int t = (int)(i / ((long long)ow * oh));
-        const int ys = nearest_src(y + oy, sy, H0), xs = nearest_src(x + ox, sx, W0);
-        const long long src = ((long long)ys * W0 + xs) * T + t;
-        if (out_img) out_img[i] = img[src] / img_div;              // a true division: bit-identical to `images / 255.0` (loader.py:327)
-        if (out_mask) {
-            const int cls = (int)lab[src];                      // 0 = background, 1..4 = parts of this view
-            const int ch = cls == 1 ? chan_lo.x : cls == 2 ? chan_lo.y : cls == 3 ? chan_lo.z : cls == 4 ? chan_lo.w : -1;
-            (void)chan_4;
-            float* m = out_mask + ((long long)t * 5) * oh * ow + (long long)y * ow + x;
+        const int t = (int)(i / plane);
+        prepare_pixel(img, lab, out_img ? out_img + i : nullptr, out_mask ? out_mask + (long long)t * 5 * plane + (long long)y * ow + x : nullptr,
+                      plane, y, x, t, H0, W0, T, sy, sx, oy, ox, chan_lo, img_div);
+    }
+}
+
+// ---- glf_prepare_batch: many sources, one launch per chunk -------------------------------------------------------------
+constexpr int kBatchChunk = 32;                     // sources per launch: 32 x 64 B + 16 B of scalars = 2 064 B of kernel arguments
+struct BatchSrc {                                   // what the kernel needs of a glf_frame_src, 64 bytes
+    const void* img; const void* lab;               // img null: the source's frames are zeros (a patient without this view)
+    int H0, W0, T, t0;
+    int rs, oy, ox;
+    float img_div;
+    int first;                                      // first output frame of this source WITHIN the chunk
+    int8_t chan[4];
+    uint8_t img_u8, lab_u8, pad[2];
+    int pad2;
+};
+static_assert(sizeof(BatchSrc) == 64, "BatchSrc is the by-value kernel argument: keep it 64 bytes");
+struct BatchChunk { BatchSrc src[kBatchChunk]; };
+
+// out_img [frames][1][oh][ow], out_mask [frames][5][oh][ow] (or null), both already advanced to the chunk's first frame.  A block
+// belongs to ONE output frame (bpf blocks per frame), so the walk that finds the frame's source is uniform over the block and reads
+// kernel arguments only: at most kBatchChunk compares, never more than this chunk.
+__global__ __launch_bounds__(256) void prepare_batch_kernel(BatchChunk chunk, int n, float* __restrict__ out_img,
+                                                            float* __restrict__ out_mask, int oh, int ow, int bpf) {
+    const int f = blockIdx.x / bpf;
+    const int p = (blockIdx.x - f * bpf) * 256 + threadIdx.x;
+    const int plane = oh * ow;
+    if (p >= plane) return;
+    int k = 0;
+    while (k + 1 < n && chunk.src[k + 1].first <= f) ++k;
+    const BatchSrc& s = chunk.src[k];
+    const int y = p / ow, x = p - y * ow;
+    float* o_img = out_img + (long long)f * plane + p;
+    float* o_mask = out_mask ? out_mask + (long long)f * 5 * plane + p : nullptr;
+    if (o_mask && (s.img == nullptr || s.lab == nullptr)) {     // no view, or an image-only source in a batch with masks
 #pragma unroll
-            for (int c = 0; c < 5; ++c) m[(long long)c * oh * ow] = (c == ch) ? 1.f : 0.f;
+        for (int c = 0; c < 5; ++c) o_mask[(long long)c * plane] = 0.f;
+        o_mask = nullptr;
+    }
+    if (s.img == nullptr) {
+        *o_img = 0.f;
+        return;
+    }
+    const int t = s.t0 + (f - s.first);
+    const float sy = (float)s.H0 / (float)s.rs, sx = (float)s.W0 / (float)s.rs;
+    const int4 chan = make_int4(s.chan[0], s.chan[1], s.chan[2], s.chan[3]);
+    const float* lf = static_cast<const float*>(s.lab); const uint8_t* lb = static_cast<const uint8_t*>(s.lab);
+    if (s.img_u8) {
+        const uint8_t* im = static_cast<const uint8_t*>(s.img);
+        if (s.lab_u8) prepare_pixel(im, lb, o_img, o_mask, plane, y, x, t, s.H0, s.W0, s.T, sy, sx, s.oy, s.ox, chan, s.img_div);
+        else          prepare_pixel(im, lf, o_img, o_mask, plane, y, x, t, s.H0, s.W0, s.T, sy, sx, s.oy, s.ox, chan, s.img_div);
+    } else {
+        const float* im = static_cast<const float*>(s.img);
+        if (s.lab_u8) prepare_pixel(im, lb, o_img, o_mask, plane, y, x, t, s.H0, s.W0, s.T, sy, sx, s.oy, s.ox, chan, s.img_div);
+        else          prepare_pixel(im, lf, o_img, o_mask, plane, y, x, t, s.H0, s.W0, s.T, sy, sx, s.oy, s.ox, chan, s.img_div);
+    }
+}
+
+// ---- glf_frame_label_sums: column sums of the [H0 * W0][T] matrix a label volume is ---------------------------------------
+// A block pass covers kSumRows(T) whole pixels x one tile of up to 256 frames: thread k reads frame c0 + k % tw of pixel
+// r + k / tw, so with T <= 256 a pass is ONE contiguous run of rows * T elements, and beyond that 256 consecutive frames of a
+// pixel.  The frame of a thread never changes, so it sums in a register (exact: int64 of (int)value, the conversion the mask
+// kernel makes); the block folds its rows in LDS and adds ONE value per frame to the output.
+template <typename TL>
+__global__ __launch_bounds__(256) void frame_label_sums_kernel(const TL* __restrict__ lab, unsigned long long* __restrict__ sums,
+                                                               long long pixels, int T, int tw, int rows) {
+    __shared__ long long part[256];
+    const int k = threadIdx.x, r_off = k / tw, c = blockIdx.y * tw + (k - r_off * tw);
+    const bool active = r_off < rows && c < T;
+    long long acc = 0;
+    if (active) {
+        const long long step = (long long)gridDim.x * rows;
+        long long r = (long long)blockIdx.x * rows + r_off;
+        for (; r + 3 * step < pixels; r += 4 * step) {          // four independent loads in flight
+            const TL a = lab[r * T + c], b = lab[(r + step) * T + c], d = lab[(r + 2 * step) * T + c], e = lab[(r + 3 * step) * T + c];
+            acc += (long long)(int)a + (long long)(int)b + (long long)(int)d + (long long)(int)e;
         }
+        for (; r < pixels; r += step) acc += (long long)(int)lab[r * T + c];
+    }
+    part[k] = active ? acc : 0;
+    __syncthreads();
+    if (r_off == 0 && c < T) {
+        long long total = 0;
+        for (int j = 0; j < rows; ++j) total += part[j * tw + k];
+        atomicAdd(sums + c, (unsigned long long)total);
     }
 }
 
@@ -238,4 +336,83 @@ extern "C" int glf_restore_labels(const float* logits, uint8_t* volume, int T, i
     hipLaunchKernelGGL(restore_labels_kernel, dim3((unsigned)blocks), dim3(256), 0, glf::S(s), logits, volume, T, c, out_h, out_w, H0, W0,
                        resize, off_y, off_x, tab, tiles, xtiles, ttiles);
     return glf::check_launch("restore_labels");
+}
+
+extern "C" int glf_frame_label_sums(const void* lab, int dtype, int H0, int W0, int T, int64_t* sums, glf_stream_t s) {
+    GLF_REQUIRE(lab != nullptr && sums != nullptr, GLF_ERR_NULL, "frame_label_sums: null argument");
+    GLF_REQUIRE(H0 > 0 && W0 > 0 && T > 0, GLF_ERR_BAD_SHAPE, "frame_label_sums: H0, W0, T must be > 0 (got %d, %d, %d)", H0, W0, T);
+    GLF_REQUIRE(dtype == GLF_SRC_F32 || dtype == GLF_SRC_U8, GLF_ERR_UNSUPPORTED, "frame_label_sums: dtype %d (0 = float32, 1 = uint8)", dtype);
+    const int tw = T < 256 ? T : 256, rows = 256 / tw, ttiles = (T + tw - 1) / tw;
+    GLF_REQUIRE(ttiles <= 65535, GLF_ERR_BAD_SHAPE, "frame_label_sums: T = %d frames, at most %d", T, 65535 * 256);
+    if (int rc = glf::ensure_init()) return rc;
+    hipError_t e = hipMemsetAsync(sums, 0, (size_t)T * sizeof(int64_t), glf::S(s));
+    if (e != hipSuccess) return glf::fail(GLF_ERR_LAUNCH, "frame_label_sums: memset: %s", hipGetErrorString(e));
+    const long long pixels = (long long)H0 * W0, passes = (pixels + rows - 1) / rows;
+    long long bx = (passes + 7) / 8;                 // 8 passes or more per block: one atomic per frame pays for >= 2 048 loads
+    const long long cap = 2048 / ttiles > 0 ? 2048 / ttiles : 1;
+    if (bx > cap) bx = cap;
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(sums);
+    if (dtype == GLF_SRC_U8)
+        hipLaunchKernelGGL(frame_label_sums_kernel<uint8_t>, dim3((unsigned)bx, ttiles), dim3(256), 0, glf::S(s),
+                           static_cast<const uint8_t*>(lab), out, pixels, T, tw, rows);
+    else
+        hipLaunchKernelGGL(frame_label_sums_kernel<float>, dim3((unsigned)bx, ttiles), dim3(256), 0, glf::S(s),
+                           static_cast<const float*>(lab), out, pixels, T, tw, rows);
+    return glf::check_launch("frame_label_sums");
+}
+
+extern "C" int glf_prepare_batch(const glf_frame_src* srcs, int n, float* out_img, float* out_mask, int out_h, int out_w, glf_stream_t s) {
+    GLF_REQUIRE(srcs != nullptr, GLF_ERR_NULL, "prepare_batch: null source descriptors");
+    GLF_REQUIRE(out_img != nullptr, GLF_ERR_NULL, "prepare_batch: null out_img");
+    GLF_REQUIRE(n > 0, GLF_ERR_BAD_SHAPE, "prepare_batch: n = %d sources, must be > 0", n);
+    GLF_REQUIRE(out_h > 0 && out_w > 0 && (long long)out_h * out_w < (1ll << 30), GLF_ERR_BAD_SHAPE, "prepare_batch: bad output extents %d x %d",
+                out_h, out_w);
+    long long frames = 0;
+    for (int i = 0; i < n; ++i) {
+        const glf_frame_src& d = srcs[i];
+        GLF_REQUIRE(d.nt > 0, GLF_ERR_BAD_SHAPE, "prepare_batch: source %d: nt = %d frames, must be > 0", i, d.nt);
+        frames += d.nt;
+        if (d.img == nullptr) continue;                      // zeros: nothing else of the descriptor is read
+        GLF_REQUIRE(d.img_dtype == GLF_SRC_F32 || d.img_dtype == GLF_SRC_U8, GLF_ERR_UNSUPPORTED,
+                    "prepare_batch: source %d: image dtype %d (0 = float32, 1 = uint8)", i, d.img_dtype);
+        GLF_REQUIRE(d.H0 > 0 && d.W0 > 0 && d.T > 0 && d.resize > 0, GLF_ERR_BAD_SHAPE, "prepare_batch: source %d: sizes must be > 0", i);
+        GLF_REQUIRE(d.t0 >= 0 && (long long)d.t0 + d.nt <= d.T, GLF_ERR_BAD_SHAPE, "prepare_batch: source %d: frames [%d, %d + %d) leave the %d of the volume",
+                    i, d.t0, d.t0, d.nt, d.T);
+        GLF_REQUIRE(d.img_div != 0.f, GLF_ERR_BAD_SHAPE, "prepare_batch: source %d: img_div must not be 0", i);
+        GLF_REQUIRE(d.off_y >= 0 && d.off_x >= 0 && d.off_y <= d.resize - out_h && d.off_x <= d.resize - out_w, GLF_ERR_BAD_SHAPE,
+                    "prepare_batch: source %d: crop window [%d+%d, %d+%d] leaves the %d x %d resized image", i, d.off_y, out_h, d.off_x, out_w,
+                    d.resize, d.resize);
+        if (d.lab != nullptr) {
+            GLF_REQUIRE(d.lab_dtype == GLF_SRC_F32 || d.lab_dtype == GLF_SRC_U8, GLF_ERR_UNSUPPORTED,
+                        "prepare_batch: source %d: label dtype %d (0 = float32, 1 = uint8)", i, d.lab_dtype);
+            for (int k = 0; k < 4; ++k)
+                GLF_REQUIRE(d.class_to_channel[k] >= -1 && d.class_to_channel[k] < 5, GLF_ERR_BAD_SHAPE,
+                            "prepare_batch: source %d: channel index out of range", i);
+        }
+    }
+    const int plane = out_h * out_w, bpf = (plane + 255) / 256;
+    GLF_REQUIRE(frames * bpf <= 0x7fffffffll, GLF_ERR_BAD_SHAPE, "prepare_batch: %lld output frames are more than one call takes", frames);
+    if (int rc = glf::ensure_init()) return rc;
+    // the descriptors travel as kernel arguments, kBatchChunk per launch: no device table, no copy, nothing to wait for
+    long long done = 0;                                      // output frames of the chunks already launched
+    for (int i0 = 0; i0 < n; i0 += kBatchChunk) {
+        const int m = n - i0 < kBatchChunk ? n - i0 : kBatchChunk;
+        BatchChunk chunk = {};
+        int first = 0;
+        for (int k = 0; k < m; ++k) {
+            const glf_frame_src& d = srcs[i0 + k];
+            BatchSrc& b = chunk.src[k];
+            b.img = d.img; b.lab = d.img ? d.lab : nullptr;
+            b.H0 = d.H0; b.W0 = d.W0; b.T = d.T; b.t0 = d.t0; b.rs = d.resize; b.oy = d.off_y; b.ox = d.off_x; b.img_div = d.img_div;
+            b.first = first;
+            for (int c = 0; c < 4; ++c) b.chan[c] = (int8_t)(b.lab ? d.class_to_channel[c] : -1);
+            b.img_u8 = d.img_dtype == GLF_SRC_U8; b.lab_u8 = d.lab_dtype == GLF_SRC_U8;
+            first += d.nt;
+        }
+        hipLaunchKernelGGL(prepare_batch_kernel, dim3((unsigned)((long long)first * bpf)), dim3(256), 0, glf::S(s), chunk, m,
+                           out_img + done * plane, out_mask ? out_mask + done * 5 * plane : nullptr, out_h, out_w, bpf);
+        if (int rc = glf::check_launch("prepare_batch")) return rc;
+        done += first;
+    }
+    return GLF_OK;
 }

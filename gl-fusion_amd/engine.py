@@ -1,10 +1,12 @@
 """Caller-side harness with the reference Trainer's surface (main.py:63-883) for the hot path:
 `Trainer(config)`, `.train(is_backbone, is_cycle)`, `.eval(net_path, is_fuse, raw_data)`,
-`.test_visualize(method_name, net_path)`, `_calculate_overlap_metrics`, `save()`, `load()`.  The reference's data layer needs NIfTI files that are not
-shipped (absolute paths on the authors' machine), so loaders here produce synthetic clips with
-the reference's tensor contract: images [N,1,112,112] in [0,1], masks [N,5,112,112] in {0,1}
-(datasets/loader.py:298-330); the unlabelled "video" loader of the cycle term yields clips of `clip_length`
-frames per view (main.py:213-218).  `is_cycle=True` adds the temporal cycle-consistency loss of main.py:213-237
+`.test_visualize(method_name, net_path)`, `_calculate_overlap_metrics`, `save()`, `load()`.  With config['train']['infos'] / ['video_infos'] the Trainer trains from
+patient volumes: data.BatchLoader over per-view SegPAHDatasets for the supervised batches (main.py:116-117, 139) and
+data.ClipLoader over AlignedVideoSegPAHDatasets for the cycle term's clips (main.py:119-122, 143-145), the volumes resident
+on the device (data.VolumeStore).  The reference's NIfTI files are not shipped (absolute paths on the authors' machine, SURVEY
+section 0), so without those keys the loaders produce synthetic clips with the same tensor contract: images [N,1,112,112]
+in [0,1], masks [N,5,112,112] in {0,1} (datasets/loader.py:298-330); the unlabelled "video" loader of the cycle term yields
+clips of `clip_length` frames per view (main.py:213-218).  `is_cycle=True` adds the temporal cycle-consistency loss of main.py:213-237
 (second forward on the video clip, pooled global-fusion features, seg_cycle / dense_seg_cycle, total = seg + 1e-2 cyc).
 """
 from __future__ import annotations
@@ -213,14 +215,40 @@ class Trainer:
         self.reducer = GradAllReducer(self.model)
         self.reducer.broadcast_parameters(0)
         frames = tr["batch_size"] * tr.get("frames_per_clip", 1)
-        self.loader = SyntheticClips(self.view_num, frames, 112, 112, self.device, seed=1234 + tr.get("global_rank", 0),
-                                     length=tr.get("iters_per_epoch", 4))
         self.dense_cyc = bool(tr.get("dense_cyc", False))                      # main.py:228
         # config['train']['graph']: replay the (cycle-free) training step from one hipGraph instead of issuing ~3 400 launches
         self.use_graph = bool(tr.get("graph", False))
         self._graph = None
-        self.video_loader = SyntheticClips(self.view_num, int(tr.get("clip_length", 40)), 112, 112, self.device,
-                                           seed=4321 + tr.get("global_rank", 0), length=tr.get("iters_per_epoch", 4))
+        # config['train']['infos'] / ['video_infos'] (dicts, or paths to the reference's .npy, main.py:283): train from patient
+        # volumes -- the supervised batches of main.py:116-117, 139 and the cycle term's clips of main.py:119-122, 143-145, over
+        # config['train']['train_list'] (the reference's data_list/train_list.npy; absent = the datasets' own split) and
+        # config['train']['use_data'] (set_select), the volumes resident on the device within config['train']['store_bytes'].
+        # Absent: that loader is synthetic, as before.
+        self.loader = self.video_loader = None
+        if tr.get("infos") is not None or tr.get("video_infos") is not None:
+            from . import data as _data
+            import torch.distributed as dist
+            rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
+            self.store = _data.VolumeStore(self.device, int(tr.get("store_bytes", 8 << 30)))
+            common = dict(is_train=True, data_list=tr.get("train_list"), set_select=tuple(tr.get("use_data", ("rmyy",))))
+            if tr.get("infos") is not None:
+                infos = _data.load_infos(tr["infos"])
+                self.loader = _data.BatchLoader({v: _data.SegPAHDataset(infos, view_num=[v], single_frame=True, device=self.device,
+                                                                        seg_parts=bool(tr.get("seg_parts", True)), **common)
+                                                 for v in self.view_num}, tr["batch_size"], self.store, rank, world)
+            if tr.get("video_infos") is not None:
+                # main.py:136 and 191 iterate `train_cyc_dataset`, a dict the reference never fills; the clips it means are
+                # train_pseudo_dataset's (main.py:119-122): Aligned_Video_Seg_PAHDataset over the whole-video infos
+                infos = _data.load_infos(tr["video_infos"])
+                self.video_loader = _data.ClipLoader({v: _data.AlignedVideoSegPAHDataset(infos, view_num=[v], random_sample=False,
+                                                                                         clip_length=int(tr.get("clip_length", 40)), **common)
+                                                      for v in self.view_num}, self.store, rank, world)
+        if self.loader is None:
+            self.loader = SyntheticClips(self.view_num, frames, 112, 112, self.device, seed=1234 + tr.get("global_rank", 0),
+                                         length=tr.get("iters_per_epoch", 4))
+        if self.video_loader is None:
+            self.video_loader = SyntheticClips(self.view_num, int(tr.get("clip_length", 40)), 112, 112, self.device,
+                                               seed=4321 + tr.get("global_rank", 0), length=tr.get("iters_per_epoch", 4))
 
     def cycle_loss(self, video: Dict[str, torch.Tensor]) -> torch.Tensor:
         """main.py:213-235: second forward on an unlabelled clip [T,1,H,W] per view, global-fusion features summed
@@ -304,6 +332,10 @@ class Trainer:
     def train(self, is_backbone: bool = False, is_cycle: bool = True):
         if is_cycle:
             self._require_fusion_features("Trainer.train(is_cycle=True)")
+            if not isinstance(self.loader, SyntheticClips) and isinstance(self.video_loader, SyntheticClips):
+                raise ValueError("glfusion_amd: Trainer.train(is_cycle=True) with config['train']['infos'] needs config['train']['video_infos'] "
+                                 "too: the cycle term would otherwise run on synthetic noise clips beside real batches (is_cycle=False trains without it)")
+        # both kinds of loader serve one interface: iteration yields (imgs, masks) batches, batch()[0] is the next clip per view
         for epoch in range(self.latest_epoch, self.config["train"]["num_epochs"]):
             self.model.train()
             for imgs, masks in self.loader:

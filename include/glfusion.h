@@ -1014,6 +1014,39 @@ int glf_render_labels(const float* logits, const float* frames, uint8_t* labels,
                       const uint8_t* palette, int alpha, glf_stream_t s);
 int glf_restore_labels(const float* logits, uint8_t* volume, int T, int c, int out_h, int out_w, int H0, int W0, int resize,
                        int off_y, int off_x, const int* channel_to_class, glf_stream_t s);
+/* ---------------------------------------------------------------------------------------
+ * Training data path: label-frame sums of a resident volume, and one batch of frames from many volumes in one call.
+ * Volumes are [H0][W0][T] (T fastest) stored as float32 (GLF_SRC_F32) or uint8 (GLF_SRC_U8); a byte converts exactly, so
+ * both storages give the same output bits.
+ * glf_frame_label_sums: sums[t] = sum over (y, x) of (int)lab[y][x][t], T int64 on the device: the quantity input_select
+ * compares with 100 (loader.py:429-458, masks.sum(dim=(0, 1))), exact for class-id volumes.  Any T >= 1.  The call writes
+ * all of sums (no pre-zeroing by the caller).  Reads run along the volume's memory order; a block sums its share of each
+ * frame in registers and LDS and adds one value per frame.  GLF_ERR_NULL, GLF_ERR_BAD_SHAPE (H0, W0, T < 1),
+ * GLF_ERR_UNSUPPORTED (dtype), all before any HIP runtime call.
+ * glf_prepare_batch: srcs = n HOST descriptors; descriptor i yields nt consecutive output frames, frames t0 .. t0 + nt - 1 of
+ * its volume, by exactly glf_prepare_frames' arithmetic (fp32 nearest scale, true division by img_div, (int)lab -> channel):
+ * out_img [sum nt][1][out_h][out_w], out_mask [sum nt][5][out_h][out_w] (NULL for image-only batches).  img == NULL: the
+ * source's frames are zeros in both outputs (a patient without this view, loader.py:267-282) and only nt is read; lab == NULL:
+ * its mask frames are zeros.  resize == H0 == W0 == out_h == out_w, offsets 0, img_div 1 is the identity (raw video clips).
+ * The descriptors reach the device as kernel arguments, 32 per launch: no allocation, copy or synchronisation per call.
+ * Checked before any HIP runtime call: GLF_ERR_NULL (srcs, out_img), then per source GLF_ERR_BAD_SHAPE (n < 1, nt < 1,
+ * sizes < 1, t0 < 0, t0 + nt > T, img_div 0, a crop window that leaves the resized image, a label pointer with a
+ * class_to_channel entry outside [-1, 4]) and GLF_ERR_UNSUPPORTED (a dtype that is neither GLF_SRC_F32 nor GLF_SRC_U8).
+ * ------------------------------------------------------------------------------------- */
+enum { GLF_SRC_F32 = 0, GLF_SRC_U8 = 1 };
+typedef struct {
+    const void* img;              /* device volume, or NULL: zeros */
+    const void* lab;              /* device volume of class ids, or NULL: no masks from this source */
+    int32_t img_dtype, lab_dtype; /* GLF_SRC_F32 / GLF_SRC_U8 */
+    int32_t H0, W0, T;
+    int32_t t0, nt;               /* first frame and frame count */
+    int32_t resize, off_y, off_x;
+    int32_t class_to_channel[4];  /* channel of class 1..4, -1 = dropped (read only with lab) */
+    float img_div;
+    int32_t reserved;
+} glf_frame_src;
+int glf_frame_label_sums(const void* lab, int dtype, int H0, int W0, int T, int64_t* sums, glf_stream_t s);
+int glf_prepare_batch(const glf_frame_src* srcs, int n, float* out_img, float* out_mask, int out_h, int out_w, glf_stream_t s);
 /* Zero `bytes` bytes at p on the stream (accumulation targets: atomically summed gradients, column statistics, maxima). */
 int glf_zero(void* p, int64_t bytes, glf_stream_t s);
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Entry point with the reference's surface (GLfusion/main.py:885-965): the same `config` dict keys, `--mode
-{train,val,visual}`, `main(rank, config)`, `Trainer(config)` -- running the MI355X HIP engine on synthetic clips (the
-reference's data files are not shipped).  Multi-GPU: `python -m torch.distributed.run --nproc-per-node N main.py
+{train,val,visual}`, `main(rank, config)`, `Trainer(config)` -- running the MI355X HIP engine on patient volumes (`--infos`, `--video-infos`,
+`--train-list`: the reference's infos dicts and id list) or, without them, on synthetic clips (the reference's data files are not
+shipped).  Multi-GPU: `python -m torch.distributed.run --nproc-per-node N main.py
 --mode train` (one process per GPU, RCCL gradient all-reduce) instead of the reference's nn.DataParallel."""
 from __future__ import annotations
 
@@ -39,7 +40,23 @@ def main(rank, config):
                         help="the network (config['net']['model']); default: the config's, else Global_and_Local.  The U-Net "
                              "baselines (ours.py:2416-2625) and the fusion baselines early_fusion / late_fusion / MLP_fusion "
                              "(ours.py:2251-2383, 1044-1107) return no fusion features and train without the cycle loss")
+    parser.add_argument("--infos", type=str, default=None, metavar="NPY",
+                        help="train from patient volumes: the reference's pickled infos dict of the labelled frames "
+                             "(config['train']['infos']); default: synthetic batches")
+    parser.add_argument("--video-infos", type=str, default=None, metavar="NPY",
+                        help="the infos dict of the whole videos, the cycle term's clips (config['train']['video_infos']); "
+                             "needed beside --infos unless the model trains without the cycle loss")
+    parser.add_argument("--train-list", type=str, default=None, metavar="NPY",
+                        help="array of the patient ids to train on, the reference's data_list/train_list.npy "
+                             "(config['train']['train_list']); default: the datasets' own 80 %% split")
     args = parser.parse_args()
+    if args.infos:
+        config["train"]["infos"] = args.infos
+    if args.video_infos:
+        config["train"]["video_infos"] = args.video_infos
+    if args.train_list:
+        import numpy as np
+        config["train"]["train_list"] = np.load(args.train_list, allow_pickle=True).tolist()
     if args.model:
         config["net"]["model"] = args.model
     if args.opt:
