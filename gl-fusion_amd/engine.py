@@ -8,6 +8,9 @@ section 0), so without those keys the loaders produce synthetic clips with the s
 in [0,1], masks [N,5,112,112] in {0,1} (datasets/loader.py:298-330); the unlabelled "video" loader of the cycle term yields
 clips of `clip_length` frames per view (main.py:213-218).  `is_cycle=True` adds the temporal cycle-consistency loss of main.py:213-237
 (second forward on the video clip, pooled global-fusion features, seg_cycle / dense_seg_cycle, total = seg + 1e-2 cyc).
+config['net']['model'] names any of MODELS -- Global_and_Local, its nine variants of models/ours.py and the five baselines; OUTPUTS says
+where each model's output tuple carries what the Trainer uses.  config['train']['cps_weight'] > 0 adds the cross pseudo supervision
+term of Global_and_Local_CPS on the same clip forward (ops.cps_bce_sum).
 """
 from __future__ import annotations
 
@@ -15,13 +18,15 @@ import functools
 import glob
 import os
 import warnings
+from collections import namedtuple
 from typing import Dict, Iterator, Tuple
 
 import torch
 
 from . import ops
-from .ddp import GradAllReducer, all_reduce_counts
+from .ddp import GradAllReducer, all_reduce_counts, default_ignore
 from .optim import SGD, Adam
+from . import models as _models
 from .models import Global_and_Local, MLP_fusion, baseline_unet, early_fusion, late_fusion, multiview_unet
 
 # config['net']['model'] -> class; the U-Net baselines return (mask, None, None, x5) and the fusion baselines (mask, f4, None, None):
@@ -29,6 +34,41 @@ from .models import Global_and_Local, MLP_fusion, baseline_unet, early_fusion, l
 MODELS = {"Global_and_Local": Global_and_Local, "baseline_unet": baseline_unet, "multiview_unet": multiview_unet,
           "early_fusion": early_fusion, "late_fusion": late_fusion, "MLP_fusion": MLP_fusion}
 NO_FUSION_FEATURES = ("baseline_unet", "multiview_unet", "early_fusion", "late_fusion", "MLP_fusion")
+# the ablation variants of models/ours.py
+VARIANTS = ("Global_and_Local_cyc_nofusion", "Foreground_and_Background", "Global_and_Local_Temporal", "Global_and_Local_conv_merge",
+            "Global_only", "Global_only_cyc_nofusion", "Local_only", "model19", "Global_and_Local_CPS")
+MODELS.update({name: getattr(_models, name) for name in VARIANTS})
+
+# Where each model's output tuple carries what the Trainer uses -- every method reads the tuple through this table:
+#   heads     outputs supervised by the BCE sum; the first is the one scored (epoch Dice, eval, validation, pictures)
+#   backbone  the output a scoring pass takes with is_fuse=False (None: the model has no second mask, the first head is scored)
+#   cycle     the output whose (h, w)-pooled features feed the cycle term (None: no fusion features, no cycle term)
+#   clip_is_video  the forward takes is_video: True for the unlabelled clip (one video), False for a labelled batch
+# Local_only: out[2] is the detached [N,1,h,w] gate map -- the reference's sum(dim=(2, 3)) of it is ONE feature without a gradient, a
+# cycle term that can move nothing -- so this ablation's cycle term acts on out[3], the local-fusion features.
+# Global_and_Local_CPS: two networks, both masks supervised; with is_fuse=False network 2's mask is scored; the cycle features are
+# network 1's.
+Outputs = namedtuple("Outputs", "heads backbone cycle clip_is_video")
+_MAIN = Outputs(heads=(0,), backbone=1, cycle=2, clip_is_video=False)
+OUTPUTS = {name: _MAIN for name in ("Global_and_Local", "Global_and_Local_cyc_nofusion", "Global_and_Local_conv_merge",
+                                    "Foreground_and_Background", "Global_only", "Global_only_cyc_nofusion", "model19")}
+OUTPUTS["Global_and_Local_Temporal"] = _MAIN._replace(clip_is_video=True)
+OUTPUTS["Local_only"] = _MAIN._replace(cycle=3)
+OUTPUTS["Global_and_Local_CPS"] = _MAIN._replace(heads=(0, 1))
+OUTPUTS.update({name: Outputs(heads=(0,), backbone=None, cycle=None, clip_is_video=False) for name in NO_FUSION_FEATURES})
+
+
+def _cps_ignore(name: str) -> bool:
+    if name.startswith("network."):
+        return not name.startswith("network.backbone.")
+    return default_ignore(name)
+
+
+def reducer_ignore(model_name: str):
+    """The `ignore` predicate GradAllReducer gets for a model: ddp.default_ignore, which drops the dead `network.*` template -- except for
+    Global_and_Local_CPS, whose network 2 runs ON the template's encoders (models/ours.py: the `_2` ModuleDicts alias
+    `network.backbone.*`, the name their parameters are listed under): those are reduced, `network.classifier.*` stays dead."""
+    return _cps_ignore if model_name == "Global_and_Local_CPS" else default_ignore
 
 
 class SyntheticClips:
@@ -189,6 +229,18 @@ class Trainer:
         self.model_name = config["net"].get("model", "Global_and_Local")
         if self.model_name not in MODELS:
             raise ValueError(f"glfusion_amd: config['net']['model'] = {self.model_name!r}; the Trainer builds one of {sorted(MODELS)}")
+        self.outputs = OUTPUTS[self.model_name]
+        # config['train']['cps_weight'] (absent = 0; no reference counterpart): weight of the cross pseudo supervision term of
+        # Global_and_Local_CPS -- on an unlabelled clip each network's hard prediction supervises the other (ops.cps_bce_sum)
+        self.cps_weight = float(tr.get("cps_weight", 0) or 0)
+        if self.cps_weight < 0 or self.cps_weight != self.cps_weight:
+            raise ValueError(f"glfusion_amd: config['train']['cps_weight'] = {self.cps_weight!r} must be >= 0")
+        if self.cps_weight > 0 and self.model_name != "Global_and_Local_CPS":
+            raise ValueError(f"glfusion_amd: config['train']['cps_weight'] = {self.cps_weight!r} needs the two networks of "
+                             f"Global_and_Local_CPS; {self.model_name} has one")
+        self.cps_report = {}                                                    # {view: agreement fraction of the two networks}, per epoch
+        self._cps_stats = None                                                  # {view: int64[4]} the last CPS step filled
+        self.clip_cycle = True                                                  # a train_step with a clip adds the cycle term (train() sets it)
         self.model = MODELS[self.model_name](view_num=self.view_num).to(self.device)
         opt = config["net"]["opt"]
         name = opt.get("opt_name", "Adam")
@@ -212,7 +264,7 @@ class Trainer:
         self.latest_epoch = 0                                                   # first epoch train() runs; load() moves it
         if tr.get("is_load", False):                                            # main.py:74, 153
             self.load()
-        self.reducer = GradAllReducer(self.model)
+        self.reducer = GradAllReducer(self.model, ignore=reducer_ignore(self.model_name))
         self.reducer.broadcast_parameters(0)
         frames = tr["batch_size"] * tr.get("frames_per_clip", 1)
         self.dense_cyc = bool(tr.get("dense_cyc", False))                      # main.py:228
@@ -255,16 +307,45 @@ class Trainer:
         over (h, w), seg_cycle (or dense_seg_cycle) per view with target_region 16, cyc_off 2, chunk_size 3,
         temperature 10."""
         self._require_fusion_features("cycle_loss")
-        _, _, feat_out, _ = self.model(video)
-        feats = ops.pooled_fusion_features(feat_out)
-        total = None
-        for view in self.view_num:
-            if self.dense_cyc:
-                l = ops.dense_seg_cycle(feats[view], 16, 2, 3, 10, soft_label=False, is_overlap=True)
-            else:
-                l = ops.seg_cycle(feats[view], 16, 2, 3, 10)
-            total = l if total is None else total + l
-        return total
+        return self._clip_terms(video, cycle=True, cps=False)[0]
+
+    def _forward(self, x, clip: bool = False):
+        """The model's forward on a labelled batch, or (clip) on an unlabelled clip -- one video, which Global_and_Local_Temporal
+        is told (OUTPUTS[...].clip_is_video)."""
+        return self.model(x, is_video=clip) if self.outputs.clip_is_video else self.model(x)
+
+    def _clip_terms(self, video: Dict[str, torch.Tensor], cycle: bool, cps: bool):
+        """ONE forward on the unlabelled clip for both terms that use it: (cycle loss, CPS loss), None for a term not asked for.
+        The cycle term takes the model's cycle features (OUTPUTS: out[2]; Local_only out[3], the local-fusion features, because its
+        out[2] is the detached gate map); the CPS term sum_{v in test_view} ops.cps_bce_sum of the two networks' masks, whose
+        agreement counts stay in self._cps_stats."""
+        out = self._forward(video, clip=True)
+        cyc = cross = None
+        if cycle:
+            feats = ops.pooled_fusion_features(out[self.outputs.cycle])
+            for view in self.view_num:
+                if self.dense_cyc:
+                    l = ops.dense_seg_cycle(feats[view], 16, 2, 3, 10, soft_label=False, is_overlap=True)
+                else:
+                    l = ops.seg_cycle(feats[view], 16, 2, 3, 10)
+                cyc = l if cyc is None else cyc + l
+        if cps:
+            if self._cps_stats is None:
+                self._cps_stats = {v: torch.empty(4, dtype=torch.int64, device=self.device) for v in self.test_view}
+            h1, h2 = self.outputs.heads
+            for view in self.test_view:
+                l = ops.cps_bce_sum(out[h1][view], out[h2][view], self._cps_stats[view])
+                cross = l if cross is None else cross + l
+        return cyc, cross
+
+    def _supervised_loss(self, out, masks):
+        """sum over the model's supervised heads and the views of test_view of the BCE sum (main.py:209-211; CPS: both networks)."""
+        loss = None
+        for head in self.outputs.heads:
+            for view in self.test_view:
+                l = ops.bce_with_logits_sum(out[head][view], masks[view])
+                loss = l if loss is None else loss + l
+        return loss
 
     def _graph_step(self, imgs, masks):
         """The segmentation step (no cycle term) replayed from ONE hipGraph (StepGraph): the batch is copied into static input
@@ -278,12 +359,9 @@ class Trainer:
             holder = {}
 
             def core():
-                pred, _, _, _ = self.model(s_imgs)
-                holder["pred"] = pred
-                loss = None
-                for view in self.test_view:
-                    l = ops.bce_with_logits_sum(pred[view], s_masks[view])
-                    loss = l if loss is None else loss + l
+                out = self._forward(s_imgs)
+                holder["pred"] = out[self.outputs.heads[0]]
+                loss = self._supervised_loss(out, s_masks)
                 loss.backward()
                 return loss.detach()
             for v in imgs:
@@ -300,46 +378,63 @@ class Trainer:
         return loss, self._graph_pred
 
     def train_step(self, imgs, masks, video=None) -> torch.Tensor:
-        """main.py:202-243: forward, sum_v BCE-sum (+ 1e-2 x cycle loss on `video`), backward, optimizer step."""
+        """main.py:202-243: forward, sum over heads and views of the BCE-sum, backward, optimizer step.  With an unlabelled clip
+        `video`, ONE forward on it adds cps_weight x the CPS term (config['train']['cps_weight'] > 0) and, unless self.clip_cycle
+        is False (train(is_cycle=False) draws its clip for the CPS term alone), 1e-2 x the cycle loss (main.py:237).  Returns (loss,
+        the first head's masks)."""
+        cycle = self.clip_cycle
         if video is None and self.use_graph:
             return self._graph_step(imgs, masks)
-        pred_frames, _, _, _ = self.model(imgs)
-        loss = None
-        for view in self.test_view:
-            l = ops.bce_with_logits_sum(pred_frames[view], masks[view])
-            loss = l if loss is None else loss + l
+        out = self._forward(imgs)
+        loss = self._supervised_loss(out, masks)
         if video is not None:
-            loss = loss + 1e-2 * self.cycle_loss(video)                        # main.py:237
+            if cycle:
+                self._require_fusion_features("train_step with a clip")
+            cyc, cross = self._clip_terms(video, cycle=cycle, cps=self.cps_weight > 0)
+            if cross is not None:
+                loss = loss + self.cps_weight * cross
+            if cyc is not None:
+                loss = loss + 1e-2 * cyc                                       # main.py:237
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.reducer.finalize()
         self.optimizer.step()
-        return loss.detach(), pred_frames
+        return loss.detach(), out[self.outputs.heads[0]]
 
     def _prediction(self, out, is_fuse: bool):
-        """The mask a scoring pass takes from the model's outputs: the fused one, or with is_fuse False the backbone mask out[1] --
-        where the model has one.  The U-Net baselines return None there, and the fusion baselines their layer-4 features (the
-        model says so: second_output_is_features): their one mask is scored whatever is_fuse says."""
-        if is_fuse or out[1] is None or getattr(self.model, "second_output_is_features", False):
-            return out[0]
-        return out[1]
+        """The mask a scoring pass takes from the model's outputs (OUTPUTS): the first head, or with is_fuse False the model's second
+        mask -- the backbone mask out[1]; for Global_and_Local_CPS network 2's -- where the model has one.  The U-Net baselines
+        return None there and the fusion baselines their layer-4 features: their one mask is scored whatever is_fuse says."""
+        if is_fuse or self.outputs.backbone is None:
+            return out[self.outputs.heads[0]]
+        return out[self.outputs.backbone]
 
     def _require_fusion_features(self, what: str) -> None:
-        if self.model_name in NO_FUSION_FEATURES:
+        if self.outputs.cycle is None:
             raise ValueError(f"glfusion_amd: {what} needs the model's fusion features (its third output), and {self.model_name} "
                              "returns none: train it with is_cycle=False")
 
     def train(self, is_backbone: bool = False, is_cycle: bool = True):
         if is_cycle:
             self._require_fusion_features("Trainer.train(is_cycle=True)")
-            if not isinstance(self.loader, SyntheticClips) and isinstance(self.video_loader, SyntheticClips):
-                raise ValueError("glfusion_amd: Trainer.train(is_cycle=True) with config['train']['infos'] needs config['train']['video_infos'] "
-                                 "too: the cycle term would otherwise run on synthetic noise clips beside real batches (is_cycle=False trains without it)")
+        use_clip = is_cycle or self.cps_weight > 0              # the CPS term draws a clip too, with or without the cycle term
+        if use_clip and not isinstance(self.loader, SyntheticClips) and isinstance(self.video_loader, SyntheticClips):
+            what, without = (("Trainer.train(is_cycle=True)", "is_cycle=False") if is_cycle else
+                             ("config['train']['cps_weight'] > 0", "cps_weight 0"))
+            raise ValueError(f"glfusion_amd: {what} with config['train']['infos'] needs config['train']['video_infos'] "
+                             f"too: the clip terms would otherwise run on synthetic noise clips beside real batches ({without} trains without them)")
+        self.clip_cycle = bool(is_cycle)
+        try:
+            self._train_epochs(use_clip)
+        finally:
+            self.clip_cycle = True
+
+    def _train_epochs(self, use_clip: bool):
         # both kinds of loader serve one interface: iteration yields (imgs, masks) batches, batch()[0] is the next clip per view
         for epoch in range(self.latest_epoch, self.config["train"]["num_epochs"]):
             self.model.train()
             for imgs, masks in self.loader:
-                video = self.video_loader.batch()[0] if is_cycle else None
+                video = self.video_loader.batch()[0] if use_clip else None
                 loss, pred = self.train_step(imgs, masks, video)
             self.scheduler.step()
             # the epoch's Dice sums its counters over ranks: a collective, so EVERY rank computes it (only rank 0 prints)
@@ -348,6 +443,11 @@ class Trainer:
                 clip = ""
                 if self.clip_grad_norm is not None:      # the epoch's one read of the device values, beside float(loss)
                     clip = f" grad-norm {float(self.optimizer.grad_norm):.4g} skipped-steps {int(self.optimizer.skipped_steps)}"
+                if self.cps_weight > 0 and self._cps_stats is not None:
+                    # the last step's agreement counts of the two networks, (n11 + n00) / numel per view: one host read per epoch
+                    rows = torch.stack([self._cps_stats[v] for v in self.test_view]).tolist()
+                    self.cps_report = {v: (r[0] + r[3]) / max(sum(r), 1) for v, r in zip(self.test_view, rows)}
+                    clip += " cps-agreement " + " ".join(f"{v}:{a:.4f}" for v, a in self.cps_report.items())
                 print(f"epoch {epoch}: loss {float(loss):.2f}{clip} dice {dice}")
                 if self.config["train"].get("validate_every_epoch", True):
                     # main.py:259-274: validation runs on the printing rank alone, over every clip of the splits, with NO collective
@@ -384,7 +484,7 @@ class Trainer:
             imgs, masks = {}, {}
             for v in self.view_num:
                 imgs[v], masks[v] = _data.prepare_frames(sample[v][0], sample[v][1], v, train=False)
-            out = self.model(imgs)
+            out = self._forward(imgs)
             pred = self._prediction(out, is_fuse)
             for v in self.test_view:
                 counts[v] += part_overlap_counts(pred[v], masks[v])
@@ -441,7 +541,7 @@ class Trainer:
             imgs, masks = {}, {}
             for v in self.view_num:
                 imgs[v], masks[v] = _data.prepare_frames(sample[v][0], sample[v][1], v, train=False)
-            out = self.model(imgs)
+            out = self._forward(imgs)
             pred = self._prediction(out, is_fuse)
             manifest[pid] = {}
             for v in self.test_view:
@@ -502,7 +602,7 @@ class Trainer:
                     frames = min(t.shape[0] for t in imgs.values())
                     imgs = {v: t[:frames] for v, t in imgs.items()}
                     masks = {v: t[:frames] for v, t in masks.items()}
-                    out = self.model(imgs)
+                    out = self._forward(imgs)
                     pred = self._prediction(out, is_fuse)
                     for v in self.test_view:
                         counts[v] += part_overlap_counts(pred[v], masks[v])

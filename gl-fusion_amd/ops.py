@@ -2909,6 +2909,41 @@ def bce_with_logits_sum(logits, target):
     return BceSumFn.apply(logits, target)
 
 
+class CpsBceFn(Function):
+    """Cross pseudo supervision (glf_cps_bce_sum): sum BCE(a, on(b)) + sum BCE(b, on(a)) with on(x) = sigmoid(x) > 0.5, the
+    prediction overlap_counts scores.  The labels are constants: no gradient passes through the threshold."""
+
+    @staticmethod
+    def forward(ctx, a, b, stats):
+        a, b = _contig(_chk(a, "cps logits a")), _contig(_chk(b, "cps logits b"))
+        if a.shape != b.shape:
+            raise RuntimeError("cps_bce_sum: the two logit maps differ in shape")
+        if stats is not None and not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.int64
+                                      and stats.numel() == 4 and stats.is_contiguous()):
+            raise RuntimeError("cps_bce_sum: stats must be a contiguous CUDA(HIP) int64 tensor of 4 elements")
+        loss = torch.empty(1, dtype=torch.float64, device=a.device)
+        check(lib.glf_cps_bce_sum(_p(a), _p(b), _p(loss), _p(stats), None, None, 1.0, None, a.numel(), _stream()), "cps_bce_sum")
+        ctx.save_for_backward(a, b)
+        return loss[0].float()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dl):
+        a, b = ctx.saved_tensors
+        da, db = torch.empty_like(a), torch.empty_like(b)
+        scratch = torch.empty(1, dtype=torch.float64, device=a.device)
+        dl = _contig(dl.float())
+        # both gradients in one launch, the upstream scalar read on the device (no host sync)
+        check(lib.glf_cps_bce_sum(_p(a), _p(b), _p(scratch), None, _p(da), _p(db), 1.0, _p(dl), a.numel(), _stream()), "cps_bce_bwd")
+        return (da if ctx.needs_input_grad[0] else None), (db if ctx.needs_input_grad[1] else None), None
+
+
+def cps_bce_sum(a, b, stats: Optional[torch.Tensor] = None):
+    """fp32 scalar sum_i bce(a_i, on(b_i)) + bce(b_i, on(a_i)) of two fp32 logit maps of one shape (predictions are fp32 under every
+    precision).  `stats`: an int64[4] device tensor the forward fills with the counts of (on(a), on(b)) = 11, 10, 01, 00."""
+    return CpsBceFn.apply(a, b, stats)
+
+
 def overlap_counts(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """int64 [tp, fp, fn, tn] of pred = sigmoid(logits) > 0.5 against target (main.py:800-815)."""
     logits, target = _contig(_chk(logits, "logits")), _contig(_chk(target, "target"))

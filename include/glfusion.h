@@ -899,6 +899,15 @@ int glf_bce_logits_sum(const float* x, const float* t, double* loss_out, float* 
 /* Trainer._calculate_overlap_metrics (main.py:800-815) on pred = sigmoid(x) > 0.5:
  * counts[4] = {tp, fp, fn, tn} as int64 (zeroed by the call). */
 int glf_overlap_counts(const float* logits, const float* target, int64_t* counts, int64_t numel, glf_stream_t s);
+/* Cross pseudo supervision between two logit maps (the loss of Global_and_Local_CPS, no reference counterpart): with
+ * on(x) = sigmoid(x) > 0.5 by the predicate glf_overlap_counts counts with,
+ * loss_out[0] = sum_i bce(a_i, on(b_i)) + sum_i bce(b_i, on(a_i)) (double[1], zeroed by the call; bce as glf_bce_logits_sum).
+ * stats (may be NULL): int64[4], zeroed by the call, counts of (on(a), on(b)) = {11, 10, 01, 00} -- what
+ * glf_overlap_counts(a, on(b)) returns.  da and db: both NULL (forward) or both given; da = (sigmoid(a) - on(b)) * g,
+ * db = (sigmoid(b) - on(a)) * g with g = grad_scale * (*grad_scale_dev), the latter a device scalar that may be NULL (the labels
+ * are constants).  One launch; every input element is read once.  da / db must not alias a, b or each other. */
+int glf_cps_bce_sum(const float* a, const float* b, double* loss_out, int64_t* stats, float* da, float* db, float grad_scale,
+                    const float* grad_scale_dev, int64_t numel, glf_stream_t s);
 /* bias gradient: db[c] = sum_r dy[r][c]; workspace glf_bn_workspace(rows, c) doubles. */
 int glf_colsum(const float* dy, int lddy, float* db, int rows, int c, double* workspace, glf_stream_t s);
 

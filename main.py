@@ -36,10 +36,17 @@ def main(rank, config):
     parser.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
                         help="clip every step by the global gradient norm X and skip steps with a non-finite one, on the device "
                              "(config['train']['clip_grad_norm']; inf = the guard alone); default: off")
-    parser.add_argument("--model", type=str, default=None, choices=("Global_and_Local", "baseline_unet", "multiview_unet", "early_fusion", "late_fusion", "MLP_fusion"),
-                        help="the network (config['net']['model']); default: the config's, else Global_and_Local.  The U-Net "
+    parser.add_argument("--model", type=str, default=None,
+                        choices=("Global_and_Local", "Global_and_Local_cyc_nofusion", "Foreground_and_Background", "Global_and_Local_Temporal",
+                                 "Global_and_Local_conv_merge", "Global_only", "Global_only_cyc_nofusion", "Local_only", "model19",
+                                 "Global_and_Local_CPS", "baseline_unet", "multiview_unet", "early_fusion", "late_fusion", "MLP_fusion"),
+                        help="the network (config['net']['model']); default: the config's, else Global_and_Local.  The nine ablation "
+                             "variants of ours.py train like it (Global_and_Local_CPS supervises both of its networks).  The U-Net "
                              "baselines (ours.py:2416-2625) and the fusion baselines early_fusion / late_fusion / MLP_fusion "
                              "(ours.py:2251-2383, 1044-1107) return no fusion features and train without the cycle loss")
+    parser.add_argument("--cps-weight", type=float, default=None, metavar="X",
+                        help="weight of the cross pseudo supervision term of --model Global_and_Local_CPS: on the unlabelled clip each "
+                             "network's hard prediction supervises the other (config['train']['cps_weight']); default: 0, off")
     parser.add_argument("--infos", type=str, default=None, metavar="NPY",
                         help="train from patient volumes: the reference's pickled infos dict of the labelled frames "
                              "(config['train']['infos']); default: synthetic batches")
@@ -63,6 +70,8 @@ def main(rank, config):
         config["net"]["opt"]["opt_name"] = args.opt
     if args.clip_grad_norm is not None:
         config["train"]["clip_grad_norm"] = args.clip_grad_norm
+    if args.cps_weight is not None:
+        config["train"]["cps_weight"] = args.cps_weight
     if args.resume:
         config["train"]["is_load"] = config["train"]["save_optimizer"] = True
     if args.precision:
