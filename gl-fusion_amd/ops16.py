@@ -23,7 +23,8 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from ._lib import GemmParams, S16GemmEpilogue, WJ_CVT_BF16, check, lib
-from . import ops as _o
+from . import conv_plan, ops as _o
+from .conv_plan import S16, tn_split16          # (fusion16 takes its slice counts from here)
 
 BF, DT_F32, DT_BF16 = _o.BF, _o.DT_F32, _o.DT_BF16
 _p, _stream, _contig = _o._p, _o._stream, _o._contig
@@ -100,22 +101,6 @@ def gemm16(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: 
                      (M, N, K, taps, kept, batch, split, geo[8] if geo else 0, geo[9] if geo else 0), abytes))
 
 
-def tn_split16(rows: int, m: int, n: int, ntaps: int, batch: int = 1) -> int:
-    """Reduction slices of glf_s16_gemm_tn: 256 x 128 tiles, one workgroup per CU.  Aim for ~2 rounds of the 256 CUs and, among the
-    slice counts around that, take the one whose workgroups fill whole rounds best (576 workgroups = 2.25 rounds run as long as
-    768 = 3); keep at least 512 rows per slice (every slice costs an [M][N] fp32 slab written and read back)."""
-    tiles = ((m + 255) // 256) * ((n + 127) // 128) * max(ntaps, 1) * batch
-    want = max(1, (512 + tiles - 1) // tiles)
-    cap = max(1, min(rows // 512, 65535 // max(batch, 1)))
-    best, best_score = min(want, cap), -1.0
-    for sp in range(max(1, want // 2), max(1, min(2 * want, cap)) + 1):
-        b = tiles * sp
-        score = b / (((b + 255) // 256) * 256.0) - 0.01 * sp
-        if score > best_score:
-            best, best_score = sp, score
-    return int(max(1, min(best, cap)))
-
-
 def s16_conv_ok(cin: int, cout: int) -> bool:
     """A convolution runs on the 16-bit kernels when forward (K = Cin), dgrad (K = Cout) and wgrad (M = Cout, N = Cin) all fit."""
     return cin % 64 == 0 and cout % 64 == 0
@@ -176,14 +161,6 @@ def colsum16(dy2d: torch.Tensor, rows: int, c: int, ld: Optional[int] = None) ->
 # ----------------------------------------------------------------------------------------
 # conv2d
 # ----------------------------------------------------------------------------------------
-def _region(taps, kh, stride, pad, dil, h, w, ho, wo, mask, gather) -> int:
-    """rect = 2 (region mode) for 3x3 stride-1 "same" convs most of whose tap work is padding (ASPP rates 12 / 24)."""
-    if taps != 9 or kh != 3 or stride != 1 or pad != dil or h != ho or w != wo or bin(mask).count("1") <= 1:
-        return 0
-    frac = _o.rect_fraction(gather, ho, wo, h, w, 3, 3, pad, dil, mask) if gather == 1 else _o.rect_fraction(2, h, w, ho, wo, 3, 3, pad, dil, mask)
-    return 2 if frac < 0.8 else 0
-
-
 class Conv2d16Fn(Function):
     """F.conv2d on bf16 [N,H,W,Cin] with the fp32 torch-layout weight [Cout,Cin,kh,kw] (groups = 1); bf16 result."""
 
@@ -195,66 +172,51 @@ class Conv2d16Fn(Function):
         cout, cin_w, kh, kw = weight.shape
         if cin_w != cin:
             raise RuntimeError(f"conv2d: input has {cin} channels, weight expects {cin_w}")
-        ho, wo = _o._conv_out(h, kh, stride, pad, dil), _o._conv_out(w, kw, stride, pad, dil)
-        if ho <= 0 or wo <= 0:
+        geom = (n, h, w, cin, cout, kh, kw, stride, pad, dil)
+        pl = conv_plan.plan("fwd", geom, S16)
+        if pl.ho <= 0 or pl.wo <= 0:
             raise RuntimeError("conv2d: empty output")
-        taps = kh * kw
         wt = weight16(_o.tap_major(weight), weight, "w")
-        y = torch.empty(n, ho, wo, cout, dtype=BF, device=x.device)
-        plain = taps == 1 and stride == 1 and pad == 0
-        geo = (n, h, w, ho, wo, kh, kw, stride, pad, dil)
-        mask = 1 if plain else _o.tap_mask(1, ho, wo, h, w, kh, kw, stride, pad, dil)
-        rect = 0 if plain else _region(taps, kh, stride, pad, dil, h, w, ho, wo, mask, 1)
-        gemm16("nt", x, wt, y, M=n * ho * wo, N=cout, K=cin, lda=cin, ldb=cin, ldc=cout, bias=bias, taps=taps, mask=mask,
-               tap_stride_b=cout * cin, gather=0 if plain else 1, geo=None if plain else geo, rect=rect, colstats=colstats)
+        y = torch.empty(n, pl.ho, pl.wo, cout, dtype=BF, device=x.device)
+        gemm16("nt", x, wt, y, M=pl.M, N=cout, K=cin, lda=cin, ldb=cin, ldc=cout, bias=bias, taps=pl.taps, mask=pl.mask,
+               tap_stride_b=cout * cin, gather=pl.gather, geo=pl.geo, rect=pl.rect, colstats=colstats)
         ctx.save_for_backward(x)
         ctx.weight_ref = weight
-        ctx.cfg = (n, h, w, cin, cout, kh, kw, ho, wo, stride, pad, dil, plain, bias is not None, tuple(weight.shape))
+        ctx.cfg = (geom, bias is not None, tuple(weight.shape))
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        n, h, w, cin, cout, kh, kw, ho, wo, stride, pad, dil, plain, has_bias, wshape = ctx.cfg
+        geom, has_bias, wshape = ctx.cfg
+        cin, cout = geom[3], geom[4]
         weight = ctx.weight_ref
         dy = _contig(dy)
-        taps = kh * kw
-        rows_o = n * ho * wo
         dx = dw = db = None
 
         def dgrad():
-            mask = 1 if plain else _o.tap_mask(2, h, w, ho, wo, kh, kw, stride, pad, dil)
-            if mask == 0:
+            pl = conv_plan.plan("dgrad", geom, S16)
+            if pl.mask == 0:
                 return _o.zeros(x.shape, dtype=BF, device=x.device)
-            rect = 0 if plain else _region(taps, kh, stride, pad, dil, h, w, ho, wo, mask, 2)
             dx = torch.empty_like(x)
             wT = weight16(_o.tap_major_T(weight), weight, "wT")
-            gemm16("nt", dy, wT, dx, M=n * h * w, N=cin, K=cout, lda=cout, ldb=cout, ldc=cin, taps=taps, mask=mask,
-                   tap_stride_b=cout * cin, gather=0 if plain else 2, geo=None if plain else (n, ho, wo, h, w, kh, kw, stride, pad, dil), rect=rect)
+            gemm16("nt", dy, wT, dx, M=pl.M, N=cin, K=cout, lda=cout, ldb=cout, ldc=cin, taps=pl.taps, mask=pl.mask,
+                   tap_stride_b=cout * cin, gather=pl.gather, geo=pl.geo, rect=pl.rect)
             return dx
 
         def wgrad():
-            mask = 1 if plain else _o.tap_mask(1, ho, wo, h, w, kh, kw, stride, pad, dil)
-            ntap = bin(mask).count("1")
-            split = tn_split16(rows_o, cout, cin, ntap)
-            # taps that fall mostly into the padding (ASPP rates 12 / 24): rectangle mode -- a tap reduces over its in-range output
-            # pixels only.  A slice is the same number of rows for every tap (a short rectangle uses fewer slices), so the slice
-            # count is the one of the in-range rows scaled back up to the whole map.
-            rect = 0
-            if not plain and stride == 1 and ntap > 1 and rows_o >= 2048:
-                frac = _o.rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask)
-                if frac < 0.8:
-                    s_in = tn_split16(max(512, int(rows_o * frac)), cout, cin, ntap)
-                    split = max(2, min(int(s_in / max(frac, 0.02) + 0.999), max(2, rows_o // 512), 65535))
-                    rect = 1
-            full = mask == (1 << taps) - 1
-            if taps == 1 and full:
+            # taps that fall mostly into the padding (ASPP rates 12 / 24) on a map of >= 2048 rows: rectangle mode -- a tap reduces over
+            # its in-range output pixels only.  A slice is the same number of rows for every tap (a short rectangle uses fewer slices),
+            # so the slice count is the one of the in-range rows scaled back up to the whole map (conv_plan.wgrad_split).
+            pl = conv_plan.plan("wgrad", geom, S16)
+            taps = pl.taps
+            if taps == 1 and not pl.zero_fill:
                 dwt = _o.grad_out(weight, (1, cout, cin), x.device)
             else:
-                dwt = (torch.empty if full else _o.zeros)(taps, cout, cin, dtype=torch.float32, device=x.device)
-            gemm16("tn", dy, x, dwt, M=cout, N=cin, K=rows_o, lda=cout, ldb=cin, ldc=cin, taps=taps, mask=mask, tap_stride_b=cout * cin,
-                   gather=0 if plain else 1, geo=None if plain else (n, h, w, ho, wo, kh, kw, stride, pad, dil), split=split, rect=rect)
+                dwt = (_o.zeros if pl.zero_fill else torch.empty)(taps, cout, cin, dtype=torch.float32, device=x.device)
+            gemm16("tn", dy, x, dwt, M=cout, N=cin, K=pl.K, lda=cout, ldb=cin, ldc=cin, taps=taps, mask=pl.mask, tap_stride_b=cout * cin,
+                   gather=pl.gather, geo=pl.geo, split=pl.split, rect=pl.rect)
             if taps == 1:
                 return dwt.view(wshape)
             dw = _o.grad_out(weight, wshape, x.device)
@@ -266,7 +228,7 @@ class Conv2d16Fn(Function):
         if ctx.needs_input_grad[1]:
             dw = wgrad()
         if has_bias and ctx.needs_input_grad[2]:
-            db = colsum16(dy, rows_o, cout)
+            db = colsum16(dy, dy.numel() // cout, cout)
         return dx, dw, db, None, None, None, None
 
 
@@ -362,16 +324,10 @@ def fold_plan16(x: torch.Tensor, weight: torch.Tensor, bn, stride: int, pad: int
     cout, cin_w, kh, kw = weight.shape
     if cin_w != cin or not s16_conv_ok(cin, cout) or cin > (1 << 18):
         return None
-    ho, wo = _o._conv_out(h, kh, stride, pad, dil), _o._conv_out(w, kw, stride, pad, dil)
-    if ho <= 0 or wo <= 0 or n * ho * wo <= 64:
+    pl = conv_plan.plan("fwd_folded", (n, h, w, cin, cout, kh, kw, stride, pad, dil), S16)
+    if pl.ho <= 0 or pl.wo <= 0 or pl.M <= 64 or pl.mask == 0:
         return None
-    taps = kh * kw
-    plain = taps == 1 and stride == 1 and pad == 0
-    mask = 1 if plain else _o.tap_mask(1, ho, wo, h, w, kh, kw, stride, pad, dil)
-    if mask == 0:
-        return None
-    rect = 0 if plain else _region(taps, kh, stride, pad, dil, h, w, ho, wo, mask, 1)
-    return plain, mask, rect, ho, wo
+    return pl.plain, pl.mask, pl.rect, pl.ho, pl.wo
 
 
 def _folded_images16(weight: torch.Tensor, bias: Optional[torch.Tensor], bn):

@@ -165,6 +165,33 @@ def test_conv_plan_matches_host_policy():
             ops.set_precision("f32")
 
 
+def test_conv_plan_matches_planner():
+    """glf_conv2d_plan against glfusion_amd.conv_plan.plan (the planner the 16-bit-storage wrappers ask, and the one the
+    fp32-storage wrappers are to move to), field by field: every pass, every conv geometry above and the ragged ones of
+    test_conv_plan_cpu.py, under every fp32-storage precision.  No policy is restated here; with the test above, the inline
+    policy of ops, the C plan and the planner are held to each other."""
+    import ctypes as C
+    import json
+    from glfusion_amd import conv_plan, ops
+    from glfusion_amd._lib import ConvParams, ConvPlan, lib
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_plan_table.json")) as f:
+        convs = [tuple(g) for g in json.load(f)["geometries"]]          # n, h, w, cin, cout, k, stride, pad, dil
+    assert len(convs) == 23 and (64, 28, 28, 2048, 256, 3, 1, 24, 24) in convs and (1, 1, 1, 64, 64, 1, 2, 1, 1) in convs
+    for prec in ("f32", "bf16x6", "f16x3", "f16"):
+        for (n, h, w, cin, cout, k, stride, pad, dil) in convs:
+            p = ConvParams()
+            p.n, p.h, p.w, p.cin, p.cout, p.kh, p.kw, p.stride, p.pad, p.dil = n, h, w, cin, cout, k, k, stride, pad, dil
+            p.precision = ops.PRECISIONS.index(prec) + 1
+            for i, pass_ in enumerate(conv_plan.PASSES):
+                pl = ConvPlan()
+                assert lib.glf_conv2d_plan(C.byref(p), i, C.byref(pl)) == 0
+                want = conv_plan.plan(pass_, (n, h, w, cin, cout, k, k, stride, pad, dil), ops.PRECISIONS.index(prec))
+                got = (pl.ho, pl.wo, pl.M, pl.N, pl.K, pl.taps, pl.kept_taps, pl.tap_mask, bool(pl.plain), pl.rect, pl.split,
+                       bool(pl.zero_fill), bool(pl.colstats_ok), pl.workspace_bytes)
+                assert got == (want.ho, want.wo, want.M, want.N, want.K, want.taps, want.kept, want.mask, want.plain, want.rect, want.split,
+                               want.zero_fill, want.colstats_ok, want.workspace_bytes), (prec, pass_, n, h, w, cin, cout, k, stride, pad, dil, got, want)
+
+
 def test_weights_plan_bookkeeping():
     """glf_weights_plan is host-only: grid bookkeeping of the multi-tensor weight refresh (first workgroup of every job in
     its pass, jobs / workgroups per pass) and its refusals (unsorted passes, misaligned packed images)."""
