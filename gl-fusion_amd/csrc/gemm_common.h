@@ -34,16 +34,26 @@ struct GemmArgs {
     // segmented region mode (glf_gemm_params.nseg > 0; 8-wave split-fp16 rows kernel, SEG instantiations only)
     const int* seg_tab;                         // device plan table (SegTab layout below); null = not a segmented launch
     int seg_kx;                                 // K extent of one extra segment
+    int seg_cols;                               // 1 = the table carries column-tile masks and a dispatch list (always with column groups,
+                                                // glf_gemm_nt_seg_cols; without them whenever the launch is small enough for a list)
 };
 
 // Device image of a segmented-region plan, in ints: [0, 64) first row tile of region r (INT_MAX beyond the last region);
 // then SEG_REGION_INTS per region: y0, x0, height, width, segment mask, rows (= n_img * height * width); then, 8-byte aligned,
-// one long long per segment: its element offset into A, (oy * wd + ox) * lda + acol.
+// one long long per segment: its element offset into A, (oy * wd + ox) * lda + acol; then one long long per segment: the
+// element offset of its slice in a row of B (K + s * seg_kx unless the caller gives its own).  With GemmArgs.seg_cols
+// two more parts follow: one segment mask per 128-column tile (the segments that contribute to its columns;
+// a workgroup walks `region mask & column-tile mask`), and the dispatch list, two ints per workgroup in blockIdx order:
+// (region << 16 | column tile, row tile inside the region).
 constexpr int SEG_MAX = 28, SEG_MAX_BANDS = 7, SEG_MAX_REGIONS = SEG_MAX_BANDS * SEG_MAX_BANDS;
 constexpr int SEG_REGION_INTS = 8;
 constexpr int SEG_TAB_REGIONS = 64, SEG_TAB_OFFS = SEG_TAB_REGIONS + SEG_REGION_INTS * SEG_MAX_REGIONS;
-constexpr int SEG_TAB_INTS = SEG_TAB_OFFS + 2 * SEG_MAX;
-static_assert(SEG_TAB_OFFS % 2 == 0, "segment offsets are 8-byte aligned");
+constexpr int SEG_TAB_BOFF = SEG_TAB_OFFS + 2 * SEG_MAX;
+constexpr int SEG_MAX_COLTILES = 64;
+constexpr int SEG_TAB_COLMASK = SEG_TAB_BOFF + 2 * SEG_MAX;
+constexpr int SEG_TAB_INTS = SEG_TAB_COLMASK + SEG_MAX_COLTILES;
+constexpr long long SEG_MAX_UNITS = 1 << 22;    // workgroups of a launch with a dispatch list
+static_assert(SEG_TAB_OFFS % 2 == 0 && SEG_TAB_INTS % 2 == 0, "segment offsets and the dispatch list are 8-byte aligned");
 constexpr int ZERO_PAGE_FLOATS = 1 << 18;
 
 
@@ -67,7 +77,9 @@ float* amax_scratch(int n, hipStream_t s);     // n consecutive device floats fr
 const float* zero_page();                      // ZERO_PAGE_FLOATS zeros on the device (glf_api.hip)
 bool f16s_rows_ok(const GemmArgs& a);
 bool f16s_tn_ok(const GemmArgs& a);
-int launch_rows_f16s_seg(const GemmArgs& a, const glf_gemm_params* p, int nprod, hipStream_t s);   // gemm_f16s.hip: segmented region mode
+// gemm_f16s.hip: segmented region mode; cols / boff: the column groups and B offsets of glf_gemm_nt_seg_cols (null = every
+// segment contributes to every column, its B slice at K + s * seg_kx)
+int launch_rows_f16s_seg(const GemmArgs& a, const glf_gemm_params* p, const int32_t* cols, const int64_t* boff, int nprod, hipStream_t s);
 }  // namespace glf
 
 namespace {
@@ -208,7 +220,7 @@ GemmArgs make_args(const float* A, const float* B, const float* bias, float* C, 
     a.vec_a = 0; a.vec_b = 0; a.rect = 0;
     a.amax_a = p->amax_a; a.amax_b = p->amax_b; a.zeros = nullptr; a.amax_c = p->amax_c; a.colstats = p->colstats; a.colmax = p->colstats ? p->colmax : nullptr; a.partial = nullptr; a.flags = 0; a.stamps = nullptr; a.a_presplit = p->a_presplit; a.b_presplit = p->b_presplit;
     a.epi = 0; a.res = nullptr; a.ld_res = 0; a.relu = 0;
-    a.seg_tab = nullptr; a.seg_kx = 0;
+    a.seg_tab = nullptr; a.seg_kx = 0; a.seg_cols = 0;
     return a;
 }
 

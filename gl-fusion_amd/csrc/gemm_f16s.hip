@@ -21,6 +21,7 @@
 #include "gemm_rows_walk.h"
 #include "gemm_tn_walk.h"
 #include "split_f16.h"
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -80,6 +81,9 @@ constexpr size_t SMEM_ROWS_H8 = 3 * BUF8 + 16;
 // small device table, args.seg_tab); a row tile enumerates (frame, pixel of its rectangle) as region mode does, walks the K columns
 // and then its rectangle's segments by ascending s -- a segment change is a new A row offset and a new B column offset, nothing
 // else -- and stores through the region-mode epilogue: every output element once.  SEG = false compiles to the code it was before.
+// With column groups (args.seg_cols; glf_gemm_nt_seg_cols) a segment contributes to a range of whole 128-column tiles only: the
+// workgroup walks `region mask & column-tile mask` (one more uniform word of the table).  Both forms take their tile from the host's
+// dispatch list when the plan has one (args.seg_cols), and B's slice of a segment is a table entry.
 template <bool GATHER, int NP, bool BP, bool PA = false, bool EPI = false, bool SEG = false>
 __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs args) {
     const int pM = args.M, pN = args.N, pK = args.K, p_lda = args.lda, p_ldb = args.ldb, p_ldc = args.ldc;
@@ -111,16 +115,31 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
     const RowsGeo G{p_gather, args.g.n_img, g_hs, g_ws, g_hd, g_wd, g_kw, g_stride, g_pad, g_dil};
     int tn;
     RowTile rt{0, pM, 0, 0, g_hd, g_wd, p_tap_mask};
-    rows_tile_order((args.flags >> 8) & 0xff, p_tiles_n, tn, rt.tm);
     unsigned seg_mask = 0;
     if constexpr (SEG) {
-        // the plan's regions: lane r holds the first row tile of region r (INT_MAX beyond the last), one ballot finds this tile's
-        const int start = p_seg[lane];
-        const int r = __builtin_amdgcn_readfirstlane(__popcll(__ballot(rt.tm >= start)) - 1);
+        int r;
+        if (args.seg_cols) {
+            // the host lists the workgroups longest chain first, balanced over the XCDs (seg_units; with column groups chains differ
+            // even across the column tiles of one row tile); this one's (region, column tile, row tile of the region) is entry
+            // blockIdx.x of that list
+            const int2 u = reinterpret_cast<const int2*>(p_seg + glf::SEG_TAB_INTS)[blockIdx.x];
+            const int rc = __builtin_amdgcn_readfirstlane(u.x);
+            r = rc >> 16; tn = rc & 0xffff;
+            rt.tm = __builtin_amdgcn_readfirstlane(u.y);
+        } else {
+            rows_tile_order((args.flags >> 8) & 0xff, p_tiles_n, tn, rt.tm);
+            // the plan's regions: lane r holds the first row tile of region r (INT_MAX beyond the last), one ballot finds this tile's
+            const int start = p_seg[lane];
+            r = __builtin_amdgcn_readfirstlane(__popcll(__ballot(rt.tm >= start)) - 1);
+            rt.tm -= p_seg[r];
+        }
         const int* __restrict__ reg = p_seg + SEG_TAB_REGIONS + SEG_REGION_INTS * r;
-        rt.tm -= p_seg[r];
         rt.y0 = reg[0]; rt.x0 = reg[1]; rt.h = reg[2]; rt.w = reg[3]; seg_mask = (unsigned)reg[4]; rt.rows = reg[5];
-    } else if (p_rect && !rows_locate<BM8, true>(p_rect, p_tap_mask, G, rt)) return;
+        if (args.seg_cols) seg_mask &= (unsigned)p_seg[glf::SEG_TAB_COLMASK + tn];      // the segments of this tile's column group
+    } else {
+        rows_tile_order((args.flags >> 8) & 0xff, p_tiles_n, tn, rt.tm);
+        if (p_rect && !rows_locate<BM8, true>(p_rect, p_tap_mask, G, rt)) return;
+    }
     const int tm = rt.tm, pMe = rt.rows;
     unsigned mask = rt.mask;
     const int bz = blockIdx.z;
@@ -145,7 +164,7 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
     int tap = -1, kc = nkc;
     int nk_cur = nkc;                   // SEG: K-iterations of the slice being walked (the K columns, then one segment at a time),
     long long ao_cur = 0;               // and that slice's element offsets into A's rows and B's rows
-    int bo_cur = 0;
+    long long bo_cur = 0;
     const float* pa[4];
     const float* pb[2];
     const int a_col[4] = {4 * ac, 4 * ac, 4 * ac, 4 * ac};
@@ -170,9 +189,9 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_f16s8_kernel(const GemmArgs 
                     const int sg = __builtin_amdgcn_readfirstlane(__ffs(rem_mask) - 1);
                     rem_mask &= rem_mask - 1;
                     const long long ao = reinterpret_cast<const long long*>(p_seg + SEG_TAB_OFFS)[sg];
-                    const int bo = pK + sg * p_kx;
+                    const long long bo = reinterpret_cast<const long long*>(p_seg + glf::SEG_TAB_BOFF)[sg];
                     const long long back = (long long)(nk_cur - 1) * BK;
-                    const long long da = ao - ao_cur - back, db = (long long)(bo - bo_cur) - back;
+                    const long long da = ao - ao_cur - back, db = bo - bo_cur - back;
                     ao_cur = ao; bo_cur = bo; nk_cur = p_kx / BK;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) pa[j] += (tm * BM8 + ar + 64 * j < pMe) ? da : (long long)BK;
@@ -1233,33 +1252,124 @@ static int seg_check(int n_img, int h, int w, int nseg, const int32_t* seg, cons
     return GLF_OK;
 }
 
-// device tables of the plans used so far: made once per (device, geometry, lda, segment list), never freed
-struct SegPlanDev { int dev, n_img, h, w, lda, nseg; int32_t seg[3 * SEG_MAX]; int* tab; long long row_tiles; };
+// ---- column groups (glf_gemm_nt_seg_cols) ----
+// A segment contributes to the columns [first, first + count) only, whole 128-column tiles: the mask of column tile t holds the
+// segments whose range covers it.  Returns false for a range that is not made of whole tiles inside [0, N).
+static bool seg_col_masks(int N, int nseg, const int32_t* cols, int tiles_n, unsigned* masks) {
+    for (int t = 0; t < tiles_n; ++t) masks[t] = 0;
+    for (int s = 0; s < nseg; ++s) {
+        const int c0 = cols[2 * s], cn = cols[2 * s + 1];
+        if (c0 < 0 || cn <= 0 || c0 % BN != 0 || cn % BN != 0 || (long long)c0 + cn > N) return false;
+        for (int t = c0 / BN; t < (c0 + cn) / BN; ++t) masks[t] |= 1u << s;
+    }
+    return true;
+}
+
+// Dispatch list of a launch with column groups.  A workgroup is (region, row tile of the region, column tile); its chain is the
+// K columns plus popcount(region mask & column-tile mask) segments, and chains of one row tile differ by up to an order of
+// magnitude (an ASPP head: 1 unit of K for the 1x1 columns, up to 9 for the rate-12 ones; the longest workgroup is a third of
+// the launch's duration).  Sorted longest chain first, so that a CU's last workgroups are the shortest; inside one chain length
+// by region, row tile, column tile.  Workgroups go to the eight XCDs round-robin by blockIdx and an XCD runs its own in order,
+// so a run of 8 * sub sorted entries is dealt out as eight GROUPS of `sub` neighbours (sub = 2 with column groups: typically
+// the two column tiles of one branch over one row tile, which read that A tile through one L2; the B tiles are shared by every
+// neighbour anyway), the heaviest group to the XCD that has been given the least work so far: the XCDs' totals stay within one
+// group's weight of each other.  A workgroup weighs w0 + w1 * chain (the K-iterations of the K columns and of one segment).
+// The same list serves a launch WITHOUT column groups (every column tile's mask is full, sub = 4): the plain tile order hands
+// each XCD one contiguous eighth of the tiles, and with regions sorted by chain length that is the longest eighth for XCD 0.
+struct SegUnit { int chain, r, tm, tn; };
+static void seg_units(int nreg, const SegRegion* regs, int tiles_n, const unsigned* colmasks, int sub, int w0, int w1, std::vector<SegUnit>& out) {
+    std::vector<SegUnit> u;
+    for (int r = 0; r < nreg; ++r)
+        for (long long tm = 0; tm < regs[r].tiles; ++tm)
+            for (int tn = 0; tn < tiles_n; ++tn) u.push_back(SegUnit{__builtin_popcount(regs[r].mask & colmasks[tn]), r, (int)tm, tn});
+    std::stable_sort(u.begin(), u.end(), [](const SegUnit& a, const SegUnit& b) {
+        if (a.chain != b.chain) return a.chain > b.chain;
+        if (a.r != b.r) return a.r < b.r;
+        if (a.tm != b.tm) return a.tm < b.tm;
+        return a.tn < b.tn;
+    });
+    out.resize(u.size());
+    const size_t n = u.size();
+    long long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const size_t run = 8 * (size_t)sub;
+    for (size_t c0 = 0; c0 < n; c0 += run) {
+        if (c0 + run > n) {                         // the last, partial run: the shortest chains, in sorted order
+            for (size_t i = c0; i < n; ++i) out[i] = u[i];
+            break;
+        }
+        int xcd[8] = {0, 1, 2, 3, 4, 5, 6, 7};      // by ascending load (insertion sort, stable); group j is the j-th heaviest
+        for (int i = 1; i < 8; ++i)
+            for (int k = i; k > 0 && load[xcd[k - 1]] > load[xcd[k]]; --k) { const int t = xcd[k]; xcd[k] = xcd[k - 1]; xcd[k - 1] = t; }
+        for (int j = 0; j < 8; ++j)
+            for (int i = 0; i < sub; ++i) {
+                const SegUnit& q = u[c0 + (size_t)sub * j + i];
+                out[c0 + 8 * (size_t)i + xcd[j]] = q;
+                load[xcd[j]] += w0 + (long long)w1 * q.chain;
+            }
+    }
+}
+
+// device tables of the plans used so far: made once per (device, geometry, lda, segment list, B offsets, column groups), never freed
+struct SegPlanDev {
+    int dev, n_img, h, w, lda, nseg, has_cols, N, K, kx, listed;
+    int32_t seg[3 * SEG_MAX], cols[2 * SEG_MAX];
+    long long boff[SEG_MAX];
+    int* tab; long long row_tiles; int max_chain;
+};
 static std::mutex g_seg_mu;
 static std::vector<SegPlanDev> g_seg_plans;
 
-int launch_rows_f16s_seg(const GemmArgs& a0, const glf_gemm_params* p, int nprod, hipStream_t s) {
+int launch_rows_f16s_seg(const GemmArgs& a0, const glf_gemm_params* p, const int32_t* cols, const int64_t* boff_in, int nprod, hipStream_t s) {
     GemmArgs a = a0;
     a.zeros = zero_page();
     const int n_img = p->n_img, h = p->hd, w = p->wd, nseg = p->nseg;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return fail(GLF_ERR_LAUNCH, "gemm_nt(seg): hipGetDevice failed");
+    if (cols && a.tiles_n > SEG_MAX_COLTILES) return fail(GLF_ERR_UNSUPPORTED, "gemm_nt(seg): column groups take at most %d column tiles", SEG_MAX_COLTILES);
+    SegPlanDev key;
+    memset(&key, 0, sizeof(key));
+    key.dev = dev; key.n_img = n_img; key.h = h; key.w = w; key.lda = p->lda; key.nseg = nseg; key.has_cols = cols != nullptr; key.N = p->N; key.K = p->K; key.kx = p->seg_kx;
+    memcpy(key.seg, p->seg, sizeof(int32_t) * 3 * nseg);
+    if (cols) memcpy(key.cols, cols, sizeof(int32_t) * 2 * nseg);
+    for (int i = 0; i < nseg; ++i) key.boff[i] = boff_in ? (long long)boff_in[i] : (long long)p->K + (long long)i * p->seg_kx;
     const int* tab = nullptr;
     long long row_tiles = 0;
+    int max_chain = nseg, listed = 0;
     {
         std::lock_guard<std::mutex> lk(g_seg_mu);
         for (const SegPlanDev& q : g_seg_plans)
-            if (q.dev == dev && q.n_img == n_img && q.h == h && q.w == w && q.lda == p->lda && q.nseg == nseg &&
-                memcmp(q.seg, p->seg, sizeof(int32_t) * 3 * nseg) == 0) { tab = q.tab; row_tiles = q.row_tiles; break; }
+            if (q.dev == dev && q.n_img == n_img && q.h == h && q.w == w && q.lda == p->lda && q.nseg == nseg && q.has_cols == key.has_cols &&
+                q.N == key.N && q.K == key.K && q.kx == key.kx && memcmp(q.seg, key.seg, sizeof(key.seg)) == 0 && memcmp(q.cols, key.cols, sizeof(key.cols)) == 0 &&
+                memcmp(q.boff, key.boff, sizeof(key.boff)) == 0) { tab = q.tab; row_tiles = q.row_tiles; max_chain = q.max_chain; listed = q.listed; break; }
         if (!tab) {
             SegRegion regs[SEG_MAX_REGIONS];
             const int nreg = seg_plan(n_img, h, w, nseg, p->seg, regs, &row_tiles);
             if (nreg < 0) return fail(GLF_ERR_UNSUPPORTED, "gemm_nt(seg): more than %d bands on an axis", SEG_MAX_BANDS);
             if (row_tiles * a.tiles_n >= 2147483647LL) return fail(GLF_ERR_BAD_SHAPE, "gemm_nt(seg): grid out of range");
+            unsigned colmasks[SEG_MAX_COLTILES] = {0};
+            std::vector<SegUnit> units;
+            if (cols) {
+                if (!seg_col_masks(p->N, nseg, cols, a.tiles_n, colmasks))
+                    return fail(GLF_ERR_UNSUPPORTED, "gemm_nt(seg): a segment's columns must be whole 128-column tiles inside [0, N)");
+                if (row_tiles * a.tiles_n > SEG_MAX_UNITS) return fail(GLF_ERR_UNSUPPORTED, "gemm_nt(seg): too many workgroups for a dispatch list");
+                listed = 1;
+            } else if (a.tiles_n <= SEG_MAX_COLTILES && row_tiles * a.tiles_n <= SEG_MAX_UNITS) {
+                // every segment contributes to every column: the same balanced dispatch list with full column-tile masks (a launch
+                // too large for one keeps the plain tile order)
+                for (int t = 0; t < a.tiles_n; ++t) colmasks[t] = 0xffffffffu;
+                listed = 1;
+            }
+            if (listed) seg_units(nreg, regs, a.tiles_n, colmasks, cols ? 2 : 4, p->K / BK, p->seg_kx / BK, units);
+            max_chain = 0;
+            for (int r = 0; r < nreg; ++r)
+                for (int t = 0; t < a.tiles_n; ++t) {
+                    const int c = __builtin_popcount(regs[r].mask & (listed ? colmasks[t] : 0xffffffffu));
+                    max_chain = c > max_chain ? c : max_chain;
+                }
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
             if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
                 return fail(GLF_ERR_UNSUPPORTED, "gemm_nt(seg): the first launch of a plan allocates its table -- run it once before capturing");
-            std::vector<int> host(SEG_TAB_INTS, 0);
+            std::vector<int> host(SEG_TAB_INTS + 2 * units.size(), 0);
             long long first = 0;
             for (int r = 0; r < SEG_TAB_REGIONS; ++r) {
                 host[r] = r < nreg ? (int)first : 2147483647;
@@ -1273,22 +1383,29 @@ int launch_rows_f16s_seg(const GemmArgs& a0, const glf_gemm_params* p, int nprod
             long long offs[SEG_MAX] = {0};
             for (int i = 0; i < nseg; ++i) offs[i] = ((long long)p->seg[3 * i] * w + p->seg[3 * i + 1]) * p->lda + p->seg[3 * i + 2];
             memcpy(host.data() + SEG_TAB_OFFS, offs, sizeof(offs));
+            memcpy(host.data() + SEG_TAB_BOFF, key.boff, sizeof(key.boff));
+            for (int t = 0; t < SEG_MAX_COLTILES; ++t) host[SEG_TAB_COLMASK + t] = (int)colmasks[t];
+            for (size_t i = 0; i < units.size(); ++i) {
+                host[SEG_TAB_INTS + 2 * i] = (units[i].r << 16) | units[i].tn;
+                host[SEG_TAB_INTS + 2 * i + 1] = units[i].tm;
+            }
             int* d = nullptr;
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), SEG_TAB_INTS * sizeof(int));
-            if (e == hipSuccess) e = hipMemcpy(d, host.data(), SEG_TAB_INTS * sizeof(int), hipMemcpyHostToDevice);
+            hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), host.size() * sizeof(int));
+            if (e == hipSuccess) e = hipMemcpy(d, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice);
             if (e != hipSuccess) return fail(GLF_ERR_WORKSPACE, "gemm_nt(seg): plan table: %s", hipGetErrorString(e));
-            SegPlanDev q;
-            q.dev = dev; q.n_img = n_img; q.h = h; q.w = w; q.lda = p->lda; q.nseg = nseg; q.tab = d; q.row_tiles = row_tiles;
-            memset(q.seg, 0, sizeof(q.seg));
-            memcpy(q.seg, p->seg, sizeof(int32_t) * 3 * nseg);
-            g_seg_plans.push_back(q);
+            key.tab = d; key.row_tiles = row_tiles; key.max_chain = max_chain; key.listed = listed;
+            g_seg_plans.push_back(key);
             tab = d;
         }
     }
-    a.seg_tab = tab; a.seg_kx = p->seg_kx; a.rect = 0; a.accumulate = 0;
+    // rows past a ragged tile's end read the zero page and walk through it for the whole chain: K columns, then the segments of the
+    // longest chain any workgroup of this plan walks; a chain that does not fit is refused
+    if ((long long)p->K + (long long)max_chain * p->seg_kx + BK > ZERO_PAGE_FLOATS)
+        return fail(GLF_ERR_UNSUPPORTED, "gemm_nt(seg): a chain of K + %d segments does not fit the zero page (%d floats)", max_chain, ZERO_PAGE_FLOATS);
+    a.seg_tab = tab; a.seg_kx = p->seg_kx; a.seg_cols = listed; a.rect = 0; a.accumulate = 0;
     a.tiles_m = (int)row_tiles;
     dim3 g2((unsigned)(row_tiles * a.tiles_n), 1, 1);
-    a.flags = ((a.tiles_n >= 8 ? 4 : 0) & 0xff) << 8;          // grouped tile order, as the plain launch
+    a.flags = ((a.tiles_n >= 8 ? 4 : 0) & 0xff) << 8;          // grouped tile order, as the plain launch (not used with a dispatch list)
     if (nprod == 3) hipLaunchKernelGGL((gemm_rows_f16s8_kernel<false, 3, true, true, false, true>), g2, dim3(NT8), SMEM_ROWS_H8, s, a);
     else hipLaunchKernelGGL((gemm_rows_f16s8_kernel<false, 1, true, true, false, true>), g2, dim3(NT8), SMEM_ROWS_H8, s, a);
     return check_launch("gemm_nt(f16x3, 256x128, segmented)");
@@ -1353,5 +1470,29 @@ extern "C" int glf_gemm_nt_seg_plan(int32_t n_img, int32_t h, int32_t w, int32_t
     }
     *n_regions = nreg;
     *row_tiles = total;
+    return GLF_OK;
+}
+
+extern "C" int glf_gemm_nt_seg_plan_cols(int32_t n_img, int32_t h, int32_t w, int32_t nseg, const int32_t* seg, const int32_t* seg_cols, int32_t N,
+                                         int32_t* regions, int32_t* n_regions, int64_t* row_tiles, uint32_t* col_masks, int32_t* order,
+                                         int64_t order_cap) {
+    using namespace glf;
+    GLF_REQUIRE(regions && n_regions && row_tiles && seg_cols && col_masks, GLF_ERR_NULL, "gemm_nt_seg_plan_cols: null argument");
+    if (int rc = glf_gemm_nt_seg_plan(n_img, h, w, nseg, seg, regions, n_regions, row_tiles)) return rc;
+    const int tiles_n = (N + BN - 1) / BN;
+    GLF_REQUIRE(N > 0 && tiles_n <= SEG_MAX_COLTILES, GLF_ERR_UNSUPPORTED, "gemm_nt_seg_plan_cols: N must give 1 .. %d column tiles", SEG_MAX_COLTILES);
+    GLF_REQUIRE(seg_col_masks(N, nseg, seg_cols, tiles_n, col_masks), GLF_ERR_UNSUPPORTED,
+                "gemm_nt_seg_plan_cols: a segment's columns must be whole 128-column tiles inside [0, N)");
+    const long long units = *row_tiles * tiles_n;
+    GLF_REQUIRE(units <= SEG_MAX_UNITS, GLF_ERR_UNSUPPORTED, "gemm_nt_seg_plan_cols: too many workgroups for a dispatch list");
+    if (order) {
+        GLF_REQUIRE(order_cap >= units, GLF_ERR_BAD_SHAPE, "gemm_nt_seg_plan_cols: order has room for %lld workgroups, the plan has %lld", (long long)order_cap, units);
+        SegRegion regs[SEG_MAX_REGIONS];
+        long long total = 0;
+        const int nreg = seg_plan(n_img, h, w, nseg, seg, regs, &total);
+        std::vector<SegUnit> u;
+        seg_units(nreg, regs, tiles_n, col_masks, 2, 1, 1, u);
+        for (size_t i = 0; i < u.size(); ++i) { order[3 * i] = u[i].r; order[3 * i + 1] = u[i].tm; order[3 * i + 2] = u[i].tn; }
+    }
     return GLF_OK;
 }

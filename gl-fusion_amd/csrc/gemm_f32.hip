@@ -820,6 +820,38 @@ __global__ __launch_bounds__(256) void gemm_skinny_nt_kernel(const float* __rest
     }
 }
 
+// Segmented region mode (glf_gemm_params.nseg): the SEG instantiations of the 8-wave split-fp16 kernel only.  cols / boff: the column
+// groups and B offsets of glf_gemm_nt_seg_cols, null for glf_gemm_nt.  Everything is refused before the first launch.
+static int seg_launch(GemmArgs& a, const glf_gemm_params* p, const int32_t* cols, const int64_t* boff, const char* who, glf_stream_t stream) {
+    const int prec = call_precision(p);
+    GLF_REQUIRE(p->nseg >= 1 && p->nseg <= GLF_SEG_MAX && p->seg != nullptr, GLF_ERR_UNSUPPORTED, "%s: nseg must be in [1, %d] with a segment list", who, GLF_SEG_MAX);
+    GLF_REQUIRE(prec >= 2 && glf::f16s_rows_ok(a) && p->a_presplit && p->b_presplit && p->amax_a && p->amax_b, GLF_ERR_UNSUPPORTED,
+                "%s: segments need precision 3 / 4, the aligned fast path and both operands pre-split with their amax", who);
+    GLF_REQUIRE(!p->gather && p->taps == 1 && !p->rect && !p->accumulate && p->batch == 1, GLF_ERR_UNSUPPORTED,
+                "%s: segments extend a plain NT launch (no gather, rect, accumulate or batch)", who);
+    // colstats / colmax: every element is stored once through the region-mode epilogue, which counts exactly the rows it stores;
+    // colmax comes from the wide-store form of that epilogue only (as for a plain launch)
+    GLF_REQUIRE(!p->colmax || (p->colstats && p->ldc % 4 == 0 && p->N % 4 == 0 && aligned16(a.C)), GLF_ERR_UNSUPPORTED,
+                "%s: colmax needs colstats and a 16-byte aligned C with ldc and N multiples of 4", who);
+    GLF_REQUIRE(p->n_img > 0 && p->hd > 0 && p->wd > 0 && (long long)p->n_img * p->hd * p->wd == p->M && p->K <= p->lda && p->N <= p->ldc,
+                GLF_ERR_BAD_SHAPE, "%s: segments need M (%d) == n_img*hd*wd, K <= lda and N <= ldc", who, p->M);
+    GLF_REQUIRE(p->seg_kx >= BK && p->seg_kx % BK == 0, GLF_ERR_UNSUPPORTED, "%s: segments need seg_kx %% 32 == 0", who);
+    if (boff) {
+        // (B's slice of segment s starts boff[s] floats behind the start of the row of each of the segment's columns: the caller
+        // vouches for the buffer behind it)
+        for (int i = 0; i < p->nseg; ++i)
+            GLF_REQUIRE(boff[i] >= 0 && boff[i] % 4 == 0, GLF_ERR_UNSUPPORTED, "%s: segment %d: the B offset must be a non-negative multiple of 4", who, i);
+    } else {
+        GLF_REQUIRE((long long)p->K + (long long)p->nseg * p->seg_kx <= p->ldb, GLF_ERR_UNSUPPORTED, "%s: segments need K + nseg * seg_kx <= ldb", who);
+    }
+    if (cols) GLF_REQUIRE(p->N % BN == 0, GLF_ERR_UNSUPPORTED, "%s: column groups need N %% 128 == 0", who);
+    for (int i = 0; i < p->nseg; ++i)
+        GLF_REQUIRE(p->seg[3 * i + 2] >= 0 && p->seg[3 * i + 2] % 4 == 0 && p->seg[3 * i + 2] + p->seg_kx <= p->lda, GLF_ERR_UNSUPPORTED,
+                    "%s: segment %d: acol must be a multiple of 4 with acol + seg_kx <= lda", who, i);
+    // (overhang rows walk the zero page from end to end of the chain: the launcher bounds the longest chain of the plan by the page)
+    return glf::launch_rows_f16s_seg(a, p, cols, boff, prec == 2 ? 3 : 1, glf::S(stream));
+}
+
 extern "C" int glf_gemm_nt(const float* A, const float* B, const float* bias, float* C,
                            const glf_gemm_params* p, glf_stream_t stream) {
     if (int rc = glf::ensure_init()) return rc;
@@ -832,23 +864,7 @@ extern "C" int glf_gemm_nt(const float* A, const float* B, const float* bias, fl
     a.vec_a = aligned16(A) && (p->lda % 4 == 0) && (p->batch_stride_a % 4 == 0);
     a.vec_b = aligned16(B) && (p->ldb % 4 == 0) && (p->batch_stride_b % 4 == 0) && (p->tap_stride_b % 4 == 0);
     dim3 grid(a.tiles_m * a.tiles_n, 1, p->batch);
-    if (p->nseg != 0) {                 // segmented region mode: the SEG instantiations of the 8-wave split-fp16 kernel only
-        GLF_REQUIRE(p->nseg >= 1 && p->nseg <= GLF_SEG_MAX && p->seg != nullptr, GLF_ERR_UNSUPPORTED, "glf_gemm_nt: nseg must be in [1, %d] with a segment list", GLF_SEG_MAX);
-        GLF_REQUIRE(prec >= 2 && glf::f16s_rows_ok(a) && p->a_presplit && p->b_presplit && p->amax_a && p->amax_b, GLF_ERR_UNSUPPORTED,
-                    "glf_gemm_nt: segments need precision 3 / 4, the aligned fast path and both operands pre-split with their amax");
-        GLF_REQUIRE(!p->gather && p->taps == 1 && !p->rect && !p->accumulate && !p->colstats && !p->colmax && p->batch == 1, GLF_ERR_UNSUPPORTED,
-                    "glf_gemm_nt: segments extend a plain NT launch (no gather, rect, accumulate, colstats or batch)");
-        GLF_REQUIRE(p->n_img > 0 && p->hd > 0 && p->wd > 0 && (long long)p->n_img * p->hd * p->wd == p->M && p->K <= p->lda && p->N <= p->ldc,
-                    GLF_ERR_BAD_SHAPE, "glf_gemm_nt: segments need M (%d) == n_img*hd*wd, K <= lda and N <= ldc", p->M);
-        // (overhang rows walk the zero page from end to end of the chain, 16 bytes per lane of a 32-float row: it must hold all of it)
-        GLF_REQUIRE(p->seg_kx >= BK && p->seg_kx % BK == 0 && (long long)p->K + (long long)p->nseg * p->seg_kx <= p->ldb &&
-                    (long long)p->K + (long long)p->nseg * p->seg_kx + BK <= glf::ZERO_PAGE_FLOATS, GLF_ERR_UNSUPPORTED,
-                    "glf_gemm_nt: segments need seg_kx %% 32 == 0 and K + nseg * seg_kx <= ldb, < 2^18");
-        for (int i = 0; i < p->nseg; ++i)
-            GLF_REQUIRE(p->seg[3 * i + 2] >= 0 && p->seg[3 * i + 2] % 4 == 0 && p->seg[3 * i + 2] + p->seg_kx <= p->lda, GLF_ERR_UNSUPPORTED,
-                        "glf_gemm_nt: segment %d: acol must be a multiple of 4 with acol + seg_kx <= lda", i);
-        return glf::launch_rows_f16s_seg(a, p, prec == 2 ? 3 : 1, glf::S(stream));
-    }
+    if (p->nseg != 0) return seg_launch(a, p, nullptr, nullptr, "glf_gemm_nt", stream);     // segmented region mode
     if (p->M <= 64 && !p->gather && p->taps == 1 && p->batch == 1 && !p->rect && !p->colstats && !p->a_presplit && !p->b_presplit && a.vec_a &&
         a.vec_b && p->K % 16 == 0 && p->N >= 64) {
         hipLaunchKernelGGL(gemm_skinny_nt_kernel, dim3((p->N + SK_COLS - 1) / SK_COLS), dim3(256), 0, glf::S(stream), A, B, bias, C, p->M, p->N, p->K,
@@ -885,6 +901,18 @@ extern "C" int glf_gemm_nt(const float* A, const float* B, const float* bias, fl
     else
         hipLaunchKernelGGL((gemm_rows_kernel<0, false>), grid, dim3(NTHREADS), SMEM_ROWS_NT, glf::S(stream), a);
     return glf::check_launch("gemm_nt");
+}
+
+// glf_gemm_nt in segmented region mode whose segments belong to groups of output columns (include/glfusion.h)
+extern "C" int glf_gemm_nt_seg_cols(const float* A, const float* B, float* C, const glf_gemm_params* p, const int32_t* seg_cols,
+                                    const int64_t* seg_boff, glf_stream_t stream) {
+    GLF_REQUIRE(seg_cols != nullptr, GLF_ERR_NULL, "gemm_nt_seg_cols: null column groups");
+    if (int rc = glf::ensure_init()) return rc;
+    if (int rc = validate(p, A, B, C)) return rc;
+    GemmArgs a = make_args(A, B, nullptr, C, p);
+    a.vec_a = aligned16(A) && (p->lda % 4 == 0);
+    a.vec_b = aligned16(B) && (p->ldb % 4 == 0);
+    return seg_launch(a, p, seg_cols, seg_boff, "glf_gemm_nt_seg_cols", stream);
 }
 
 // glf_gemm_nt with the fused output epilogue C = act(alpha * acc + shift[n] (+ residual[m][n])): the EPI instantiations of the

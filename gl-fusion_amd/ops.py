@@ -185,7 +185,7 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
          split: int = 1, rect: bool = False, amax_a: Optional[torch.Tensor] = None,
          amax_b: Optional[torch.Tensor] = None, amax_c: Optional[torch.Tensor] = None,
          colstats: Optional[torch.Tensor] = None, a_packed: bool = False, b_packed: bool = False,
-         colmax: Optional[torch.Tensor] = None, epilogue=None, oihw: bool = False, foreign=None, seg=None) -> bool:
+         colmax: Optional[torch.Tensor] = None, epilogue=None, oihw: bool = False, foreign=None, seg=None, seg_cols=None) -> bool:
     """mode in {'nt','nn','tn'}; geo = (n_img, hs, ws, hd, wd, kh, kw, stride, pad, dil).
     epilogue ('nt' only): (residual or None, its row stride, relu) -- the call goes to glf_gemm_nt_epilogue, which stores
     act(alpha * acc + bias[n] + residual[m][n]) once (bias is then required: the folded BatchNorm shift).
@@ -199,7 +199,9 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
     seg ('nt' only, glf_gemm_params.nseg): (kx, [(oy, ox, acol), ...], dense FLOPs, executed FLOPs) -- the segmented region
     mode over the geo = (n_img, h, w, h, w, 1, 1, 1, 0, 1) map; the two FLOP counts are what the profiler record carries.  A
     launch the library refuses as unsupported returns False (nothing ran: the caller takes its other route); every other
-    call returns True."""
+    call returns True.
+    seg_cols (with seg, glf_gemm_nt_seg_cols): [(first column, columns, B offset), ...], one per segment -- the segment adds to
+    that group of output columns only and reads its slice of B at that offset from the start of a column's row."""
     p = GemmParams()
     p.M, p.N, p.K, p.lda, p.ldb, p.ldc = M, N, K, lda, ldb, ldc
     p.taps, p.tap_mask, p.tap_stride_b, p.gather = taps, mask, tap_stride_b, gather
@@ -225,6 +227,13 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
             raise ValueError("gemm: segments exist for mode 'nt' only")
         seg_arr = (C.c_int32 * (3 * len(seg[1])))(*[v for t in seg[1] for v in t])
         p.nseg, p.seg_kx, p.seg = len(seg[1]), int(seg[0]), C.cast(seg_arr, C.c_void_p)
+        if seg_cols is not None:
+            if bias is not None or epilogue is not None or len(seg_cols) != len(seg[1]):
+                raise ValueError("gemm: column groups take one (first column, columns, B offset) per segment, no bias, no epilogue")
+            cols_arr = (C.c_int32 * (2 * len(seg_cols)))(*[v for t in seg_cols for v in t[:2]])
+            boff_arr = (C.c_int64 * len(seg_cols))(*[t[2] for t in seg_cols])
+    elif seg_cols is not None:
+        raise ValueError("gemm: column groups belong to a segmented launch (seg=)")
     ws = None
     if mode == "tn" and (split > 1 or oihw) and mask:
         # two-stage reduction: the slices store partial sums, a second kernel adds them in a fixed order -- no atomics, no
@@ -243,7 +252,10 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
     elif epilogue is not None:
         raise ValueError("gemm: the fused epilogue exists for mode 'nt' only")
     elif mode == "nt":
-        rc = lib.glf_gemm_nt(_p(A), _p(B), _p(bias), _p(Cm), C.byref(p), _stream())
+        if seg_cols is not None:
+            rc = lib.glf_gemm_nt_seg_cols(_p(A), _p(B), _p(Cm), C.byref(p), C.cast(cols_arr, C.c_void_p), C.cast(boff_arr, C.c_void_p), _stream())
+        else:
+            rc = lib.glf_gemm_nt(_p(A), _p(B), _p(bias), _p(Cm), C.byref(p), _stream())
         if seg is not None and rc == -2:          # GLF_ERR_UNSUPPORTED
             return False
         check(rc, "gemm_nt")
@@ -272,6 +284,8 @@ def gemm(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: in
         if seg is not None:
             dense, executed = float(seg[2]), float(seg[3])
             abytes = 4.0 * (M * lda + N * (K + len(seg[1]) * seg[0]) + M * N)
+            if seg_cols is not None:           # a segment's slice exists for its own columns only
+                abytes = 4.0 * (M * lda + N * K + seg[0] * sum(t[1] for t in seg_cols) + M * N)
         prof.append((KERNEL_NAMES[(mode, gather != 0)], dense, executed, ev0, ev1,
                      (M, N, K, taps, kept_taps, batch, split, geo[8] if geo else 0, geo[9] if geo else 0), abytes))
     return True
@@ -1158,6 +1172,16 @@ CENTRE_TAP = 1 << 4                    # of a 3x3 kernel
 _centre_cache = {}
 
 
+def _tap_slab_into(src: torch.Tensor, taps: int, tap: int, dst: torch.Tensor, cout: int, cin: int, what: str) -> None:
+    """dst [Cout][Cin] = tap `tap` of the contiguous OIHW weight src, outside the multi-tensor refresh (a new or stale image):
+    the strided gather the image's GLF_WJ_COPY job does.  Not through tap_major(): that would register the whole tap-major
+    image of the weight, 9 Cout Cin floats recomputed with every update, for a head whose launches read none of it."""
+    if taps == 1:
+        check(lib.glf_copy_frames(_p(src), cout * cin, _p(dst), cout * cin, 1, cout * cin, _stream()), what)
+    else:
+        dst.copy_(src.view(cout, cin, taps)[:, :, tap])
+
+
 def aspp_centre_weights(weights) -> torch.Tensor:
     """Wc [k Cout][Cin]: the 1x1 weight and the centre taps of the 3x3 weights stacked by rows, bit-identical to slicing the
     parameters.  Like fusion._qkv_weights: the buffer lives as long as the first weight, every row block is a registered weight
@@ -1184,8 +1208,7 @@ def aspp_centre_weights(weights) -> torch.Tensor:
             _registry(t.device).drop(im.key)
             im, fresh = _wimage(t, "centre", kind, src, dims, lambda dst=dst: dst)
         if fresh:
-            one = src if taps == 1 else tap_major(t)[taps // 2]       # the centre slab [Cout][Cin] of the tap-major image
-            check(lib.glf_copy_frames(_p(one), cout * cin, _p(im.dst), cout * cin, 1, cout * cin, _stream()), "aspp_centre_weights")
+            _tap_slab_into(src, taps, taps // 2, im.dst, cout, cin, "aspp_centre_weights")
     return Wc
 
 
@@ -1239,8 +1262,7 @@ def aspp_dgrad_weights(weights, segs) -> torch.Tensor:
             _registry(t.device).drop(im.key)
             im, fresh = _wimage(t, tag, kind, src, dims, lambda dst=dst: dst)
         if fresh:
-            one = src if taps == 1 else tap_major(t)[tap]
-            check(lib.glf_copy_frames(_p(one), cout * cin, _p(im.dst), cout * cin, 1, cout * cin, _stream()), "aspp_dgrad_weights")
+            _tap_slab_into(src, taps, tap, im.dst, cout, cin, "aspp_dgrad_weights")
     return Wd
 
 
@@ -1266,6 +1288,71 @@ def _aspp_dgrad_one(G, am_g, weights, dils, dx, slot, n: int, h: int, w: int, ci
     return gemm("nt", G, wb, dx, M=rows, N=cin, K=ldu, lda=ldu, ldb=ldb, ldc=cin, geo=(n, h, w, h, w, 1, 1, 1, 0, 1),
                 amax_a=am_g, amax_b=am_wd, amax_c=slot, a_packed=True, b_packed=True,
                 seg=(cout, [(oy, ox, acol) for _, _, oy, ox, acol in segs], dense, executed))
+
+
+# The head's FORWARD as one launch (glf_gemm_nt_seg_cols): the stacked centre contraction x Wc^T extended by one segment per kept
+# off-centre tap, each adding to its own branch's columns only -- every element of U stored once, with final column statistics
+# for every branch, where the rate-12 / 24 taps used to be per-tap rectangles that add into U with float atomics and leave their
+# BatchNorms to reduce their own statistics.  0: those launches.
+ASPP_FWD_ONE = os.environ.get("GLF_ASPP_FWD_ONE", "1") != "0"
+COL_TILE = 128                         # column groups of a segmented launch are whole column tiles of the NT kernel
+
+
+def aspp_fwd_segments(dils, h: int, w: int, cout: int):
+    """[(branch, tap, oy, ox, first column)] of the kept off-centre taps of the dilated branches on an h x w map, branch by
+    branch in tap order: the tap reads the input pixel (y + oy, x + ox) and adds to the columns [first, first + cout) of U."""
+    segs = []
+    for i, d in enumerate(dils, start=1):
+        off = tap_mask(1, h, w, h, w, 3, 3, 1, d, d) & ~CENTRE_TAP
+        for t in range(9):
+            if (off >> t) & 1:
+                ky, kx = divmod(t, 3)
+                segs.append((i, t, (ky - 1) * d, (kx - 1) * d, i * cout))
+    return segs
+
+
+def aspp_fwd_weights(weights, segs) -> torch.Tensor:
+    """Wf [(k + nseg) Cout][Cin]: the rows of aspp_centre_weights (Wc), then the tap slab [Cout][Cin] of every segment in
+    aspp_fwd_segments order -- each branch's taps in row blocks of their own, reached through a B offset per segment
+    (aspp_fwd_cols), not a dense [k Cout][Cin + nseg Cin] image that would be 3/4 unused.  The same row blocks in the same order
+    as aspp_dgrad_weights' (a 3x3 pad == dil conv keeps the same taps in both directions): ONE buffer, one set of GLF_WJ_COPY
+    jobs and one maximum serve the head's forward and its input gradient; the forward adds its packed form."""
+    return aspp_dgrad_weights(weights, segs)
+
+
+def aspp_fwd_cols(segs, k: int, cout: int, cin: int):
+    """[(first column, columns, B offset)] per segment for gemm(seg_cols=): segment s is row block k + s of aspp_fwd_weights'
+    image, so its slice for column c of its branch starts (k + s) Cout - first column rows behind the start of row c."""
+    return [(col0, cout, ((k + s) * cout - col0) * cin) for s, (_, _, _, _, col0) in enumerate(segs)]
+
+
+def _aspp_fwd_one(x, am_x, weights, dils, U, sums, n: int, h: int, w: int, cin: int, cout: int):
+    """U = x Wf^T in one segmented launch with column groups; the packed x it read, or None when this head does not take that
+    route (nothing ran: the caller makes today's launches).  Under engine.StepGraph the first launch of a plan, which
+    allocates and copies its device table, happens in the eager warm-up steps, as for the input gradient's launch."""
+    k = len(weights)
+    ldu = k * cout
+    if not ASPP_FWD_ONE or _PREC[0] not in (2, 3) or cout % COL_TILE != 0 or not nt_presplit_ok(cin, cin, cin):
+        return None
+    segs = aspp_fwd_segments(dils, h, w, cout)
+    if not segs or len(segs) > SEG_MAX:
+        return None
+    Wf = aspp_fwd_weights(weights, segs)
+    am_wf = amax_of(Wf)
+    wb = weight_packed(Wf, Wf, "w", am_wf)
+    xa = act_packed(x, am_x)
+    if wb is None or xa is None:
+        return None
+    rows = n * h * w
+    # executed work: the K columns of every pixel plus the (pixel, in-range segment) pairs; dense: what the stacked launch and the
+    # off-centre launches it replaces reported together (every tap of those branches, padding included)
+    pairs = sum(max(0, h - abs(oy)) * max(0, w - abs(ox)) for _, _, oy, ox, _ in segs)
+    executed = 2.0 * cin * cout * (rows * k + n * pairs)
+    dense = 2.0 * rows * cin * (ldu + 9 * cout * len({i for i, _, _, _, _ in segs}))
+    ok = gemm("nt", xa, wb, U, M=rows, N=ldu, K=cin, lda=cin, ldb=cin, ldc=ldu, geo=(n, h, w, h, w, 1, 1, 1, 0, 1),
+              amax_a=am_x, amax_b=am_wf, colstats=sums, a_packed=True, b_packed=True,
+              seg=(cin, [(oy, ox, 0) for _, _, oy, ox, _ in segs], dense, executed), seg_cols=aspp_fwd_cols(segs, k, cout, cin))
+    return xa if ok else None
 
 
 def aspp_centre_ok(x: torch.Tensor, convs) -> bool:
@@ -1339,7 +1426,8 @@ class _GradGroup:
 class AsppCentreFn(Function):
     """The conv branches of an ASPP head (a 1x1 conv and 3x3 stride-1 pad == dil convs over one input) up to their BatchNorm
     inputs: k outputs, column slices of one [N,H,W,k Cout] buffer, plus the per-branch column statistics [k][2][Cout] (final
-    for the 1x1 branch and for every 3x3 branch whose kept taps are the centre alone)."""
+    for every branch after the one segmented launch, _aspp_fwd_one; otherwise for the 1x1 branch and for every 3x3 branch
+    whose kept taps are the centre alone)."""
 
     @staticmethod
     def forward(ctx, x, dils, stats: bool, *weights):
@@ -1347,17 +1435,23 @@ class AsppCentreFn(Function):
         n, h, w, cin = x.shape
         k, cout = len(weights), weights[0].shape[0]
         rows, ldu, dev = n * h * w, k * cout, x.device
-        Wc = aspp_centre_weights(weights)
-        am_x, am_wc = amax_of(x), amax_of(Wc)
-        ok = nt_presplit_ok(cin, cin, cin)
-        ok_x = ok and (ldu >= PRESPLIT_MIN_COLS or packed_hit(x, am_x) is not None)
-        xa, pa = pick(x, act_packed(x, am_x) if ok_x else None, ok_x)
-        wb, pb = pick(Wc, weight_packed(Wc, Wc, "w", am_wc) if ok else None, ok)
+        am_x = amax_of(x)
         U = torch.empty(n, h, w, ldu, dtype=torch.float32, device=dev)
         sums = stats_slot(ldu, dev) if stats else None
-        gemm("nt", xa, wb, U, M=rows, N=ldu, K=cin, lda=cin, ldb=cin, ldc=ldu, amax_a=am_x, amax_b=am_wc, colstats=sums,
-             a_packed=pa, b_packed=pb)
-        for i in range(1, k):
+        # one segmented launch stores U and the statistics of every branch; where it does not apply: the stacked centre launch,
+        # then one adding launch per branch that keeps off-centre taps
+        xa = _aspp_fwd_one(x, am_x, weights, dils, U, sums, n, h, w, cin, cout)
+        one, pa = xa is not None, xa is not None
+        if not one:
+            Wc = aspp_centre_weights(weights)
+            am_wc = amax_of(Wc)
+            ok = nt_presplit_ok(cin, cin, cin)
+            ok_x = ok and (ldu >= PRESPLIT_MIN_COLS or packed_hit(x, am_x) is not None)
+            xa, pa = pick(x, act_packed(x, am_x) if ok_x else None, ok_x)
+            wb, pb = pick(Wc, weight_packed(Wc, Wc, "w", am_wc) if ok else None, ok)
+            gemm("nt", xa, wb, U, M=rows, N=ldu, K=cin, lda=cin, ldb=cin, ldc=ldu, amax_a=am_x, amax_b=am_wc, colstats=sums,
+                 a_packed=pa, b_packed=pb)
+        for i in range(1, 1 if one else k):
             d = dils[i - 1]
             mask = tap_mask(1, h, w, h, w, 3, 3, 1, d, d)
             off = mask & ~CENTRE_TAP
@@ -1375,6 +1469,7 @@ class AsppCentreFn(Function):
                  amax_a=am_x, amax_b=am_w, a_packed=pi, b_packed=pbi)
         # [2][k Cout] -> [k][2][Cout]: the layout a BatchNorm reads its own sums in (a 16 KB copy)
         s4 = sums.view(2, k, cout).permute(1, 0, 2).contiguous() if stats else torch.empty(0, dtype=torch.float64, device=dev)
+        s4._glf_final_all = one                  # the one launch counted every branch's elements: no BatchNorm reduces its own
         ctx.mark_non_differentiable(s4)
         ctx.save_for_backward(x)
         ctx.x_packed = (xa, am_x) if (pa and packed_hit(x, am_x) is not None) else None
@@ -1468,13 +1563,14 @@ class AsppCentreFn(Function):
 
 def aspp_centre_convs(x, convs, stats: bool):
     """The conv outputs of the ASPP conv branches `convs` (see aspp_centre_ok) and, with stats, their column statistics:
-    ([u_0 .. u_{k-1}], [sums_i or None]) -- sums_i is None where branch i kept off-centre taps (its BatchNorm reduces its
-    own statistics, as it does today)."""
+    ([u_0 .. u_{k-1}], [sums_i or None]) -- every branch gets its sums from the one segmented launch (ASPP_FWD_ONE); on the
+    other route sums_i is None where branch i kept off-centre taps (its BatchNorm reduces its own statistics)."""
     n, h, w = x.shape[0], x.shape[1], x.shape[2]
     dils = tuple(int(cv.dilation[0]) for cv in convs[1:])
     out = AsppCentreFn.apply(x, dils, bool(stats), *[cv.weight for cv in convs])
     us, s4 = out[:-1], out[-1]
-    final = [True] + [(tap_mask(1, h, w, h, w, 3, 3, 1, d, d) & ~CENTRE_TAP) == 0 for d in dils]
+    all_final = bool(getattr(s4, "_glf_final_all", False))
+    final = [True] + [all_final or (tap_mask(1, h, w, h, w, 3, 3, 1, d, d) & ~CENTRE_TAP) == 0 for d in dils]
     return list(us), [s4[i] if (stats and f) else None for i, f in enumerate(final)]
 
 

@@ -171,9 +171,14 @@ typedef struct {
                                 /* in-range segments is constant: a row tile walks the K columns, then its rectangle's segments   */
                                 /* by ascending s, and every output element is stored ONCE (no accumulate, no zero fill, no       */
                                 /* atomics; bitwise reproducible; amax_c reported).  Precision 3 / 4 with BOTH operands pre-split, */
-                                /* K and seg_kx multiples of 32, acol a multiple of 4, batch 1, no colstats; anything else is     */
+                                /* K and seg_kx multiples of 32, acol a multiple of 4, batch 1; anything else is                  */
                                 /* GLF_ERR_UNSUPPORTED.  The plan's small device table is made on the first launch of a given     */
                                 /* (geometry, segment list) and kept: later launches allocate and copy nothing (graph-capturable). */
+                                /* colstats / colmax are honoured: every stored element counts once, the overhang rows of a ragged */
+                                /* rectangle tile do not.  Rows past a ragged tile's end read a zero page of 2^18 floats for the   */
+                                /* whole chain: K plus the most segments any rectangle walks, times seg_kx, has to fit into it     */
+                                /* (GLF_ERR_UNSUPPORTED otherwise).  Segments that belong to a group of output columns:            */
+                                /* glf_gemm_nt_seg_cols.                                                                          */
 } glf_gemm_params;
 #define GLF_TN_OIHW_MAX_TAPS 9
 #define GLF_SEG_MAX 28
@@ -188,6 +193,31 @@ typedef struct {
  * rectangle (the last one ragged).  *row_tiles = their sum: the launch's grid is that times ceil(N / 128). */
 int glf_gemm_nt_seg_plan(int32_t n_img, int32_t h, int32_t w, int32_t nseg, const int32_t* seg, int32_t* regions,
                          int32_t* n_regions, int64_t* row_tiles);
+
+/* glf_gemm_nt in segmented region mode (p->nseg >= 1, no bias) whose segments belong to GROUPS OF OUTPUT COLUMNS -- the forward of
+ * an ASPP head: the K columns are the 1x1 branch and every centre tap, a segment is an off-centre tap of ONE branch and adds to that
+ * branch's columns only.  seg_cols is a HOST array [nseg][2] = (first column, column count) of whole 128-column tiles inside
+ * [0, N) with N % 128 == 0 and at most 64 column tiles.  seg_boff, a HOST array [nseg] or NULL, is the offset in floats (>= 0,
+ * % 4 == 0) from the start of the B row of one of the segment's columns to the segment's slice of seg_kx floats; NULL means
+ * K + s * seg_kx.  With offsets the B image need not be [N][K + nseg * seg_kx]: each group keeps its segments behind its own rows,
+ * or in row blocks of their own (ops.aspp_fwd_weights: offset = (block row - first column) * ldb); the caller vouches for the
+ * buffer behind every offset.  A workgroup walks `rectangle mask & column-tile mask`; chains then differ across the column tiles of
+ * one row tile, and the workgroups are dispatched longest chain first from a list kept with the plan's device table
+ * (glf_gemm_nt_seg_plan_cols).  Everything else -- operands, precisions, amax_c, colstats / colmax, the zero-page bound, the first
+ * launch of a plan allocating its table -- as documented for glf_gemm_params.nseg. */
+int glf_gemm_nt_seg_cols(const float* A, const float* B, float* C, const glf_gemm_params* p, const int32_t* seg_cols,
+                         const int64_t* seg_boff, glf_stream_t stream);
+/* Host-only plan of a glf_gemm_nt_seg_cols launch: glf_gemm_nt_seg_plan's results, plus col_masks[ceil(N / 128)] = the segments
+ * that contribute to each column tile, plus (order != NULL, room for order_cap >= *row_tiles * ceil(N / 128) entries) the dispatch
+ * list [workgroups][3] = (rectangle, row tile inside it, column tile) in blockIdx order: non-increasing chain length
+ * popcount(rectangle mask & column-tile mask) from one run of 16 entries to the next (inside a run, neighbouring pairs are dealt
+ * to the eight XCDs that blockIdx % 8 selects, the heaviest pair to the XCD given the least work so far; a workgroup weighs
+ * 1 + its chain length here, K / 32 + chain * seg_kx / 32 in the launcher: the same list when seg_kx == K).  A glf_gemm_nt launch
+ * with nseg > 0 and no column groups is dispatched from the same kind of list (full column-tile masks, groups of four) when it
+ * has at most 64 column tiles; results do not depend on the dispatch order. */
+int glf_gemm_nt_seg_plan_cols(int32_t n_img, int32_t h, int32_t w, int32_t nseg, const int32_t* seg, const int32_t* seg_cols, int32_t N,
+                              int32_t* regions, int32_t* n_regions, int64_t* row_tiles, uint32_t* col_masks, int32_t* order,
+                              int64_t order_cap);
 
 /* *out = max |x| over the [rows, cols] view with row stride ld (elements); out is a device float. */
 int glf_amax(const float* x, int64_t rows, int cols, int64_t ld, float* out, glf_stream_t stream);
