@@ -13,13 +13,13 @@
 //     one call, from uint8 or float32 volumes, by glf_prepare_frames' arithmetic (one shared per-pixel body).
 // HBM-bound byte / index work: one thread per output pixel, coalesced along x.
 #include "glf_common.h"
+#include "mask_predicates.h"
 #include <cstdint>
 
 namespace {
 
-__device__ __forceinline__ float sigmoid_d(float x) { return 1.0f / (1.0f + expf(-x)); }
-// THE binarisation of a logit (main.py:250, 385, 606): metrics, label maps and restored volumes all decide a pixel here
-__device__ __forceinline__ bool channel_on(float x) { return sigmoid_d(x) > 0.5f; }
+using glf::channel_on;                              // mask_predicates.h: the one binarisation of a logit
+using glf::target_on;
 
 // nearest-neighbour source index exactly as ATen's upsample_nearest (legacy 'nearest'): floor(dst * (in / out)) in
 // fp32, clamped to in - 1
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void overlap_nchw_kernel(const float* __restri
         const long long n = i / hw, p = i - n * hw;
         const long long o = (n * C + c) * hw + p;
         const bool pr = channel_on(x[o]);                     // main.py:250, 385
-        const bool gt = t[o] != 0.f;
+        const bool gt = target_on(t[o]);
         tp += pr && gt; fp += pr && !gt; fn += !pr && gt; tn += !pr && !gt;
     }
 #pragma unroll

@@ -94,6 +94,106 @@ def part_overlap_counts(logits: torch.Tensor, target: torch.Tensor) -> torch.Ten
     return counts
 
 
+def _percentile(percentile) -> int:
+    if int(percentile) != percentile or not 0 <= int(percentile) <= 100:
+        raise ValueError(f"contour metrics: the percentile is an integer 0..100 (got {percentile!r})")
+    return int(percentile)
+
+
+def contour_stats(logits: torch.Tensor, target: torch.Tensor, percentile: int = 95) -> Tuple[torch.Tensor, torch.Tensor]:
+    """What the contour metrics are made of, in one launch (glf_contour_distances; no reference counterpart): [N,C,H,W] logits and
+    targets -> (stats int64 [N,C,2,4] = (count, max_d2, d2_lo, d2_hi), sums float64 [N,C,2]) per frame, class channel and direction
+    (0: prediction -> target, 1: target -> prediction).  A mask's contour is its on pixels (sigmoid(logit) > 0.5, the predicate
+    part_overlap_counts counts with; target != 0) with a 4-neighbour that is off or outside the image; d2 is a contour pixel's exact
+    squared distance in pixels to the other contour, d2_lo / d2_hi the two order statistics that bracket the `percentile`, sums the
+    sum of sqrt(d2), bitwise reproducible.  An empty contour on either side: both directions keep their count, -1 and 0.0 elsewhere."""
+    logits, target = _contig(_chk(logits, "logits")), _contig(_chk(target, "target"))
+    if logits.shape != target.shape or logits.dim() != 4:
+        raise RuntimeError("contour_stats: [N,C,H,W] logits and targets of one shape expected")
+    pct = _percentile(percentile)
+    n, c, h, w = logits.shape
+    stats = torch.empty(n, c, 2, 4, dtype=torch.int64, device=logits.device)
+    sums = torch.empty(n, c, 2, dtype=torch.float64, device=logits.device)
+    check(lib.glf_contour_distances(_p(logits), _p(target), _p(stats), _p(sums), n, c, h, w, pct, _stream()), "contour_distances")
+    return stats, sums
+
+
+def contour_metrics(stats: torch.Tensor, sums: torch.Tensor, percentile: int = 95) -> Dict[str, torch.Tensor]:
+    """contour_stats' output -> [N,C] device tensors, without a host read: 'hd' = sqrt(max over directions of max_d2), 'hdp' = the
+    larger of the two directed percentiles P = sqrt(d2_lo) + frac * (sqrt(d2_hi) - sqrt(d2_lo)), frac = ((percentile * (count - 1))
+    % 100) / 100 (numpy's linear interpolation; percentile per direction, then the larger), 'assd' = (sums[0] + sums[1]) /
+    (count[0] + count[1]), all float64 and unspecified where the pair is not scored; and the bool masks 'scored' (both contours
+    non-empty), 'missed' (target only), 'spurious' (prediction only), 'absent' (neither): exactly one is true per pair."""
+    pct = _percentile(percentile)
+    if stats.dim() != 4 or tuple(stats.shape[2:]) != (2, 4) or stats.dtype != torch.int64 or sums.dtype != torch.float64 \
+            or tuple(sums.shape) != tuple(stats.shape[:3]):
+        raise RuntimeError("contour_metrics: stats int64 [N,C,2,4] and sums float64 [N,C,2] expected")
+    count = stats[..., 0]
+    has_pred, has_target = count[..., 0] > 0, count[..., 1] > 0
+    root = stats[..., 1:].clamp(min=0).double().sqrt()                    # [N,C,2,3]: max, lo, hi
+    frac = ((pct * (count - 1)) % 100).double() / 100.0
+    p = root[..., 1] + frac * (root[..., 2] - root[..., 1])
+    return {"hd": root[..., 0].amax(dim=-1), "hdp": p.amax(dim=-1), "assd": sums.sum(dim=-1) / count.sum(dim=-1).clamp(min=1).double(),
+            "scored": has_pred & has_target, "missed": has_target & ~has_pred, "spurious": has_pred & ~has_target,
+            "absent": ~has_pred & ~has_target}
+
+
+class ContourAccumulator:
+    """One view's contour sums over a pass: `total` [C,7] float64 on the device = (sum hd, sum hdp, sum assd, scored, missed, spurious,
+    absent) per class channel, over the (frame, channel) pairs added so far.  Everything is additive: `add` takes a clip, `+=`
+    another accumulator, one all_reduce of `total` combines ranks, and `report` (or `reports` for several views at once) is the
+    one host read at the end of a pass."""
+    KEYS = ("hd", "hd95", "assd", "scored", "missed", "spurious", "absent")
+
+    def __init__(self, channels: int = 5, device=None, percentile: int = 95):
+        self.percentile = _percentile(percentile)
+        self.total = torch.zeros(channels, 7, dtype=torch.float64, device=device)
+
+    def add(self, logits: torch.Tensor, target: torch.Tensor) -> "ContourAccumulator":
+        m = contour_metrics(*contour_stats(logits, target, self.percentile), self.percentile)
+        scored = m["scored"]
+        zero = torch.zeros((), dtype=torch.float64, device=scored.device)
+        cols = [torch.where(scored, m[k], zero).sum(dim=0) for k in ("hd", "hdp", "assd")]
+        cols += [m[k].sum(dim=0).double() for k in ("scored", "missed", "spurious", "absent")]
+        self.total += torch.stack(cols, dim=1)
+        return self
+
+    def __iadd__(self, other) -> "ContourAccumulator":
+        """acc += (logits, target) adds a clip; acc += another accumulator adds what it holds."""
+        if isinstance(other, ContourAccumulator):
+            self.total += other.total
+            return self
+        logits, target = other
+        return self.add(logits, target)
+
+    @staticmethod
+    def report_from_rows(rows: Sequence[Sequence[float]]) -> dict:
+        """[C][7] host numbers -> {'hd', 'hd95', 'assd': per-part means over the scored pairs (None without any), 'scored', 'missed',
+        'spurious', 'absent': per-part pair counts, 'mean': (hd, hd95, assd) over all scored pairs of all parts, or None}."""
+        out = {key: [row[i] / row[3] if row[3] > 0 else None for row in rows] for i, key in enumerate(ContourAccumulator.KEYS[:3])}
+        for i, key in enumerate(ContourAccumulator.KEYS[3:]):
+            out[key] = [int(round(row[3 + i])) for row in rows]
+        n = sum(row[3] for row in rows)
+        out["mean"] = tuple(sum(row[i] for row in rows) / n for i in range(3)) if n > 0 else None
+        return out
+
+    def report(self) -> dict:
+        return self.report_from_rows(self.total.tolist())
+
+    @staticmethod
+    def reports(accs: "Dict[str, ContourAccumulator]", reduce: bool = False) -> Dict[str, dict]:
+        """{view: accumulator} -> {view: report} with ONE collective (if `reduce` and several ranks run) and ONE host read for all views."""
+        views = list(accs)
+        if not views:
+            return {}
+        stacked = torch.stack([accs[v].total for v in views])
+        if reduce:
+            import torch.distributed as dist
+            if dist.is_initialized() and dist.get_world_size() > 1:
+                dist.all_reduce(stacked)
+        return {v: ContourAccumulator.report_from_rows(rows) for v, rows in zip(views, stacked.tolist())}
+
+
 def render_labels(logits: torch.Tensor, frames: Optional[torch.Tensor] = None, alpha: int = 255, palette=PALETTE):
     """The pictures of main.py:606-634 in one kernel (glf_render_labels).  logits [N,C,H,W] (C = 1..8, float32: predictions are
     fp32 under every precision; a 0/1 mask renders to the reference's `visual_gnd`) -> (labels uint8 [N,H,W], rgba uint8

@@ -188,6 +188,17 @@ class StepGraph:
         self.wtable = None
 
 
+def _contour_line(rep: dict) -> str:
+    """One printed line of a view's contour report (data.ContourAccumulator.report): pixels; '-' where no pair was scored."""
+    def fmt(x):
+        return "-" if x is None else f"{x:.3f}"
+    mean = rep["mean"] or (None, None, None)
+    return (f"contour (pixels) hd {fmt(mean[0])} hd95 {fmt(mean[1])} assd {fmt(mean[2])}; part hd " + " ".join(fmt(x) for x in rep["hd"])
+            + "; part hd95 " + " ".join(fmt(x) for x in rep["hd95"]) + "; part assd " + " ".join(fmt(x) for x in rep["assd"])
+            + "; pairs scored/missed/spurious/absent "
+            + " ".join(f"{a}/{b}/{c}/{d}" for a, b, c, d in zip(rep["scored"], rep["missed"], rep["spurious"], rep["absent"])))
+
+
 def _fold_bn_scope(fn):
     """Run a Trainer method with ops.set_fold_bn(True) / ops.set_fold_bn_s16(True) when config['train']['fold_bn'] /
     config['train']['fold_bn_s16'] ask for it; the previous values come back."""
@@ -216,6 +227,7 @@ class Trainer:
         if not torch.cuda.is_available():
             raise RuntimeError("glfusion_amd.engine.Trainer needs an MI355X: the HIP engine has no CPU fallback")
         self.print_val = tr.get("global_rank", 0) == 0                       # main.py:92
+        self.contour_metrics = bool(tr.get("contour_metrics", False))       # eval passes also report HD / HD95 / ASSD (not in the reference)
         # config['train']['precision'] (no reference counterpart): "f32" | "bf16x6" | "f16x3" | "f16" | "bf16" (16-bit activation storage,
         # BASELINE.json configs[2] / [4]); absent = whatever glfusion_amd.ops is set to
         if tr.get("precision"):
@@ -457,15 +469,19 @@ class Trainer:
 
     @torch.no_grad()
     @_fold_bn_scope
-    def eval(self, net_path: str = None, is_fuse: bool = True, raw_data: bool = True, patients=None):
+    def eval(self, net_path: str = None, is_fuse: bool = True, raw_data: bool = True, patients=None, on_clip=None):
         """main.py:417-543.  Per patient and view a raw clip volume goes through the data path (data.prepare_frames: the
         loader's resize / centre crop / part masks / 255 and the `[1,1,H,W,T] -> [T,1,H,W]` reshape of main.py:495-499),
         the model predicts all frames of the clip (the fused mask, or the backbone mask when is_fuse is False, main.py:
         504-506), BCE-sum losses accumulate per view (main.py:510-512) and the overlap counters accumulate over patients
         -- tp / fp / fn / tn are additive, so the reference's concatenation of every prediction (main.py:514-516) is not
         needed.  Returns {view: (pixel_acc, dice, precision, specificity, recall)} (main.py:519); the per-part Dice of
-        main.py:537-543 and the losses are left in `self.eval_report`."""
-        from .data import SyntheticPatients, part_overlap_counts
+        main.py:537-543 and the losses are left in `self.eval_report`.  With config['train']['contour_metrics'] the report also
+        holds 'contour' = {view: data.ContourAccumulator's report}: Hausdorff, 95th-percentile Hausdorff and average symmetric
+        surface distance in pixels, averaged per part and per view over the (frame, part) pairs where both contours exist, and the
+        counts of scored / missed / spurious / absent pairs; one launch per (patient, view), one collective and one host read per
+        pass.  on_clip(k, view, logits, masks), if given, sees the device tensors of each (patient, view) this rank scores."""
+        from .data import ContourAccumulator, SyntheticPatients, part_overlap_counts
         from . import data as _data
         if net_path and os.path.exists(net_path):
             self.model.load_state_dict(torch.load(net_path, map_location=self.device)["network"], strict=True)
@@ -475,6 +491,7 @@ class Trainer:
                                          int(self.config["train"].get("clip_length", 40)), device=self.device, seed=77)
         counts = {v: torch.zeros(5, 4, dtype=torch.int64, device=self.device) for v in self.test_view}
         loss4view = {v: 0.0 for v in self.test_view}
+        contour = {v: ContourAccumulator(5, self.device) for v in self.test_view} if self.contour_metrics else None
         import torch.distributed as dist
         world = dist.get_world_size() if dist.is_initialized() else 1
         rank = dist.get_rank() if dist.is_initialized() else 0
@@ -487,8 +504,12 @@ class Trainer:
             out = self._forward(imgs)
             pred = self._prediction(out, is_fuse)
             for v in self.test_view:
+                if on_clip is not None:
+                    on_clip(k, v, pred[v], masks[v])
                 counts[v] += part_overlap_counts(pred[v], masks[v])
                 loss4view[v] += float(ops.bce_with_logits_sum(pred[v], masks[v]))
+                if contour is not None:
+                    contour[v] += (pred[v], masks[v])
         result, part_dice = {}, {}
         if world > 1:
             lt = torch.tensor([loss4view[v] for v in self.test_view], dtype=torch.float64, device=self.device)
@@ -499,11 +520,15 @@ class Trainer:
             result[v] = ops.overlap_metrics_from_counts(per_part.sum(dim=0))
             part_dice[v] = [ops.overlap_metrics_from_counts(per_part[c])[1] for c in range(5)]
         self.eval_report = {"loss": loss4view, "part_dice": part_dice}
+        if contour is not None:
+            self.eval_report["contour"] = ContourAccumulator.reports(contour, reduce=True)
         if self.print_val:
             for v in self.test_view:
                 print(f"validation view {v}: loss {loss4view[v]:.4f} pixel-acc {result[v][0]:.4f} dice {result[v][1]:.4f} "
                       f"precision {result[v][2]:.4f} specificity {result[v][3]:.4f} recall {result[v][4]:.4f}; part dice "
                       + " ".join(f"{d:.4f}" for d in part_dice[v]))
+                if contour is not None:
+                    print(f"validation view {v}: " + _contour_line(self.eval_report["contour"][v]))
         return result
 
     @torch.no_grad()
@@ -577,7 +602,7 @@ class Trainer:
         loaded and scored, and the best validation epoch from `first_scored` on is reported (main.py:412-415: epochs 50+).
         `infos`: the reference loads ./infos/test_infos.npy (NIfTI paths, not shipped); default = synthetic volumes with the same ids.
         reduce: sum the overlap counters over ranks (every rank must then make this call); False for a call made by one rank alone."""
-        from .data import SegPAHDataset, synthetic_infos, part_overlap_counts
+        from .data import ContourAccumulator, SegPAHDataset, synthetic_infos, part_overlap_counts
         clip = 40 if raw_data else int(self.config["train"].get("clip_length", 40))                       # main.py:307-311
         if infos is None:
             infos = synthetic_infos(self.view_num, 10, clip, device="cpu", seed=91)
@@ -591,6 +616,7 @@ class Trainer:
             for name, per_view in sets.items():
                 counts = {v: torch.zeros(5, 4, dtype=torch.int64, device=self.device) for v in self.test_view}
                 loss4view = {v: 0.0 for v in self.test_view}
+                contour = {v: ContourAccumulator(5, self.device) for v in self.test_view} if self.contour_metrics else None
                 for i in range(len(per_view[self.view_num[0]])):
                     imgs, masks = {}, {}
                     for v in self.view_num:
@@ -607,7 +633,10 @@ class Trainer:
                     for v in self.test_view:
                         counts[v] += part_overlap_counts(pred[v], masks[v])
                         loss4view[v] += float(ops.bce_with_logits_sum(pred[v], masks[v]))
+                        if contour is not None:
+                            contour[v] += (pred[v], masks[v])
                 res = {}
+                contour_report = ContourAccumulator.reports(contour, reduce=reduce) if contour is not None else None
                 for v in self.test_view:
                     # reduce=False: this rank scored every clip itself (the per-epoch call from train(), rank 0 only): no collective
                     per_part = all_reduce_counts(counts[v]) if reduce else counts[v]
@@ -618,6 +647,10 @@ class Trainer:
                         print(f"------Validation Result . {name} for view{v} {tag}------ Loss : {loss4view[v]:.4f} Pixel Acc : {m[0]:.4f} "
                               f"Dice : {m[1]:.4f} Precision : {m[2]:.4f} Specificity : {m[3]:.4f} Recall : {m[4]:.4f}; part dice "
                               + " ".join(f"{d:.4f}" for d in res[v]["part_dice"]))
+                    if contour_report is not None:
+                        res[v]["contour"] = contour_report[v]
+                        if self.print_val:
+                            print(f"------Validation Result . {name} for view{v} {tag}------ " + _contour_line(contour_report[v]))
                 report[name] = res
             val = report["Inner-val"]
             report["val_dice"] = sum(val[v]["metrics"][1] for v in self.test_view) / max(len(self.test_view), 1)

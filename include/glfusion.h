@@ -1086,6 +1086,30 @@ typedef struct {
 } glf_frame_src;
 int glf_frame_label_sums(const void* lab, int dtype, int H0, int W0, int T, int64_t* sums, glf_stream_t s);
 int glf_prepare_batch(const glf_frame_src* srcs, int n, float* out_img, float* out_mask, int out_h, int out_w, glf_stream_t s);
+/* ---------------------------------------------------------------------------------------
+ * Contour metrics (no reference counterpart; main.py:800-815 counts overlap only): what Hausdorff distance, its percentile
+ * form and the average symmetric surface distance are made of, per (frame, class channel, direction), in pixels.
+ * logits, target: [n][c][h][w] fp32.  A prediction pixel is ON by glf_overlap_counts_nchw's device predicate
+ * (sigmoid(logit) > 0.5: logit 0.0, -0.0, -inf and NaN are off, +inf is on), a target pixel when target != 0.
+ * The CONTOUR of a mask is its on pixels with at least one 4-neighbour (up, down, left, right) that is off or outside the
+ * image (= M xor binary_erosion(M) with the cross element and border value 0).  Direction 0 gives every contour pixel p of the
+ * prediction d2(p) = min over contour pixels q of the target of (py - qy)^2 + (px - qx)^2; direction 1 is target -> prediction.
+ * stats [n][c][2][4] int64 = (count, max_d2, d2_lo, d2_hi): count = contour pixels of the direction's source mask; d2_lo, d2_hi =
+ * the ascending-sorted d2 at ranks lo = (pct * (count - 1)) / 100 and hi = lo + ((pct * (count - 1)) % 100 != 0).  All exact.
+ * sums [n][c][2] double = sum of sqrt((double)d2) over the source contour, added in a fixed order: bitwise reproducible.
+ * When either contour of a pair is empty both directions report their own count, max_d2 = d2_lo = d2_hi = -1 and sum 0.0.
+ * Every element of stats and sums is written by the call (no pre-zeroing by the caller).
+ * One launch, one workgroup per (frame, channel, direction), all intermediate state in LDS (bitmaps, a separable integer
+ * distance transform by column strips, two histogram passes for the ranks): no workspace, allocation, synchronisation or state.
+ * h, w <= GLF_CONTOUR_MAX_DIM (so that d2 < 2^17 and a plane's bitmaps fit LDS); the work per plane is O(h * w * h) at most,
+ * whatever the masks are.
+ * Checked before any HIP runtime call, in this order: GLF_ERR_NULL (any of the four pointers; wins over everything), then
+ * GLF_ERR_BAD_SHAPE (n, c, h, w < 1, pct outside 0..100, 2 * n * c > 2^31 - 1), then GLF_ERR_UNSUPPORTED (h or w above
+ * GLF_CONTOUR_MAX_DIM).
+ * ------------------------------------------------------------------------------------- */
+#define GLF_CONTOUR_MAX_DIM 256
+int glf_contour_distances(const float* logits, const float* target, int64_t* stats, double* sums, int n, int c, int h, int w,
+                          int pct, glf_stream_t s);
 /* Zero `bytes` bytes at p on the stream (accumulation targets: atomically summed gradients, column statistics, maxima). */
 int glf_zero(void* p, int64_t bytes, glf_stream_t s);
 

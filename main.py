@@ -56,6 +56,9 @@ def main(rank, config):
     parser.add_argument("--train-list", type=str, default=None, metavar="NPY",
                         help="array of the patient ids to train on, the reference's data_list/train_list.npy "
                              "(config['train']['train_list']); default: the datasets' own 80 %% split")
+    parser.add_argument("--contour-metrics", action="store_true",
+                        help="evaluation also reports Hausdorff distance, its 95th percentile and the average symmetric surface "
+                             "distance per view and part, in pixels (config['train']['contour_metrics']); default: off")
     args = parser.parse_args()
     if args.infos:
         config["train"]["infos"] = args.infos
@@ -76,6 +79,8 @@ def main(rank, config):
         config["train"]["is_load"] = config["train"]["save_optimizer"] = True
     if args.precision:
         config["train"]["precision"] = args.precision
+    if args.contour_metrics:
+        config["train"]["contour_metrics"] = True
     if args.fold_bn:
         config["train"]["fold_bn"] = True
     if args.fold_bn_s16:
