@@ -1,11 +1,12 @@
 """The launch plan of a convolution pass: which taps can reach the map, whether the pass runs dense, as per-tap rectangles or in
 region mode, how many reduction slices the weight gradient is cut into, whether the output must be zero-filled first and whether
 fused column statistics can be honoured.  ONE pure function, plan(), for every pass, precision and storage; the slice-count
-rules of the TN kernels live beside it.  The 16-bit-storage wrappers (ops16) ask it; the fp32-storage wrappers of ops still
-spell the same rules out themselves (ops.tap_mask / rect_fraction / region_mode / wgrad_split) and are to move here.  Pure Python
-(no torch, no library): glf_conv2d_plan of csrc/conv_api.hip is the same policy for C hosts (fp32 storage, no `keep`), and
-tests/test_abi_cpu.py holds the C plan to this planner field by field and to the rules in ops; tests/test_conv_plan_cpu.py holds
-the planner to a table recorded from the rules in ops and ops16."""
+rules of the TN kernels live beside it.  Every wrapper asks it: the 16-bit-storage ones of ops16 and the fp32-storage ones of ops
+(Conv2dFn, the fallback loops of AsppCentreFn, conv_stats_fusable, fold_plan).  ops holds none of the rules; it re-exports
+tap_mask, rect_fraction, RECT_THRESHOLD and CENTRE_TAP as these very objects.  Pure Python (no torch, no library):
+glf_conv2d_plan of csrc/conv_api.hip is the same policy for C hosts (fp32 storage, no `keep`), and tests/test_abi_cpu.py holds the
+C plan to this planner field by field and to the rules restated one by one; tests/test_conv_plan_cpu.py holds the planner to a
+table recorded from the rules as ops and ops16 spelled them before it existed."""
 from __future__ import annotations
 
 from functools import lru_cache

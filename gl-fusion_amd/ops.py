@@ -19,7 +19,9 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
+from . import conv_plan
 from ._lib import GemmEpilogue, GemmParams, SEG_MAX, TN_OIHW_MAX_TAPS, WeightJob, WJ_AMAX, WJ_COPY, WJ_PACK, WJ_PASSES, WJ_PASS_OF, WJ_TAP_MAJOR, WJ_TAP_MAJOR_T, WJ_TRANSPOSE, WJ_ZERO, check, lib
+from .conv_plan import CENTRE_TAP, RECT_THRESHOLD, rect_fraction, tap_mask          # re-exported: the same objects, the rules live in conv_plan
 
 
 # ----------------------------------------------------------------------------------------
@@ -121,41 +123,6 @@ def from_nhwc(y: torch.Tensor) -> torch.Tensor:
 # ----------------------------------------------------------------------------------------
 # contraction front-end
 # ----------------------------------------------------------------------------------------
-def _axis_valid_fwd(hd: int, hs: int, k: int, stride: int, pad: int, dil: int) -> List[bool]:
-    return [any(0 <= y * stride - pad + t * dil < hs for y in range(hd)) for t in range(k)]
-
-
-def _axis_valid_bwd(hd: int, hs: int, k: int, stride: int, pad: int, dil: int) -> List[bool]:
-    out = []
-    for t in range(k):
-        ok = False
-        for y in range(hd):
-            v = y + pad - t * dil
-            if v >= 0 and v % stride == 0 and v // stride < hs:
-                ok = True
-                break
-        out.append(ok)
-    return out
-
-
-_mask_cache = {}
-
-
-def tap_mask(gather: int, hd: int, wd: int, hs: int, ws: int, kh: int, kw: int, stride: int, pad: int, dil: int) -> int:
-    key = (gather, hd, wd, hs, ws, kh, kw, stride, pad, dil)
-    m = _mask_cache.get(key)
-    if m is None:
-        f = _axis_valid_fwd if gather == 1 else _axis_valid_bwd
-        vy, vx = f(hd, hs, kh, stride, pad, dil), f(wd, ws, kw, stride, pad, dil)
-        m = 0
-        for ky in range(kh):
-            for kx in range(kw):
-                if vy[ky] and vx[kx]:
-                    m |= 1 << (ky * kw + kx)
-        _mask_cache[key] = m
-    return m
-
-
 # contraction precision of the calls this module issues (index into PRECISIONS); passed PER CALL through
 # glf_gemm_params.precision, so nothing process-wide is touched in the library
 _PREC = [0]
@@ -599,27 +566,7 @@ def set_amax(t: torch.Tensor, amax: Optional[torch.Tensor]) -> None:
 
 
 def _tn_split(rows: int, m: int, n: int, ntaps: int, batch: int = 1) -> int:
-    """Reduction slices for the TN (wgrad) kernel: fill ~4 waves of 512 resident workgroups,
-    keep >= 16 K-tiles (512 rows) per slice."""
-    tiles = ((m + 127) // 128) * ((n + 127) // 128) * max(ntaps, 1) * batch
-    # workgroups to aim for: 2048 128x128 tiles on the fp32 / bf16x6 kernels (two per CU); the f16x3 kernel has 256-wide
-    # tiles, one workgroup per CU, and shares the chip with other streams: 1024 measured best (293.5 vs 299.2 ms / step)
-    target = 1024 if _PREC[0] >= 2 else 2048
-    want = max(1, (target + tiles - 1) // tiles)
-    cap = max(1, rows // 512)
-    hi = 65535 // max(batch, 1)
-    if _PREC[0] >= 2:
-        # among the slice counts around the target, the one whose workgroups (256-wide tiles, one per CU) fill whole
-        # rounds of the 256 CUs best
-        wg = ((m + 255) // 256) * ((n + 127) // 128) * max(ntaps, 1) * batch
-        best, best_score = want, -1.0
-        for s in range(max(1, want // 2), max(1, min(want * 2, cap, hi)) + 1):
-            b = wg * s
-            score = b / (((b + 255) // 256) * 256.0) - 0.004 * s
-            if score > best_score:
-                best, best_score = s, score
-        want = best
-    return int(max(1, min(want, cap, hi)))
+    return conv_plan.tn_split(rows, m, n, ntaps, batch, _PREC[0])
 
 
 # ----------------------------------------------------------------------------------------
@@ -660,21 +607,6 @@ def grad_out(param: Optional[torch.Tensor], shape, device) -> torch.Tensor:
                 s[3] = True
                 return s[1][s[2]:s[2] + n].view(tuple(shape))
     return torch.empty(tuple(shape), dtype=torch.float32, device=device)
-
-
-def wgrad_split(rows_o: int, frac: float, cout: int, cin: int, ntap: int, rect: bool) -> int:
-    """Reduction slices of a convolution's weight gradient (mirror of conv_api.hip's plan).  A slice is ceil(rows / split) rows
-    of EVERY tap's reduction; in rect mode (ASPP: most taps reach only a small rectangle of the map) a tap uses as many slices
-    as its rectangle is long, so the count is scaled up by the in-range fraction to keep the launch at its target size -- and
-    all workgroups reduce the same number of rows (before: every tap was cut into `split` pieces of its own rectangle, the
-    centre tap's workgroups ran 3 x (rate 12) to 50 x (rate 24) longer than the corner taps')."""
-    split = _tn_split(max(512, int(rows_o * frac)) if rect else rows_o, cout, cin, ntap)
-    if rect:
-        # (measured on the 2048 -> 256 ASPP convs, profiles/r03_aspp_wgrad_probe.txt: half of split / frac is the sweet spot --
-        # rate 12: 7 slices 1.01 ms, 14 slices 1.22 ms; rate 24: 19 slices 0.48 ms, 39 slices 0.50 ms, 78 slices 0.57 ms)
-        s2 = max(split, int(split / (2.0 * max(frac, 0.02)) + 0.999))
-        split = max(1, min(s2, max(1, rows_o // 512), 65535))
-    return split
 
 
 _ones_cache = {}
@@ -915,61 +847,6 @@ def tap_major(weight: torch.Tensor) -> torch.Tensor:
 # ----------------------------------------------------------------------------------------
 # conv2d (NHWC, implicit GEMM)
 # ----------------------------------------------------------------------------------------
-_rect_cache = {}
-
-
-def rect_fraction(gather: int, hd: int, wd: int, hs: int, ws: int, kh: int, kw: int, pad: int, dil: int, mask: int) -> float:
-    """sum over kept taps of (in-range rectangle area) / (kept taps x full area), stride 1 (mirrors tap_rect
-    in gemm_f32.hip).  Small values = most tap work is padding => the tap-parallel rect mode pays."""
-    key = (gather, hd, wd, hs, ws, kh, kw, pad, dil, mask)
-    f = _rect_cache.get(key)
-    if f is None:
-        tot, n = 0, 0
-        for t in range(kh * kw):
-            if not (mask >> t) & 1:
-                continue
-            ky, kx = divmod(t, kw)
-            oy = pad - ky * dil if gather == 1 else ky * dil - pad
-            ox = pad - kx * dil if gather == 1 else kx * dil - pad
-            rh = max(0, min(hs + oy, hd) - max(oy, 0))
-            rw = max(0, min(ws + ox, wd) - max(ox, 0))
-            tot += rh * rw
-            n += 1
-        f = tot / max(1, n * hd * wd)
-        _rect_cache[key] = f
-    return f
-
-
-# use rect mode when less than this fraction of the kept taps' work is in range (per conv pass)
-# The rectangle GEMMs sum their taps with float atomics; dgrad writes the widest outputs (Cin = 2048 columns for
-# ASPP) over the shortest reductions (Cout = 256), so once the MFMA work is cheap (f16x3) the atomics cost more
-# than the padding work they avoid unless most of it is padding: measured on the ASPP shapes, rate 12 (51 % in
-# range) is faster dense, rate 24 (18 %) faster as rectangles.
-RECT_THRESHOLD = {"fwd": 0.8, "dgrad": 0.8, "wgrad": 0.8, "dgrad_f16x3": 0.35, "region": 0.8}
-
-
-def region_mode(taps: int, kh: int, stride: int, pad: int, dil: int, h: int, w: int, ho: int, wo: int, k: int, frac: float) -> bool:
-    """rect = 2 of glf_gemm_nt (f16x3 kernels): a 3x3 stride-1 "same" conv (pad == dil) is cut into <= 9 rectangles of
-    output pixels with a constant set of in-range taps -- no padding work, no atomics, no zero fill.  Used for the
-    dgrad of the ASPP rate-12 / 24 convs (2048-column outputs): 14.4 -> 11.2 ms and 7.6 -> 6.7 ms per step against
-    dense / per-tap rectangles with atomics.  Measured NOT to pay elsewhere: the forward of the same convs (256-column
-    outputs, 392 workgroups) is faster as per-tap rectangles -- the regions' blocks are fewer and of uneven length
-    (4 / 6 / 9 taps) -- and for dilations 1-4 the 5-18 % of padding work saved is less than the extra partial tiles
-    and the per-element pixel arithmetic of the epilogue cost."""
-    return (_PREC[0] >= 2 and taps == 9 and kh == 3 and stride == 1 and pad == dil and h == ho and w == wo
-            and k % 32 == 0 and frac < RECT_THRESHOLD["region"])
-
-
-def _rect_thr(which: str) -> float:
-    if which == "dgrad" and _PREC[0] >= 2:
-        return RECT_THRESHOLD["dgrad_f16x3"]
-    return RECT_THRESHOLD[which]
-
-
-def _conv_out(h: int, k: int, stride: int, pad: int, dil: int) -> int:
-    return (h + 2 * pad - dil * (k - 1) - 1) // stride + 1
-
-
 def tn_oihw_ok(cin: int, taps: int, dw: torch.Tensor) -> bool:
     """True when glf_gemm_tn's second stage can store the parameter-shaped gradient `dw` itself (glf_gemm_params.c_oihw): a
     multi-tap kernel of at most TN_OIHW_MAX_TAPS taps, Cin % 4 == 0 and a 16-byte aligned destination (a bucket slot may start
@@ -977,21 +854,14 @@ def tn_oihw_ok(cin: int, taps: int, dw: torch.Tensor) -> bool:
     return 1 < taps <= TN_OIHW_MAX_TAPS and cin % 4 == 0 and dw.data_ptr() % 16 == 0 and dw.is_contiguous()
 
 
-def _conv_wgrad(weight, wshape, x, x_packed, da, lda: int, pa: bool, am_dy, cfg, mask: int, foreign=None, out=None):
-    """The weight gradient of a convolution (Conv2dFn's cfg) from its output gradient `da` (row stride lda; pa: a packed pre-split
-    image scaled by am_dy) over the taps of `mask`: the parameter-shaped gradient (in its all-reduce bucket slot where one is
-    registered).  Taps outside `mask` receive zeros, except foreign = (tap, src [Cout][Cin], row stride): that tap, not in
-    `mask`, is copied from src.  A multi-tap gradient is stored in parameter layout by the reduction itself (tn_oihw_ok): no
-    tap-major intermediate, no zero fill, no re-layout pass; an empty `mask` then launches that store alone.
+def _conv_wgrad(weight, wshape, x, x_packed, da, lda: int, pa: bool, am_dy, pl, foreign=None, out=None):
+    """The weight gradient of a convolution from its output gradient `da` (row stride lda; pa: a packed pre-split image scaled by
+    am_dy) as pl = conv_plan.plan("wgrad", ...) lays it out: the parameter-shaped gradient (in its all-reduce bucket slot where
+    one is registered).  Taps outside pl.mask receive zeros, except foreign = (tap, src [Cout][Cin], row stride): that tap, not in
+    the mask, is copied from src.  A multi-tap gradient is stored in parameter layout by the reduction itself (tn_oihw_ok): no
+    tap-major intermediate, no zero fill, no re-layout pass; an empty mask then launches that store alone.
     out: the destination the caller already took with grad_out()."""
-    n, h, w, cin, cout, kh, kw, ho, wo, stride, pad, dil, plain = cfg[:13]
-    taps, rows_o = kh * kw, n * ho * wo
-    ntap = bin(mask).count("1")
-    rect = (not plain and taps > 1 and stride == 1 and ntap > 1
-            and rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) < _rect_thr("wgrad"))
-    frac = rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) if rect else 1.0
-    split = wgrad_split(rows_o, frac, cout, cin, ntap, rect) if ntap else 1
-    full = mask == (1 << taps) - 1
+    cout, cin, taps, full = pl.M, pl.N, pl.taps, not pl.zero_fill
     dw = (out if out is not None else grad_out(weight, wshape, x.device)) if taps > 1 else None
     fused = taps > 1 and tn_oihw_ok(cin, taps, dw)
     if fused:
@@ -1003,11 +873,10 @@ def _conv_wgrad(weight, wshape, x, x_packed, da, lda: int, pa: bool, am_dy, cfg,
     ok = tn_presplit_ok(cout, cin, lda, cin)
     am_x = x_packed[1] if x_packed is not None else amax_of(x)
     xb, pb = pick(x, x_packed[0] if x_packed is not None else None, ok)        # x: the image the forward made, if any
-    if ntap or fused:
-        gemm("tn", da, xb, dwt, M=cout, N=cin, K=rows_o, lda=lda, ldb=cin, ldc=cin, taps=taps, mask=mask,
-             tap_stride_b=cout * cin, gather=0 if plain else 1,
-             geo=None if plain else (n, h, w, ho, wo, kh, kw, stride, pad, dil), split=split, rect=rect,
-             amax_a=am_dy, amax_b=am_x, a_packed=pa, b_packed=pb, oihw=fused, foreign=foreign if fused else None)
+    if pl.kept or fused:
+        gemm("tn", da, xb, dwt, M=cout, N=cin, K=pl.K, lda=lda, ldb=cin, ldc=cin, taps=taps, mask=pl.mask, tap_stride_b=cout * cin,
+             gather=pl.gather, geo=pl.geo, split=pl.split, rect=pl.rect, amax_a=am_dy, amax_b=am_x, a_packed=pa, b_packed=pb,
+             oihw=fused, foreign=foreign if fused else None)
     if fused:
         return dw
     if taps == 1:
@@ -1029,29 +898,25 @@ class Conv2dFn(Function):
         cout, cin_w, kh, kw = weight.shape
         if cin_w != cin:
             raise RuntimeError(f"conv2d: input has {cin} channels, weight expects {cin_w}")
-        ho, wo = _conv_out(h, kh, stride, pad, dil), _conv_out(w, kw, stride, pad, dil)
+        geom = (n, h, w, cin, cout, kh, kw, stride, pad, dil)
+        pl = conv_plan.plan("fwd", geom, _PREC[0], bias=bias is not None)
+        ho, wo, taps, plain, mask, rect = pl.ho, pl.wo, pl.taps, pl.plain, pl.mask, pl.rect
         if ho <= 0 or wo <= 0:
             raise RuntimeError("conv2d: empty output")
-        taps = kh * kw
         wt = tap_major(weight)
         y = torch.empty(n, ho, wo, cout, dtype=torch.float32, device=x.device)
-        plain = taps == 1 and stride == 1 and pad == 0
-        geo = (n, h, w, ho, wo, kh, kw, stride, pad, dil)
-        mask = 1 if plain else tap_mask(1, ho, wo, h, w, kh, kw, stride, pad, dil)
-        rect = (not plain and taps > 1 and stride == 1 and bias is None and bin(mask).count("1") > 1
-                and rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) < _rect_thr("fwd"))
-        if rect:
+        if pl.zero_fill:
             zero_(y)
             if colstats is not None:
                 raise RuntimeError("conv2d: fused column statistics are not available for a conv evaluated as per-tap rectangles")
         am_w, am_x = amax_of(weight), amax_of(x)
         x_pk = packed_only(x)                # the producing BatchNorm wrote the activation as a packed image (no fp32 form exists)
         # <= 64 output rows (the ASPP pooled branch: one row per frame): glf_gemm_nt's skinny kernel takes plain fp32 operands
-        skinny = plain and n * ho * wo <= 64 and cout >= 64 and cin % 16 == 0 and not x_pk and colstats is None
+        skinny = plain and pl.M <= 64 and cout >= 64 and cin % 16 == 0 and not x_pk and colstats is None
         ok = nt_presplit_ok(cin, cin, cin) and not skinny
         if x_pk and not (ok and am_x is not None and takes_packed_input(weight)):
             raise RuntimeError("glfusion_amd: a packed-only activation reached a convolution that cannot consume it")
-        ok_x = ok and (cout * bin(mask).count("1") >= PRESPLIT_MIN_COLS or packed_hit(x, am_x) is not None)
+        ok_x = ok and (cout * pl.kept >= PRESPLIT_MIN_COLS or packed_hit(x, am_x) is not None)
         xa, pa = (x, True) if x_pk else pick(x, act_packed(x, am_x) if ok_x else None, ok_x)
         wb, pb = pick(wt, weight_packed(wt, weight, "w", am_w) if ok else None, ok)
         # exact fp32 (the strict-precision leg): per-tap rectangles ONE TAP PER LAUNCH.  In one launch the taps of an output pixel meet in
@@ -1062,69 +927,60 @@ class Conv2dFn(Function):
         # 9 K-long chain and moved the train-mode logits past 1e-4).
         masks = [1 << t_ for t_ in range(taps) if (mask >> t_) & 1] if (rect and _PREC[0] == 0) else [mask]
         for mk in masks:
-            gemm("nt", xa, wb, y, M=n * ho * wo, N=cout, K=cin, lda=cin, ldb=cin, ldc=cout, bias=bias,
-                 taps=taps, mask=mk, tap_stride_b=cout * cin, gather=0 if plain else 1, geo=None if plain else geo, rect=rect,
+            gemm("nt", xa, wb, y, M=pl.M, N=cout, K=cin, lda=cin, ldb=cin, ldc=cout, bias=bias,
+                 taps=taps, mask=mk, tap_stride_b=cout * cin, gather=pl.gather, geo=pl.geo, rect=rect,
                  amax_a=am_x, amax_b=am_w, colstats=colstats, colmax=getattr(colstats, "_glf_colmax", None), a_packed=pa, b_packed=pb)
         ctx.save_for_backward(x, wt)
         ctx.x_packed = (xa, am_x) if (pa and (x_pk or packed_hit(x, am_x) is not None)) else None      # retained: the weight gradient reads the same image
         ctx.weight_ref = weight            # for the cached [tap][Cin][Cout] layout of the split-bf16 dgrad
-        ctx.cfg = (n, h, w, cin, cout, kh, kw, ho, wo, stride, pad, dil, plain, bias is not None, tuple(weight.shape))
+        ctx.cfg = (geom, bias is not None, tuple(weight.shape))
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
         x, wt = ctx.saved_tensors
-        n, h, w, cin, cout, kh, kw, ho, wo, stride, pad, dil, plain, has_bias, wshape = ctx.cfg
+        geom, has_bias, wshape = ctx.cfg
+        cin, cout = geom[3], geom[4]
         dy = _contig(dy)
-        taps = kh * kw
-        rows_o = n * ho * wo
         dx = dw = db = None
         am_dy, am_w = amax_of(dy), amax_of(ctx.weight_ref)
         dy_pk = packed_only(dy)              # BatchNorm backward wrote the gradient as a packed pre-split image (no fp32 form exists)
         if dy_pk and (has_bias or am_dy is None or not (split_mode() and cout % 32 == 0)):
             raise RuntimeError("glfusion_amd: a packed-only gradient reached a convolution that cannot consume it")
         def dgrad():
-            mask = 1 if plain else tap_mask(2, h, w, ho, wo, kh, kw, stride, pad, dil)
-            if mask == 0:
+            pl = conv_plan.plan("dgrad", geom, _PREC[0])
+            if pl.mask == 0:
                 return zeros(x.shape, device=x.device)
-            frac = 1.0 if plain or stride != 1 else rect_fraction(2, h, w, ho, wo, kh, kw, pad, dil, mask)
-            if not plain and bin(mask).count("1") > 1 and region_mode(taps, kh, stride, pad, dil, ho, wo, h, w, cout, frac):
-                rect = 2
-            else:
-                rect = int(not plain and taps > 1 and stride == 1 and bin(mask).count("1") > 1 and frac < _rect_thr("dgrad"))
-            dx = zeros(x.shape, device=x.device) if rect == 1 else torch.empty_like(x)
+            dx = zeros(x.shape, device=x.device) if pl.zero_fill else torch.empty_like(x)
             if split_mode() and cout % 32 == 0:
                 # dgrad as NT on the split-bf16 kernels: B_tap[n = ci][k = co]
                 wT = tap_major_T(ctx.weight_ref)
                 ok = nt_presplit_ok(cout, cout, cout)
-                ok_dy = ok and cin * bin(mask).count("1") >= PRESPLIT_MIN_COLS
+                ok_dy = ok and cin * pl.kept >= PRESPLIT_MIN_COLS
                 da, pa = (dy, True) if dy_pk else pick(dy, act_packed(dy, am_dy, True) if ok_dy else None, ok_dy)
                 wb, pb = pick(wT, weight_packed(wT, ctx.weight_ref, "wT", am_w) if ok else None, ok)
-                gemm("nt", da, wb, dx, M=n * h * w, N=cin, K=cout, lda=cout, ldb=cout, ldc=cin,
-                     taps=taps, mask=mask, tap_stride_b=cout * cin, gather=0 if plain else 2,
-                     geo=None if plain else (n, ho, wo, h, w, kh, kw, stride, pad, dil), rect=rect,
-                     amax_a=am_dy, amax_b=am_w, a_packed=pa, b_packed=pb)
+                gemm("nt", da, wb, dx, M=pl.M, N=cin, K=cout, lda=cout, ldb=cout, ldc=cin, taps=pl.taps, mask=pl.mask,
+                     tap_stride_b=cout * cin, gather=pl.gather, geo=pl.geo, rect=pl.rect, amax_a=am_dy, amax_b=am_w, a_packed=pa, b_packed=pb)
             else:
-                gemm("nn", dy, wt, dx, M=n * h * w, N=cin, K=cout, lda=cout, ldb=cin, ldc=cin, taps=taps, mask=mask,
-                     tap_stride_b=cout * cin, gather=0 if plain else 2,
-                     geo=None if plain else (n, ho, wo, h, w, kh, kw, stride, pad, dil), rect=rect)
+                gemm("nn", dy, wt, dx, M=pl.M, N=cin, K=cout, lda=cout, ldb=cin, ldc=cin, taps=pl.taps, mask=pl.mask,
+                     tap_stride_b=cout * cin, gather=pl.gather, geo=pl.geo, rect=pl.rect)
             return dx
 
         def wgrad():
+            pl = conv_plan.plan("wgrad", geom, _PREC[0])
             ok = tn_presplit_ok(cout, cin, cout, cin)
-            mask = 1 if plain else tap_mask(1, ho, wo, h, w, kh, kw, stride, pad, dil)
             # dy: the image dgrad made (or one worth making for this kernel alone)
-            ok_dy = ok and (packed_hit(dy, am_dy) is not None or cin * bin(mask).count("1") >= PRESPLIT_MIN_COLS)
+            ok_dy = ok and (packed_hit(dy, am_dy) is not None or cin * pl.kept >= PRESPLIT_MIN_COLS)
             da, pa = (dy, True) if dy_pk else pick(dy, act_packed(dy, am_dy, True) if ok_dy else None, ok_dy)
-            return _conv_wgrad(ctx.weight_ref, wshape, x, ctx.x_packed, da, cout, pa, am_dy, ctx.cfg, mask)
+            return _conv_wgrad(ctx.weight_ref, wshape, x, ctx.x_packed, da, cout, pa, am_dy, pl)
 
         if ctx.needs_input_grad[0]:
             dx = dgrad()
         if ctx.needs_input_grad[1]:
             dw = wgrad()
         if has_bias and ctx.needs_input_grad[2]:
-            db = colsum(dy, rows_o, cout)
+            db = colsum(dy, dy.numel() // cout, cout)
         return dx, dw, db, None, None, None, None
 
 
@@ -1136,25 +992,14 @@ def conv2d(x, weight, bias=None, stride: int = 1, pad: int = 0, dil: int = 1, co
 
 
 def conv_stats_fusable(weight, stride: int, pad: int, dil: int, h: int, w: int, dtype=None) -> bool:
-    """True when conv2d(..., colstats=) is honoured: f16x3 kernels (Cin % 32 == 0, Cout % 4 == 0) and the conv is not
-    one that runs as per-tap rectangles with atomics (ASPP rate 12 / 24 forward)."""
-    if _S16[0]:                          # the 16-bit kernels always honour colstats (region mode stores every element once)
-        return dtype == torch.bfloat16 and weight.shape[1] % 64 == 0 and weight.shape[0] % 64 == 0
-    if _PREC[0] < 2:
+    """True when conv2d(..., colstats=) is honoured: the forward plan's colstats_ok (f16x3 kernels, Cin % 32 == 0, Cout % 4 == 0, not
+    a conv that runs as per-tap rectangles with atomics -- ASPP rate 12 / 24; 16-bit storage: Cin % 64 == 0 and Cout % 64 == 0)
+    for a non-empty output and, under 16-bit storage, a bf16 input."""
+    if _S16[0] and dtype != torch.bfloat16:
         return False
     cout, cin, kh, kw = weight.shape
-    if cin % 32 != 0 or cout % 4 != 0:
-        return False
-    taps = kh * kw
-    if taps == 1 and stride == 1 and pad == 0:
-        return True
-    ho, wo = _conv_out(h, kh, stride, pad, dil), _conv_out(w, kw, stride, pad, dil)
-    if ho <= 0 or wo <= 0:
-        return False
-    mask = tap_mask(1, ho, wo, h, w, kh, kw, stride, pad, dil)
-    rect = (taps > 1 and stride == 1 and bin(mask).count("1") > 1
-            and rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) < _rect_thr("fwd"))
-    return not rect
+    pl = conv_plan.plan("fwd", (1, h, w, cin, cout, kh, kw, stride, pad, dil), conv_plan.S16 if _S16[0] else _PREC[0])
+    return pl.colstats_ok and pl.ho > 0 and pl.wo > 0
 
 
 # ----------------------------------------------------------------------------------------
@@ -1162,13 +1007,13 @@ def conv_stats_fusable(weight, stride: int, pad: int, dil: int, h: int, w: int, 
 # ----------------------------------------------------------------------------------------
 # The 1x1 branch and the centre taps of the 3x3 "same" branches (pad == dil: the centre tap is in range for every pixel) are
 # full-map products over the same input.  Stacked, they are one plain launch with N = k Cout forward and one with K = k Cout in
-# dgrad, at the shapes the big projections run at; the off-centre taps of a branch keep the launch they use today and ADD
-# into what the stacked launch stored.  The four BatchNorm backward passes write their gradients as column slices of one
-# packed image under one scale (_GradGroup), and the head's input gradient is one tensor where there were four plus a sum.
+# dgrad, at the shapes the big projections run at; the off-centre taps of a branch keep the launch the branch would use alone
+# (conv_plan.plan(..., keep=~CENTRE_TAP)) and ADD into what the stacked launch stored.  The four BatchNorm backward passes write
+# their gradients as column slices of one packed image under one scale (_GradGroup), and the head's input gradient is one tensor
+# where there were four plus a sum.
 ASPP_CENTRE = os.environ.get("GLF_ASPP_CENTRE", "1") != "0"
 # the centre taps' WEIGHT gradients as one stacked contraction too (0: one contraction per branch, centre tap included)
 ASPP_CENTRE_WGRAD = os.environ.get("GLF_ASPP_CENTRE_WGRAD", "1") != "0"
-CENTRE_TAP = 1 << 4                    # of a 3x3 kernel
 _centre_cache = {}
 
 
@@ -1267,7 +1112,8 @@ def aspp_dgrad_weights(weights, segs) -> torch.Tensor:
 
 
 def _aspp_dgrad_one(G, am_g, weights, dils, dx, slot, n: int, h: int, w: int, cin: int, cout: int) -> bool:
-    """dx = G Wd^T in one segmented launch; False when this head does not take that route (the caller runs today's launches)."""
+    """dx = G Wd^T in one segmented launch; False when this head does not take that route (the caller runs the stacked and the
+    per-branch launches)."""
     k = len(weights)
     ldu = k * cout
     segs = aspp_dgrad_segments(dils, h, w, cout)
@@ -1328,8 +1174,8 @@ def aspp_fwd_cols(segs, k: int, cout: int, cin: int):
 
 def _aspp_fwd_one(x, am_x, weights, dils, U, sums, n: int, h: int, w: int, cin: int, cout: int):
     """U = x Wf^T in one segmented launch with column groups; the packed x it read, or None when this head does not take that
-    route (nothing ran: the caller makes today's launches).  Under engine.StepGraph the first launch of a plan, which
-    allocates and copies its device table, happens in the eager warm-up steps, as for the input gradient's launch."""
+    route (nothing ran: the caller makes the stacked and the per-branch launches).  Under engine.StepGraph the first launch of a
+    plan, which allocates and copies its device table, happens in the eager warm-up steps, as for the input gradient's launch."""
     k = len(weights)
     ldu = k * cout
     if not ASPP_FWD_ONE or _PREC[0] not in (2, 3) or cout % COL_TILE != 0 or not nt_presplit_ok(cin, cin, cin):
@@ -1453,19 +1299,17 @@ class AsppCentreFn(Function):
                  a_packed=pa, b_packed=pb)
         for i in range(1, 1 if one else k):
             d = dils[i - 1]
-            mask = tap_mask(1, h, w, h, w, 3, 3, 1, d, d)
-            off = mask & ~CENTRE_TAP
-            if not off:
-                continue
-            # the launch this conv uses today (per-tap rectangles with atomics, or dense), minus the centre tap: it adds into
+            # the launch this conv would use alone (per-tap rectangles with atomics, or dense), minus the centre tap: it adds into
             # its column slice of U, which needs no zero fill
-            rect = bin(mask).count("1") > 1 and rect_fraction(1, h, w, h, w, 3, 3, d, d, mask) < _rect_thr("fwd")
+            pl = conv_plan.plan("fwd", (n, h, w, cin, cout, 3, 3, 1, d, d), _PREC[0], keep=~CENTRE_TAP)
+            if not pl.mask:
+                continue
             wt, am_w = tap_major(weights[i]), amax_of(weights[i])
-            ok_xi = ok and (cout * bin(off).count("1") >= PRESPLIT_MIN_COLS or packed_hit(x, am_x) is not None)
+            ok_xi = ok and (cout * pl.kept >= PRESPLIT_MIN_COLS or packed_hit(x, am_x) is not None)
             xi, pi = pick(x, act_packed(x, am_x) if ok_xi else None, ok_xi)
             wi, pbi = pick(wt, weight_packed(wt, weights[i], "w", am_w) if ok else None, ok)
-            gemm("nt", xi, wi, U[..., i * cout:(i + 1) * cout], M=rows, N=cout, K=cin, lda=cin, ldb=cin, ldc=ldu, taps=9, mask=off,
-                 tap_stride_b=cout * cin, gather=1, geo=(n, h, w, h, w, 3, 3, 1, d, d), rect=rect, accumulate=not rect,
+            gemm("nt", xi, wi, U[..., i * cout:(i + 1) * cout], M=rows, N=cout, K=cin, lda=cin, ldb=cin, ldc=ldu, taps=9, mask=pl.mask,
+                 tap_stride_b=cout * cin, gather=1, geo=pl.geo, rect=pl.rect, accumulate=not pl.rect,
                  amax_a=am_x, amax_b=am_w, a_packed=pi, b_packed=pbi)
         # [2][k Cout] -> [k][2][Cout]: the layout a BatchNorm reads its own sums in (a 16 KB copy)
         s4 = sums.view(2, k, cout).permute(1, 0, 2).contiguous() if stats else torch.empty(0, dtype=torch.float64, device=dev)
@@ -1509,19 +1353,15 @@ class AsppCentreFn(Function):
                      a_packed=True, b_packed=pb)
             for i in range(1, 1 if one else k):
                 d = dils[i - 1]
-                mask = tap_mask(2, h, w, h, w, 3, 3, 1, d, d)
-                off = mask & ~CENTRE_TAP
-                if not off:
+                # (region mode: a region whose taps are all masked out gets no tiles, its pixels are not touched)
+                pl = conv_plan.plan("dgrad", (n, h, w, cin, cout, 3, 3, 1, d, d), _PREC[0], keep=~CENTRE_TAP)
+                if not pl.mask:
                     continue
-                frac = rect_fraction(2, h, w, h, w, 3, 3, d, d, mask)
-                if bin(mask).count("1") > 1 and region_mode(9, 3, 1, d, d, h, w, h, w, cout, frac):
-                    rect = 2                     # a region whose taps are all masked out gets no tiles: its pixels are not touched
-                else:
-                    rect = int(bin(mask).count("1") > 1 and frac < _rect_thr("dgrad"))
+                rect = pl.rect
                 wT, am_w = tap_major_T(weights[i]), amax_of(weights[i])
                 wi, pbi = pick(wT, weight_packed(wT, weights[i], "wT", am_w), True)
-                gemm("nt", dys[i], wi, dx, M=rows, N=cin, K=cout, lda=ldu, ldb=cout, ldc=cin, taps=9, mask=off, tap_stride_b=cout * cin,
-                     gather=2, geo=(n, h, w, h, w, 3, 3, 1, d, d), rect=rect, accumulate=rect != 1, amax_a=am_g, amax_b=am_w,
+                gemm("nt", dys[i], wi, dx, M=rows, N=cin, K=cout, lda=ldu, ldb=cout, ldc=cin, taps=9, mask=pl.mask, tap_stride_b=cout * cin,
+                     gather=2, geo=pl.geo, rect=rect, accumulate=rect != 1, amax_a=am_g, amax_b=am_w,
                      amax_c=slot if rect != 1 else None, a_packed=True, b_packed=pbi)
                 if rect == 1:
                     slot = None                  # atomics report no maximum: dx is measured on first use
@@ -1535,15 +1375,14 @@ class AsppCentreFn(Function):
             dWc = torch.empty(ldu, cin, dtype=torch.float32, device=dev)
             am_x = ctx.x_packed[1] if ctx.x_packed is not None else amax_of(x)
             xb, pb = pick(x, ctx.x_packed[0] if ctx.x_packed is not None else None, tn_presplit_ok(ldu, cin, ldu, cin))
-            gemm("tn", G, xb, dWc, M=ldu, N=cin, K=rows, lda=ldu, ldb=cin, ldc=cin, split=wgrad_split(rows, 1.0, ldu, cin, 1, False),
+            gemm("tn", G, xb, dWc, M=ldu, N=cin, K=rows, lda=ldu, ldb=cin, ldc=cin, split=conv_plan.wgrad_split(rows, 1.0, ldu, cin, 1, False, _PREC[0]),
                  amax_a=am_g, amax_b=am_x, a_packed=True, b_packed=pb)
         for i in range(k):
             if not ctx.needs_input_grad[3 + i]:
                 dws.append(None)
                 continue
             kk, d = (1, 1) if i == 0 else (3, dils[i - 1])
-            cfg = (n, h, w, cin, cout, kk, kk, h, w, 1, 0 if i == 0 else d, d, i == 0)
-            mask = 1 if i == 0 else tap_mask(1, h, w, h, w, 3, 3, 1, d, d)
+            geom = (n, h, w, cin, cout, kk, kk, 1, 0 if i == 0 else d, d)
             if stacked and i == 0:
                 # a copy of 4 Cout Cin bytes (2 MB at 2048 -> 256) into the parameter's slot; the alternative, a reduce that sends
                 # one row block elsewhere, would put a second destination into every TN second stage for this one caller
@@ -1551,13 +1390,15 @@ class AsppCentreFn(Function):
                 if dw.data_ptr() % 16 == 0:
                     check(lib.glf_copy_frames(_p(dWc), cout * cin, _p(dw), cout * cin, 1, cout * cin, _stream()), "aspp_centre(dw 1x1)")
                 else:                      # (a bucket slot that starts off a 16-byte boundary: the branch's own reduction stores there)
-                    _conv_wgrad(weights[0], tuple(weights[0].shape), x, ctx.x_packed, dys[0], ldu, True, am_g, cfg, mask, out=dw)
+                    _conv_wgrad(weights[0], tuple(weights[0].shape), x, ctx.x_packed, dys[0], ldu, True, am_g,
+                                    conv_plan.plan("wgrad", geom, _PREC[0]), out=dw)
                 dws.append(dw)
             elif stacked:
-                dws.append(_conv_wgrad(weights[i], tuple(weights[i].shape), x, ctx.x_packed, dys[i], ldu, True, am_g, cfg, mask & ~CENTRE_TAP,
-                                       foreign=(4, dWc[i * cout:(i + 1) * cout], cin)))
+                dws.append(_conv_wgrad(weights[i], tuple(weights[i].shape), x, ctx.x_packed, dys[i], ldu, True, am_g,
+                                       conv_plan.plan("wgrad", geom, _PREC[0], keep=~CENTRE_TAP), foreign=(4, dWc[i * cout:(i + 1) * cout], cin)))
             else:
-                dws.append(_conv_wgrad(weights[i], tuple(weights[i].shape), x, ctx.x_packed, dys[i], ldu, True, am_g, cfg, mask))
+                dws.append(_conv_wgrad(weights[i], tuple(weights[i].shape), x, ctx.x_packed, dys[i], ldu, True, am_g,
+                                       conv_plan.plan("wgrad", geom, _PREC[0])))
         return (dx, None, None) + tuple(dws)
 
 
@@ -2040,7 +1881,7 @@ class _Folded:
 
 
 def fold_plan(x: torch.Tensor, weight: torch.Tensor, bn, stride: int, pad: int, dil: int):
-    """(plain, mask, rect, ho, wo) when conv(x, weight) -> bn runs on the folded path right now, else None: switch on, split-fp16
+    """The conv's "fwd_folded" ConvPlan when conv(x, weight) -> bn runs on the folded path right now, else None: switch on, split-fp16
     precision, no autograd graph, BatchNorm in eval mode with running statistics, and a conv the epilogue kernels cover (aligned
     fast path, more than 64 output rows, every output element stored once: dense, or region mode where the unfolded conv would
     sum per-tap rectangles with atomics and the conv is a 3x3 'same' one; other per-tap-rectangle convs stay unfolded)."""
@@ -2054,21 +1895,11 @@ def fold_plan(x: torch.Tensor, weight: torch.Tensor, bn, stride: int, pad: int, 
     cout, cin_w, kh, kw = weight.shape
     if cin_w != cin or cin % 32 != 0 or cin > (1 << 18) or cout % 4 != 0:
         return None
-    ho, wo = _conv_out(h, kh, stride, pad, dil), _conv_out(w, kw, stride, pad, dil)
-    if ho <= 0 or wo <= 0 or n * ho * wo <= 64:               # <= 64 rows: the skinny kernel of the ASPP pooled branch keeps its path
+    pl = conv_plan.plan("fwd_folded", (n, h, w, cin, cout, kh, kw, stride, pad, dil), _PREC[0])
+    # <= 64 rows: the skinny kernel of the ASPP pooled branch keeps its path; rect 1: per-tap rectangles no region mode replaces
+    if pl.ho <= 0 or pl.wo <= 0 or pl.M <= 64 or pl.mask == 0 or pl.rect == 1:
         return None
-    taps = kh * kw
-    plain = taps == 1 and stride == 1 and pad == 0
-    mask = 1 if plain else tap_mask(1, ho, wo, h, w, kh, kw, stride, pad, dil)
-    if mask == 0:
-        return None
-    rect = 0
-    if (not plain and taps > 1 and stride == 1 and bin(mask).count("1") > 1
-            and rect_fraction(1, ho, wo, h, w, kh, kw, pad, dil, mask) < _rect_thr("fwd")):
-        if not (taps == 9 and kh == 3 and pad == dil and ho == h and wo == w):
-            return None
-        rect = 2
-    return plain, mask, rect, ho, wo
+    return pl
 
 
 def _fold_entry(cache: dict, weight: torch.Tensor, bias: Optional[torch.Tensor], bn, dtype):
@@ -2114,26 +1945,23 @@ def _folded_images(weight: torch.Tensor, bias: Optional[torch.Tensor], bn):
 def conv_bn_folded(x, weight, bias, bn, stride: int, pad: int, dil: int, relu: bool, residual=None, plan=None, amax_x=None):
     """relu?(bn_eval(conv(x)) + residual?) in one launch on NHWC tensors; plan = fold_plan(...) (not None).  amax_x: the bound of
     max|x| when x itself does not carry one (the ASPP concat buffer)."""
-    plain, mask, rect, ho, wo = plan
     x = _contig(_chk(x, "conv input"))
-    n, h, w, cin = x.shape
-    cout, _, kh, kw = weight.shape
-    taps = kh * kw
+    n, cin, cout = x.shape[0], x.shape[-1], weight.shape[0]
     wf, shift = _folded_images(weight, bias, bn)
-    y, ldy, shared = _take_out((n, ho, wo, cout), x.device)
+    y, ldy, shared = _take_out((n, plan.ho, plan.wo, cout), x.device)
     am = shared if shared is not None else amax_slot(x.device)
     am_w, am_x = amax_of(wf), (amax_x if amax_x is not None else amax_of(x))
     ok = nt_presplit_ok(cin, cin, cin)
-    ok_x = ok and (cout * bin(mask).count("1") >= PRESPLIT_MIN_COLS or packed_hit(x, am_x) is not None)
+    ok_x = ok and (cout * plan.kept >= PRESPLIT_MIN_COLS or packed_hit(x, am_x) is not None)
     xa, pa = pick(x, act_packed(x, am_x) if ok_x else None, ok_x)
     wb, pb = pick(wf, weight_packed(wf, wf, "w", am_w) if ok else None, ok)
     res, ldr = (None, 0)
     if residual is not None:
         res, ldr = _rows_view(_chk(residual, "bn residual"))
-        if res.numel() // res.shape[-1] != n * ho * wo or res.shape[-1] != cout:
+        if res.numel() // res.shape[-1] != plan.M or res.shape[-1] != cout:
             raise RuntimeError("conv_bn_folded: residual shape does not match the conv output")
-    gemm("nt", xa, wb, y, M=n * ho * wo, N=cout, K=cin, lda=cin, ldb=cin, ldc=ldy, bias=shift, taps=taps, mask=mask,
-         tap_stride_b=cout * cin, gather=0 if plain else 1, geo=None if plain else (n, h, w, ho, wo, kh, kw, stride, pad, dil), rect=rect,
+    gemm("nt", xa, wb, y, M=plan.M, N=cout, K=cin, lda=cin, ldb=cin, ldc=ldy, bias=shift, taps=plan.taps, mask=plan.mask,
+         tap_stride_b=cout * cin, gather=plan.gather, geo=plan.geo, rect=plan.rect,
          amax_a=am_x, amax_b=am_w, amax_c=am, a_packed=pa, b_packed=pb, epilogue=(res, ldr, relu))
     set_amax(y, am)
     return y

@@ -91,7 +91,7 @@ def gemm16(mode: str, A: torch.Tensor, B: torch.Tensor, Cm: torch.Tensor, *, M: 
         kept = bin(mask).count("1")
         dense = 2.0 * M * N * K * taps * batch
         src_rows = (geo[0] * geo[1] * geo[2]) if geo else None
-        in_range = _o.rect_fraction(gather, geo[3], geo[4], geo[1], geo[2], geo[5], geo[6], geo[8], geo[9], mask) if (rect and geo and gather) else 1.0
+        in_range = conv_plan.rect_fraction(gather, geo[3], geo[4], geo[1], geo[2], geo[5], geo[6], geo[8], geo[9], mask) if (rect and geo and gather) else 1.0
         csz = 2 if Cm.dtype == BF else 4
         if mode == "tn":
             abytes = batch * (2.0 * (K * M + (src_rows if src_rows else K) * N) + csz * M * N * kept)

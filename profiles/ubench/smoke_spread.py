@@ -5,15 +5,16 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import torch
-from glfusion_amd import ops
+from glfusion_amd import conv_plan, ops
 from glfusion_amd.models import Global_and_Local
 from oracle import glfusion_ref as orc
 
 if os.environ.get("SPREAD_NORECT"):          # no per-tap rectangle launches (the float-atomic form) for: all | fwd | dgrad | wgrad
     which = os.environ["SPREAD_NORECT"]
-    for k in ops.RECT_THRESHOLD:
+    for k in conv_plan.RECT_THRESHOLD:
         if k != "region" and (which in ("1", "all") or k.startswith(which)):
-            ops.RECT_THRESHOLD[k] = 0.0
+            conv_plan.RECT_THRESHOLD[k] = 0.0
+    conv_plan.plan.cache_clear()             # (the planner is memoised)
 runs = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 prec = sys.argv[2] if len(sys.argv) > 2 else "f32"
 dev = torch.device("cuda:0")

@@ -112,11 +112,14 @@ def test_adam_pointer_table_chunks():
 
 
 def test_conv_plan_matches_host_policy():
-    """glf_conv2d_plan (the launch policy embedded in the C convolution entry points) against the policy the Python autograd
-    wrappers use (ops.tap_mask / rect_fraction / region_mode / _tn_split): same kept taps, same mode, same reduction slices, for
-    every conv geometry of the model (and a few ragged ones) under every precision.  No GPU needed: the plan launches nothing."""
+    """glf_conv2d_plan (the launch policy embedded in the C convolution entry points) against the policy of the Python autograd
+    wrappers, restated here rule by rule from the planner's parts (conv_plan.tap_mask / rect_fraction / RECT_THRESHOLD /
+    wgrad_split / conv_out; the region-mode condition and the choice of threshold are written out): same kept taps, same mode,
+    same reduction slices, for every conv geometry of the model (and a few ragged ones) under every precision.  No GPU needed: the
+    plan launches nothing."""
     import ctypes as C
-    from glfusion_amd import ops
+    from glfusion_amd import conv_plan, ops
+    thr = conv_plan.RECT_THRESHOLD
     from glfusion_amd._lib import ConvParams, ConvPlan, lib
     convs = [  # n, h, w, cin, cout, k, stride, pad, dil
         (64, 55, 55, 64, 64, 3, 1, 1, 1), (64, 55, 55, 128, 128, 3, 2, 1, 1), (64, 55, 55, 256, 512, 1, 2, 0, 1),
@@ -125,51 +128,55 @@ def test_conv_plan_matches_host_policy():
         (64, 28, 28, 256, 5, 1, 1, 0, 1), (64, 1, 1, 2048, 256, 1, 1, 0, 1), (32, 56, 56, 2048, 256, 3, 1, 36, 36),
         (3, 15, 13, 32, 40, 3, 1, 1, 1), (2, 28, 28, 64, 288, 3, 1, 12, 12), (192, 28, 28, 1024, 2048, 1, 1, 0, 1)]
     for prec in ("f32", "bf16x6", "f16x3", "f16"):
-        ops.set_precision(prec)
+        ops.set_precision(prec)                            # (conv_stats_fusable answers for the current precision)
+        pi = ops.PRECISIONS.index(prec)
         try:
             for (n, h, w, cin, cout, k, stride, pad, dil) in convs:
                 p = ConvParams()
                 p.n, p.h, p.w, p.cin, p.cout, p.kh, p.kw, p.stride, p.pad, p.dil = n, h, w, cin, cout, k, k, stride, pad, dil
-                p.precision = ops.PRECISIONS.index(prec) + 1
-                ho, wo = ops._conv_out(h, k, stride, pad, dil), ops._conv_out(w, k, stride, pad, dil)
+                p.precision = pi + 1
+                ho, wo = conv_plan.conv_out(h, k, stride, pad, dil), conv_plan.conv_out(w, k, stride, pad, dil)
                 taps, plain = k * k, (k == 1 and stride == 1 and pad == 0)
                 pl = ConvPlan()
                 # forward
                 assert lib.glf_conv2d_plan(C.byref(p), 0, C.byref(pl)) == 0
-                mask = 1 if plain else ops.tap_mask(1, ho, wo, h, w, k, k, stride, pad, dil)
+                mask = 1 if plain else conv_plan.tap_mask(1, ho, wo, h, w, k, k, stride, pad, dil)
                 rect = (not plain and taps > 1 and stride == 1 and bin(mask).count("1") > 1
-                        and ops.rect_fraction(1, ho, wo, h, w, k, k, pad, dil, mask) < ops._rect_thr("fwd"))
+                        and conv_plan.rect_fraction(1, ho, wo, h, w, k, k, pad, dil, mask) < thr["fwd"])
                 assert (pl.ho, pl.wo, pl.tap_mask, pl.rect, pl.plain) == (ho, wo, mask, int(rect), int(plain)), (prec, "fwd", n, h, cin, cout, k, dil)
                 from torch import empty
                 wshape = empty(cout, cin, k, k, device="meta")
                 assert bool(pl.colstats_ok) == ops.conv_stats_fusable(wshape, stride, pad, dil, h, w), (prec, "colstats", cin, cout, k, dil)
                 # dgrad
                 assert lib.glf_conv2d_plan(C.byref(p), 1, C.byref(pl)) == 0
-                mask = 1 if plain else ops.tap_mask(2, h, w, ho, wo, k, k, stride, pad, dil)
-                frac = 1.0 if plain or stride != 1 else ops.rect_fraction(2, h, w, ho, wo, k, k, pad, dil, mask)
-                if mask and not plain and bin(mask).count("1") > 1 and ops.region_mode(taps, k, stride, pad, dil, ho, wo, h, w, cout, frac):
+                mask = 1 if plain else conv_plan.tap_mask(2, h, w, ho, wo, k, k, stride, pad, dil)
+                frac = 1.0 if plain or stride != 1 else conv_plan.rect_fraction(2, h, w, ho, wo, k, k, pad, dil, mask)
+                # region mode: the f16x3 kernels, a 3x3 stride-1 "same" conv, K = Cout a multiple of 32, mostly padding
+                region = (pi >= 2 and taps == 9 and k == 3 and stride == 1 and pad == dil and ho == h and wo == w
+                          and cout % 32 == 0 and frac < thr["region"])
+                if mask and not plain and bin(mask).count("1") > 1 and region:
                     want = 2
                 else:
-                    want = int(not plain and taps > 1 and stride == 1 and bin(mask).count("1") > 1 and frac < ops._rect_thr("dgrad"))
+                    want = int(not plain and taps > 1 and stride == 1 and bin(mask).count("1") > 1
+                               and frac < thr["dgrad_f16x3" if pi >= 2 else "dgrad"])
                 assert (pl.tap_mask, pl.rect) == (mask, want), (prec, "dgrad", n, h, cin, cout, k, dil)
                 # wgrad
                 assert lib.glf_conv2d_plan(C.byref(p), 2, C.byref(pl)) == 0
-                mask = 1 if plain else ops.tap_mask(1, ho, wo, h, w, k, k, stride, pad, dil)
+                mask = 1 if plain else conv_plan.tap_mask(1, ho, wo, h, w, k, k, stride, pad, dil)
                 ntap = bin(mask).count("1")
                 rect = (not plain and taps > 1 and stride == 1 and ntap > 1
-                        and ops.rect_fraction(1, ho, wo, h, w, k, k, pad, dil, mask) < ops._rect_thr("wgrad"))
-                frac = ops.rect_fraction(1, ho, wo, h, w, k, k, pad, dil, mask) if rect else 1.0
-                split = ops.wgrad_split(n * ho * wo, frac, cout, cin, ntap, rect)
+                        and conv_plan.rect_fraction(1, ho, wo, h, w, k, k, pad, dil, mask) < thr["wgrad"])
+                frac = conv_plan.rect_fraction(1, ho, wo, h, w, k, k, pad, dil, mask) if rect else 1.0
+                split = conv_plan.wgrad_split(n * ho * wo, frac, cout, cin, ntap, rect, pi)
                 assert (pl.tap_mask, pl.rect, pl.split) == (mask, int(rect), split), (prec, "wgrad", n, h, cin, cout, k, dil, pl.split, split)
         finally:
             ops.set_precision("f32")
 
 
 def test_conv_plan_matches_planner():
-    """glf_conv2d_plan against glfusion_amd.conv_plan.plan (the planner the 16-bit-storage wrappers ask, and the one the
-    fp32-storage wrappers are to move to), field by field: every pass, every conv geometry above and the ragged ones of
-    test_conv_plan_cpu.py, under every fp32-storage precision.  No policy is restated here; with the test above, the inline
-    policy of ops, the C plan and the planner are held to each other."""
+    """glf_conv2d_plan against glfusion_amd.conv_plan.plan (the planner the wrappers of both storages ask), field by field: every
+    pass, every conv geometry above and the ragged ones of test_conv_plan_cpu.py, under every fp32-storage precision.  No policy
+    is restated here; with the test above, the rules spelled out one by one, the C plan and the planner are held to each other."""
     import ctypes as C
     import json
     from glfusion_amd import conv_plan, ops

@@ -1,8 +1,8 @@
 """CPU, no library: glfusion_amd.conv_plan.plan() against the frozen table golden/conv_plan_table.json.
 
-The table was recorded from the functions whose rules the planner states (ops.tap_mask / rect_fraction / region_mode / _rect_thr / wgrad_split,
-ops16._region / tn_split16 and the conditions written out in Conv2dFn, _conv_wgrad, AsppCentreFn, fold_plan, Conv2d16Fn and
-fold_plan16) at the commit before it, for every precision of ops.PRECISIONS, every pass and every geometry: the fifteen of
+The table was recorded from the functions that stated the planner's rules before it existed (ops.tap_mask / rect_fraction / region_mode /
+_rect_thr / wgrad_split, ops16._region / tn_split16 and the conditions written out in Conv2dFn, _conv_wgrad, AsppCentreFn, fold_plan,
+Conv2d16Fn and fold_plan16; every wrapper asks the planner now), for every precision of ops.PRECISIONS, every pass and every geometry: the fifteen of
 test_abi_cpu.py::test_conv_plan_matches_host_policy plus 16-bit region / rectangle cases on both sides of the rows_o >= 2048 rule,
 pad != dil, stride 2 with dilation, centre tap only, a partial mask (only the middle row of taps survives) and a mask that is empty
 in both directions.  Pass "fwd_bias" is the forward of a conv with a bias (what the conv does about column statistics then was
@@ -59,6 +59,29 @@ def test_plan_fields_are_consistent():
                 assert pl.geo == (n,) + src + dst + (k, k, stride, pad, dil)
             assert pl.split == 1 or pass_ == "wgrad"
             assert pl.workspace_bytes == (pl.split * pl.kept * cout * cin * 4 if pl.split > 1 else 0)
+
+
+def test_ops_holds_no_launch_policy_of_its_own():
+    """The fp32-storage wrappers ask the planner: the policy names ops still offers ARE the planner's objects (whoever changes a
+    threshold through ops changes the planner's), the helpers that restated the rules are gone, and conv_stats_fusable answers
+    what the frozen table records for the forward pass under the four fp32-storage precisions."""
+    import torch
+    from glfusion_amd import conv_plan, ops
+    assert ops.tap_mask is conv_plan.tap_mask and ops.rect_fraction is conv_plan.rect_fraction
+    assert ops.RECT_THRESHOLD is conv_plan.RECT_THRESHOLD and ops.CENTRE_TAP == conv_plan.CENTRE_TAP
+    for name in ("region_mode", "_rect_thr", "_conv_out", "wgrad_split", "_mask_cache", "_rect_cache"):
+        assert not hasattr(ops, name), name
+    t = _table()
+    seen = 0
+    for prec, pass_, gi, _, _, _, _, _, colstats_ok, _, _ in t["rows"]:
+        if pass_ != "fwd" or t["precisions"][prec] == "bf16":
+            continue
+        n, h, w, cin, cout, k, stride, pad, dil = t["geometries"][gi]
+        with ops.precision_scope(t["precisions"][prec]):
+            got = ops.conv_stats_fusable(torch.empty(cout, cin, k, k, device="meta"), stride, pad, dil, h, w)
+        assert got == colstats_ok, (t["precisions"][prec], t["geometries"][gi])
+        seen += 1
+    assert seen == 4 * len(t["geometries"])
 
 
 def test_planner_loads_without_torch_or_the_library():

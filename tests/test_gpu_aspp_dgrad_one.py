@@ -80,6 +80,7 @@ def _one_launch(ops, shape, Gp, am_g, ws, dx, slot=None):
 
 def _three_launches(ops, shape, Gp, am_g, ws, dx):
     """The launches ops.AsppCentreFn.backward makes with the switch off, on the same packed gradient image."""
+    from glfusion_amd import conv_plan
     n, h, w, cin, cout, rates = SHAPES[shape]
     k, rows = 1 + len(rates), n * h * w
     ldu = k * cout
@@ -89,12 +90,11 @@ def _three_launches(ops, shape, Gp, am_g, ws, dx):
              a_packed=True, b_packed=True)
     for i in range(1, k):
         d = rates[i - 1]
-        mask = ops.tap_mask(2, h, w, h, w, 3, 3, 1, d, d)
-        off = mask & ~ops.CENTRE_TAP
+        pl = conv_plan.plan("dgrad", (n, h, w, cin, cout, 3, 3, 1, d, d), ops.PRECISIONS.index(ops.get_precision()), keep=~ops.CENTRE_TAP)
+        off, rect = pl.mask, pl.rect
         if not off:
             continue
-        frac = ops.rect_fraction(2, h, w, h, w, 3, 3, d, d, mask)
-        rect = 2 if ops.region_mode(9, 3, 1, d, d, h, w, h, w, cout, frac) else 0
+        assert rect in (0, 2)                  # (dense or regions: both accumulate into dx without atomics)
         wT = ws[i].detach().permute(2, 3, 1, 0).reshape(9, cin, cout).contiguous()
         am_w = ops.amax_of(wT)
         ops.gemm("nt", Gp[:, i * cout:(i + 1) * cout], ops.packed_of(wT, am_w), dx, M=rows, N=cin, K=cout, lda=ldu, ldb=cout, ldc=cin,

@@ -89,6 +89,7 @@ def _one_launch(ops, shape, xp, am_x, ws, U, slot=None, sums=None, colmax=None):
 
 def _old_launches(ops, shape, xp, am_x, ws, U):
     """The launches ops.AsppCentreFn.forward makes with the switch off, on the same packed input image."""
+    from glfusion_amd import conv_plan
     n, h, w, cin, cout, rates = SHAPES[shape]
     k, rows = 1 + len(rates), n * h * w
     ldu = k * cout
@@ -98,11 +99,10 @@ def _old_launches(ops, shape, xp, am_x, ws, U):
              a_packed=True, b_packed=True)
     for i in range(1, k):
         d = rates[i - 1]
-        mask = ops.tap_mask(1, h, w, h, w, 3, 3, 1, d, d)
-        off = mask & ~ops.CENTRE_TAP
+        pl = conv_plan.plan("fwd", (n, h, w, cin, cout, 3, 3, 1, d, d), ops.PRECISIONS.index(ops.get_precision()), keep=~ops.CENTRE_TAP)
+        off, rect = pl.mask, pl.rect
         if not off:
             continue
-        rect = bin(mask).count("1") > 1 and ops.rect_fraction(1, h, w, h, w, 3, 3, d, d, mask) < ops._rect_thr("fwd")
         wt = ws[i].detach().permute(2, 3, 0, 1).reshape(9, cout, cin).contiguous()
         am_w = ops.amax_of(wt)
         ops.gemm("nt", xp, ops.packed_of(wt, am_w), U[:, i * cout:(i + 1) * cout], M=rows, N=cout, K=cin, lda=cin, ldb=cin, ldc=ldu,
