@@ -107,32 +107,19 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_bf16s8_kernel(const GemmArgs
     const float p_alpha = args.alpha;
     const float* __restrict__ p_A = args.A; const float* __restrict__ p_B = args.B; const float* __restrict__ p_bias = args.bias;
     float* __restrict__ p_C = args.C;
-    const int g_hs = args.g.hs, g_ws = args.g.ws, g_hd = args.g.hd, g_wd = args.g.wd, g_kw = args.g.kw;
-    const int g_stride = args.g.stride, g_pad = args.g.pad, g_dil = args.g.dil;
-    const int g_nimg = args.g.n_img, p_rect = GATHER ? args.rect : 0;
+    const RowsGeo G{p_gather, args.g.n_img, args.g.hs, args.g.ws, args.g.hd, args.g.wd, args.g.kw, args.g.stride, args.g.pad, args.g.dil};
+    const int p_rect = GATHER ? args.rect : 0;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];
     unsigned* s_mask = reinterpret_cast<unsigned*>(smem_s + 2 * BUF8);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tn = bid % p_tiles_n;
-    int tm = bid / p_tiles_n;
-    int pMe = pM;
-    int r_y0 = 0, r_x0 = 0, r_h = g_hd, r_w = g_wd;
-    unsigned mask = p_tap_mask;
-    if (p_rect) {
-        for (unsigned mm = p_tap_mask; mm; mm &= mm - 1) {
-            const int t = __ffs(mm) - 1;
-            int y0, y1, x0, x1;
-            tap_rect(p_gather, t, g_kw, g_pad, g_dil, g_hs, g_ws, g_hd, g_wd, y0, y1, x0, x1);
-            const int mt = g_nimg * (y1 - y0) * (x1 - x0);
-            const int tiles = (mt + BM8 - 1) / BM8;
-            if (tm < tiles || (mm & (mm - 1)) == 0) { mask = 1u << t; pMe = mt; r_y0 = y0; r_x0 = x0; r_h = y1 - y0; r_w = x1 - x0; break; }
-            tm -= tiles;
-        }
-    }
+    int tn;
+    RowTile rt{0, pM, 0, 0, G.hd, G.wd, p_tap_mask};
+    rows_tile_order(0, p_tiles_n, tn, rt.tm);
+    if (p_rect) rows_locate<BM8, false>(1, p_tap_mask, G, rt);
+    unsigned mask = rt.mask;
     const int bz = blockIdx.z;
     const float* __restrict__ A = p_A + (long long)bz * p_bsa;
     const float* __restrict__ B = p_B + (long long)bz * p_bsb;
@@ -140,40 +127,11 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_bf16s8_kernel(const GemmArgs
 
     const int ac = tid & 7, ar = tid >> 3;              // 8 float4 per 32-deep row; rows ar + 64 j
 
-    int a_n[4], a_y[4], a_x[4];
-    long long a_off[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int m = tm * BM8 + ar + 64 * j;
-        if (GATHER) {
-            if (m < pMe) {
-                const int hw = r_h * r_w;
-                const int n = m / hw, rem = m - n * hw;
-                const int yy = rem / r_w;
-                a_n[j] = n; a_y[j] = r_y0 + yy; a_x[j] = r_x0 + rem - yy * r_w;
-            } else { a_n[j] = -1; a_y[j] = 0; a_x[j] = 0; }
-            a_off[j] = -1;
-        } else {
-            a_n[j] = 0; a_y[j] = 0; a_x[j] = 0;
-            a_off[j] = (m < pM) ? (long long)m * p_lda : -1;
-        }
-    }
-    if (GATHER && p_taps > 1 && !p_rect) {
-        if (tid == 0) *s_mask = 0u;
-        __syncthreads();
-        if (ac == 0) {
-            unsigned local = 0;
-            for (unsigned mm = mask; mm; mm &= mm - 1) {
-                const int t = __ffs(mm) - 1;
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (a_n[j] >= 0 && map_src(g_hs, g_ws, g_kw, g_stride, g_pad, g_dil, p_gather, a_n[j], a_y[j], a_x[j], t) >= 0) local |= 1u << t;
-            }
-            if (local) atomicOr(s_mask, local);
-        }
-        __syncthreads();
-        mask &= *s_mask;
-    }
+    RowState<4> rows;
+    rows_init<4, 64, GATHER>(rows, rt.tm * BM8 + ar, rt, p_lda, G.hd, G.wd);
+    const bool fastg = GATHER && rows_fast_gather(G);
+    if (fastg) rows_to_fast(rows, G);
+    rows_census<BM8, 4, GATHER>(rows, mask, fastg, ac == 0, p_taps, p_rect, G, s_mask);
 
     const int nkc = pK / BK;
     const int ntiles = __popc(mask) * nkc;
@@ -184,25 +142,13 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_bf16s8_kernel(const GemmArgs
     const float* pa[4];
     const float* pb[2];
     unsigned a_ok = 0, a_ok_c = 0;                       // validity of the rows being LOADED / being CONVERTED
+    const int a_col[4] = {4 * ac, 4 * ac, 4 * ac, 4 * ac};
 
+    // padding / out-of-range rows load from a clamped address (A's row 0) and are zeroed by a_ok_c when they are converted
     auto advance = [&]() __attribute__((always_inline)) {
         if (++kc >= nkc) {
             kc = 0;
-            tap = __ffs(rem_mask) - 1;
-            rem_mask &= rem_mask - 1;
-            a_ok = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                long long off;
-                if (GATHER) {
-                    const int sr = (a_n[j] >= 0) ? map_src(g_hs, g_ws, g_kw, g_stride, g_pad, g_dil, p_gather, a_n[j], a_y[j], a_x[j], tap) : -1;
-                    off = (sr >= 0) ? (long long)sr * p_lda : -1;
-                } else {
-                    off = a_off[j];
-                }
-                a_ok |= (off >= 0 ? 1u : 0u) << j;
-                pa[j] = A + (off >= 0 ? off : 0) + 4 * ac;
-            }
+            tap = rows_next_tap<4, GATHER>(rows, rem_mask, pa, A, A, p_lda, fastg, G, a_col, &a_ok);
             const float* Bt = B + (long long)tap * p_tsb;
 #pragma unroll
             for (int j = 0; j < 2; ++j) pb[j] = Bt + (long long)min(tn * BN + ar + 64 * j, pN - 1) * p_ldb + 4 * ac;
@@ -302,31 +248,8 @@ __global__ __launch_bounds__(NT8, 2) void gemm_rows_bf16s8_kernel(const GemmArgs
         GLF_S8_BODY(false, false)
     }
 
-    const int col_l = lane & 31, row_l = 4 * (lane >> 5);
-    auto emit = [&](const f32x16& acc, int ti, int tj) {
-        const int col = tn * BN + wn + 32 * tj + col_l;
-        if (col >= pN) return;
-        const float bv = p_bias ? p_bias[col] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = tm * BM8 + wm + 32 * ti + (r & 3) + 8 * (r >> 2) + row_l;
-            if (row < pMe) {
-                if (p_rect) {
-                    const int hw = r_h * r_w;
-                    const int n = row / hw, rem = row - n * hw;
-                    const int yy = rem / r_w;
-                    const long long orow = ((long long)n * g_hd + r_y0 + yy) * g_wd + r_x0 + (rem - yy * r_w);
-                    atomicAdd(C + orow * p_ldc + col, p_alpha * acc[r]);
-                } else {
-                    float* dst = C + (long long)row * p_ldc + col;
-                    float v = p_alpha * acc[r] + bv;
-                    if (p_accumulate) v += *dst;
-                    *dst = v;
-                }
-            }
-        }
-    };
-    emit(c00, 0, 0); emit(c01, 0, 1); emit(c10, 1, 0); emit(c11, 1, 1);
+    const RowsOut out{C, p_bias, nullptr, nullptr, nullptr, nullptr, 0, p_bsc, pN, p_ldc, p_accumulate, p_rect, 0, tn, G.hd, G.wd, p_alpha};
+    rows_plain_epilogue<BM8>(out, rt, c00, c01, c10, c11);
 }
 
 // ----------------------------------------------------------------------------------------------------------

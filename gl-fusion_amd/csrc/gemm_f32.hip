@@ -96,9 +96,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_rows_kernel(const GemmArgs a
     const float p_alpha = args.alpha;
     const float* __restrict__ p_A = args.A; const float* __restrict__ p_B = args.B; const float* __restrict__ p_bias = args.bias;
     float* __restrict__ p_C = args.C;
-    const int g_hs = args.g.hs, g_ws = args.g.ws, g_hd = args.g.hd, g_wd = args.g.wd, g_kw = args.g.kw;
-    const int g_stride = args.g.stride, g_pad = args.g.pad, g_dil = args.g.dil;
-    const int g_nimg = args.g.n_img, p_rect = GATHER ? args.rect : 0;
+    const RowsGeo G{p_gather, args.g.n_img, args.g.hs, args.g.ws, args.g.hd, args.g.wd, args.g.kw, args.g.stride, args.g.pad, args.g.dil};
+    const int p_rect = GATHER ? args.rect : 0;
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int LDA = LD_T;
@@ -110,23 +109,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_rows_kernel(const GemmArgs a
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tn = bid % p_tiles_n;
-    int tm = bid / p_tiles_n;
-    int pMe = pM;                                   // rows of this block's GEMM (rect mode: its tap's rectangle)
-    int r_y0 = 0, r_x0 = 0, r_h = g_hd, r_w = g_wd;
-    unsigned mask = p_tap_mask;
-    if (p_rect) {                                   // tiles are laid out tap after tap
-        for (unsigned mm = p_tap_mask; mm; mm &= mm - 1) {
-            const int t = __ffs(mm) - 1;
-            int y0, y1, x0, x1;
-            tap_rect(p_gather, t, g_kw, g_pad, g_dil, g_hs, g_ws, g_hd, g_wd, y0, y1, x0, x1);
-            const int mt = g_nimg * (y1 - y0) * (x1 - x0);
-            const int tiles = (mt + BM - 1) / BM;
-            if (tm < tiles || (mm & (mm - 1)) == 0) { mask = 1u << t; pMe = mt; r_y0 = y0; r_x0 = x0; r_h = y1 - y0; r_w = x1 - x0; break; }
-            tm -= tiles;
-        }
-    }
+    int tn;
+    RowTile rt{0, pM, 0, 0, G.hd, G.wd, p_tap_mask};    // rect mode: rows and pixels of its tap's rectangle
+    rows_tile_order(0, p_tiles_n, tn, rt.tm);
+    if (p_rect) rows_locate<BM, false>(1, p_tap_mask, G, rt);
+    unsigned mask = rt.mask;
     const int bz = blockIdx.z;
     const float* __restrict__ A = p_A + (long long)bz * p_bsa;
     const float* __restrict__ B = p_B + (long long)bz * p_bsb;
@@ -135,41 +122,20 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_rows_kernel(const GemmArgs a
     const int ac = tid & 7, ar = tid >> 3;          // k-contiguous staging: 8 float4 per 32-deep row
     const int bc = tid & 31, br = tid >> 5;         // row-contiguous staging (BMODE 1)
 
-    int a_n[4], a_y[4], a_x[4];
-    long long a_off[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int m = tm * BM + ar + 32 * j;
-        if (GATHER) {
-            if (m < pMe) {
-                const int hw = r_h * r_w;
-                const int n = m / hw, rem = m - n * hw;
-                const int yy = rem / r_w;
-                a_n[j] = n; a_y[j] = r_y0 + yy; a_x[j] = r_x0 + rem - yy * r_w;
-            } else { a_n[j] = -1; a_y[j] = 0; a_x[j] = 0; }
-            a_off[j] = -1;
-        } else {
-            a_n[j] = 0; a_y[j] = 0; a_x[j] = 0;
-            a_off[j] = (m < pM) ? (long long)m * p_lda : -1;
-        }
-    }
+    // Fast path (block-uniform): every float4 is in range and 16-byte aligned, so the eight loads of a tile are
+    // issued unconditionally from clamped addresses; rows that are padding / out of range are zeroed by a
+    // select when the registers are written to LDS (store_piece), i.e. AFTER the loads' latency has been
+    // hidden under MFMAs -- a select at load time would make the wave wait for the data right there.  Loads inside per-lane
+    // branches make hipcc wait vmcnt(0) at every merge -- eight serialised L2 round trips per K-tile, measured
+    // as a 20 % loss on the whole kernel.
+    const bool vec_a = p_vec_a, vec_b = p_vec_b;
+    const bool fast = vec_a && vec_b && (pK % BK) == 0 && (BMODE == 0 || (pN % 4) == 0);
 
-    if (GATHER && p_taps > 1 && !p_rect) {
-        if (tid == 0) *s_mask = 0u;
-        __syncthreads();
-        if (ac == 0) {
-            unsigned local = 0;
-            for (unsigned mm = mask; mm; mm &= mm - 1) {
-                const int t = __ffs(mm) - 1;
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (a_n[j] >= 0 && map_src(g_hs, g_ws, g_kw, g_stride, g_pad, g_dil, p_gather, a_n[j], a_y[j], a_x[j], t) >= 0) local |= 1u << t;
-            }
-            if (local) atomicOr(s_mask, local);
-        }
-        __syncthreads();
-        mask &= *s_mask;
-    }
+    RowState<4> rows;                               // rows ar + 32 j of the tile
+    rows_init<4, 32, GATHER>(rows, rt.tm * BM + ar, rt, p_lda, G.hd, G.wd);
+    const bool fastg = GATHER && rows_fast_gather(G);
+    if (fastg) rows_to_fast(rows, G);
+    rows_census<BM, 4, GATHER>(rows, mask, fastg, ac == 0, p_taps, p_rect, G, s_mask);
 
     const int nkc = (pK + BK - 1) / BK;
     const int ntiles = __popc(mask) * nkc;
@@ -179,35 +145,25 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_rows_kernel(const GemmArgs a
     float4 ra[4], rb[4];
     unsigned rem_mask = mask;
     int tap = -1, kc = nkc;          // "before the first tile"
-    const bool vec_a = p_vec_a, vec_b = p_vec_b;
 
+    // Both paths take the row pointers of a tap from the shared tap change: pa[j] = float4 #ac of row j's first K-tile, from a
+    // clamped address (A's row 0) where the row is padding / out of range; a_ok says which rows are real.
+    const float* pa[4];
+    const float* pb[4];
+    unsigned a_ok = 0;
+    const int a_col[4] = {4 * ac, 4 * ac, 4 * ac, 4 * ac};
     auto advance = [&]() __attribute__((always_inline)) {
         if (++kc >= nkc) {
             kc = 0;
-            tap = __ffs(rem_mask) - 1;
-            rem_mask &= rem_mask - 1;
-            if (GATHER) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    int s = (a_n[j] >= 0) ? map_src(g_hs, g_ws, g_kw, g_stride, g_pad, g_dil, p_gather, a_n[j], a_y[j], a_x[j], tap) : -1;
-                    a_off[j] = (s >= 0) ? (long long)s * p_lda : -1;
-                }
-            }
+            tap = rows_next_tap<4, GATHER>(rows, rem_mask, pa, A, A, p_lda, fastg, G, a_col, &a_ok);
         }
     };
-    // Fast path (block-uniform): every float4 is in range and 16-byte aligned, so the eight loads of a tile are
-    // issued unconditionally from clamped addresses; rows that are padding / out of range are zeroed by a
-    // select when the registers are written to LDS (store_piece), i.e. AFTER the loads' latency has been
-    // hidden under MFMAs -- a select at load time would make the wave wait for the data right there.  Loads inside per-lane
-    // branches make hipcc wait vmcnt(0) at every merge -- eight serialised L2 round trips per K-tile, measured
-    // as a 20 % loss on the whole kernel.
-    const bool fast = vec_a && vec_b && (pK % BK) == 0 && (BMODE == 0 || (pN % 4) == 0);
     auto load_tile = [&]() __attribute__((always_inline)) {
         const int kbase = kc * BK + 4 * ac;
         const float* Bt = B + (long long)tap * p_tsb;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            ra[j] = (a_off[j] >= 0) ? ld4(A + a_off[j] + kbase, pK - kbase, vec_a) : make_float4(0.f, 0.f, 0.f, 0.f);
+            ra[j] = ((a_ok >> j) & 1u) ? ld4(pa[j] + kc * BK, pK - kbase, vec_a) : make_float4(0.f, 0.f, 0.f, 0.f);
         if (BMODE == 0) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -254,28 +210,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_rows_kernel(const GemmArgs a
 #define GLF_SP_NEXT(q) if (has_next && (q) >= 4) { GLF_SP((q) - 4) }
 
     // ---- fast path state: per-thread source pointers advanced incrementally (no per-tile address maths) ----
-    const float* pa[4];
-    const float* pb[4];
-    unsigned a_ok = 0;
     const long long b_step = (BMODE == 0) ? (long long)BK : (long long)BK * p_ldb;
     auto advance_fast = [&]() __attribute__((always_inline)) {
         if (++kc >= nkc) {
             kc = 0;
-            tap = __ffs(rem_mask) - 1;
-            rem_mask &= rem_mask - 1;
-            a_ok = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                long long off;
-                if (GATHER) {
-                    const int sr = (a_n[j] >= 0) ? map_src(g_hs, g_ws, g_kw, g_stride, g_pad, g_dil, p_gather, a_n[j], a_y[j], a_x[j], tap) : -1;
-                    off = (sr >= 0) ? (long long)sr * p_lda : -1;
-                } else {
-                    off = a_off[j];
-                }
-                a_ok |= (off >= 0 ? 1u : 0u) << j;
-                pa[j] = A + (off >= 0 ? off : 0) + 4 * ac;
-            }
+            tap = rows_next_tap<4, GATHER>(rows, rem_mask, pa, A, A, p_lda, fastg, G, a_col, &a_ok);
             const float* Bt = B + (long long)tap * p_tsb;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -365,32 +304,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_rows_kernel(const GemmArgs a
         }
     }
 
-    // epilogue: lane holds column (lane&31), rows (r&3) + 8*(r>>2) + 4*(lane>>5)
-    const int col_l = lane & 31, row_l = 4 * (lane >> 5);
-    auto emit = [&](const f32x16& acc, int ti, int tj) {
-        const int col = tn * BN + wn + 32 * tj + col_l;
-        if (col >= pN) return;
-        const float bv = p_bias ? p_bias[col] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = tm * BM + wm + 32 * ti + (r & 3) + 8 * (r >> 2) + row_l;
-            if (row < pMe) {
-                if (p_rect) {                               // rectangle row -> output pixel; taps meet in atomics
-                    const int hw = r_h * r_w;
-                    const int n = row / hw, rem = row - n * hw;
-                    const int yy = rem / r_w;
-                    const long long orow = ((long long)n * g_hd + r_y0 + yy) * g_wd + r_x0 + (rem - yy * r_w);
-                    atomicAdd(C + orow * p_ldc + col, p_alpha * acc[r]);
-                } else {
-                    float* dst = C + (long long)row * p_ldc + col;
-                    float v = p_alpha * acc[r] + bv;
-                    if (p_accumulate) v += *dst;
-                    *dst = v;
-                }
-            }
-        }
-    };
-    emit(c00, 0, 0); emit(c01, 0, 1); emit(c10, 1, 0); emit(c11, 1, 1);
+    const RowsOut out{C, p_bias, nullptr, nullptr, nullptr, nullptr, 0, p_bsc, pN, p_ldc, p_accumulate, p_rect, 0, tn, G.hd, G.wd, p_alpha};
+    rows_plain_epilogue<BM>(out, rt, c00, c01, c10, c11);
 }
 
 // ----------------------------------------------------------------------------------------

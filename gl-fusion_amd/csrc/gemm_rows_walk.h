@@ -1,7 +1,9 @@
 // What the NT ("rows") kernels share: which rows a workgroup owns (one tile enumeration for the launchers and the kernels), the
 // order the tiles are walked in, the per-thread state of the A rows a thread stages, and the output epilogue of the two
 // split-fp16 tile configurations (gemm_f16s.hip: 8 waves, 256 rows; gemm_f16s4.hip: 4 waves, 128 rows).  gemm_s16.hip takes the
-// enumeration, the tile order and the row state.
+// enumeration, the tile order and the row state.  The exact-fp32 rows kernel (gemm_f32.hip, 128 rows) and the bf16x6 rows kernel
+// (gemm_bf16s.hip, 256 rows) take those three and the plain output epilogue at the end of this file; what stays with them is the
+// staging of padding / overhang rows, a clamped load zeroed by a select instead of a load from the zero page (rows_next_tap).
 //
 // Every helper is __forceinline__ and takes scalars or a struct of scalars, never GemmArgs: a by-reference use of the by-value
 // kernel argument made hipcc spill the whole struct (gemm_common.h, GeoS).
@@ -207,20 +209,25 @@ __device__ __forceinline__ bool rows_census(const RowState<R>& s, unsigned& mask
 }
 
 // tap change: takes the next tap off rem_mask and points the thread's R row pointers at its rows of A (element type T, col[j] =
-// the thread's column offset in row j); padding / overhang rows read the zero page.  Returns the tap.
+// the thread's column offset in row j); padding / overhang rows read `zero`, the zero page.  Returns the tap.
+// ok != nullptr (the exact-fp32 and bf16x6 kernels): bit j of *ok = row j is a real row.  Those kernels have no zero page --
+// it would cap K at its size, and the exact kernel's slow path reads K tails and unaligned rows -- so they pass A itself for
+// `zero` (row 0: an address every launch may read) and zero the other rows by a select when the registers go to LDS.
 template <int R, bool GATHER, typename T>
 __device__ __forceinline__ int rows_next_tap(const RowState<R>& s, unsigned& rem_mask, const T* (&pa)[R], const T* A, const T* zero,
-                                             int lda, bool fastg, const RowsGeo& g, const int (&col)[R]) {
+                                             int lda, bool fastg, const RowsGeo& g, const int (&col)[R], unsigned* ok = nullptr) {
     const int tap = __ffs(rem_mask) - 1;
     rem_mask &= rem_mask - 1;
+    unsigned real = 0;
     if (fastg) {
         int oy, ox;
         tap_offsets(tap, g, oy, ox);
         const int d = oy * g.ws + ox;
 #pragma unroll
         for (int j = 0; j < R; ++j) {
-            const bool ok = (unsigned)(s.y[j] + oy) < (unsigned)g.hs && (unsigned)(s.x[j] + ox) < (unsigned)g.ws;
-            pa[j] = (ok ? A + (long long)(s.n[j] + d) * lda : zero) + col[j];
+            const bool in = (unsigned)(s.y[j] + oy) < (unsigned)g.hs && (unsigned)(s.x[j] + ox) < (unsigned)g.ws;
+            pa[j] = (in ? A + (long long)(s.n[j] + d) * lda : zero) + col[j];
+            real |= (in ? 1u : 0u) << j;
         }
     } else {
 #pragma unroll
@@ -233,8 +240,10 @@ __device__ __forceinline__ int rows_next_tap(const RowState<R>& s, unsigned& rem
                 off = s.off[j];
             }
             pa[j] = (off >= 0 ? A + off : zero) + col[j];
+            real |= (off >= 0 ? 1u : 0u) << j;
         }
     }
+    if (ok) *ok = real;
     return tap;
 }
 
@@ -448,6 +457,47 @@ __device__ __forceinline__ void rows_f16s_epilogue(const RowsOut& o, const RowTi
         if (lane == 0 && cmax > *reinterpret_cast<volatile float*>(o.amax_c))      // thousands of waves, ONE address: only a wave that raises it
             atomicMax(reinterpret_cast<unsigned*>(o.amax_c), __float_as_uint(cmax));
     }
+}
+
+// ---- the plain output epilogue (exact-fp32 and bf16x6 kernels) ------------------------------------------------------------
+// BM_ x 128 tile of waves holding 64 x 64 results as 2 x 2 blocks; a lane holds column (lane & 31), rows (r & 3) + 8 (r >> 2) +
+// 4 (lane >> 5) of a block.  One-dword stores of alpha * acc + bias (+ C); rect != 0 (per-tap rectangles): the tile's row -> its
+// output pixel, and the taps meet in atomics.  Of RowsOut it reads C, bias, N, ldc, accumulate, rect, tn, hd, wd and alpha.
+template <int BM_>
+__device__ __forceinline__ void rows_plain_epilogue(const RowsOut& o, const RowTile& t, const f32x16& c00, const f32x16& c01,
+                                                    const f32x16& c10, const f32x16& c11) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int row0 = t.tm * BM_ + (wave >> 1) * 64 + 4 * (lane >> 5), col0 = o.tn * BN + (wave & 1) * 64 + (lane & 31);
+    const int pMe = t.rows, pN = o.N, p_ldc = o.ldc, p_accumulate = o.accumulate, p_rect = o.rect;
+    const int r_y0 = t.y0, r_x0 = t.x0, r_h = t.h, r_w = t.w, g_hd = o.hd, g_wd = o.wd;
+    const float p_alpha = o.alpha;
+    float* __restrict__ C = o.C;
+    const float* __restrict__ p_bias = o.bias;
+    auto emit = [&](const f32x16& acc, int ti, int tj) {
+        const int col = col0 + 32 * tj;
+        if (col >= pN) return;
+        const float bv = p_bias ? p_bias[col] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = row0 + 32 * ti + (r & 3) + 8 * (r >> 2);
+            if (row >= pMe) continue;
+            if (p_rect) {
+                // unsigned divisions (nothing here is negative): the signed ones shared their magic numbers and signs with
+                // the divisions of rows_init(), five scalars that then stayed live across the main loop and spilled SGPRs
+                const unsigned hw = r_h * r_w;
+                const int n = (unsigned)row / hw, rem = row - n * hw;
+                const int yy = (unsigned)rem / (unsigned)r_w;
+                const long long orow = ((long long)n * g_hd + r_y0 + yy) * g_wd + r_x0 + (rem - yy * r_w);
+                atomicAdd(C + orow * p_ldc + col, p_alpha * acc[r]);
+            } else {
+                float* dst = C + (long long)row * p_ldc + col;
+                float v = p_alpha * acc[r] + bv;
+                if (p_accumulate) v += *dst;
+                *dst = v;
+            }
+        }
+    };
+    emit(c00, 0, 0); emit(c01, 0, 1); emit(c10, 1, 0); emit(c11, 1, 1);
 }
 
 }  // namespace

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Bitwise A/B of two builds of the library over the NT kernels' tile walk, row state and epilogue (csrc/gemm_rows_walk.h).
 
-For each case of a fixed list the call runs on seeded inputs through ops.gemm (f16x3 and f16) or the bf16-storage NT entry
-point and a SHA-256 of the bytes of C (and of amax_c where requested) is printed.  Two kinds of case are not bitwise
+For each case of a fixed list the call runs on seeded inputs through ops.gemm (f32, bf16x6, f16x3 and f16; the first two skip
+what only the split-fp16 kernels build: column statistics, the fused epilogue, region mode, pre-split operands) or the
+bf16-storage NT entry point and a SHA-256 of the bytes of C (and of amax_c where requested) is printed.  Two kinds of case are not bitwise
 reproducible from run to run -- per-tap rectangles (rect = 1: float atomics into C) and column statistics fed by more than
 one row tile (f64 atomics across workgroups) -- and are compared against float64 instead (the elementwise 5e-5 of
 tests/test_gpu_ops.py for C, 1e-6 relative for the statistics).
 
 Usage: rows_walk_ab.py                     one run of the library GLF_LIB_PATH (or the tree's) selects
-       rows_walk_ab.py LIB_A LIB_B         two fresh child processes one after the other, then the comparison"""
+       rows_walk_ab.py LIB_A LIB_B         two fresh child processes one after the other, then the comparison
+GLF_AB_PRECISIONS=f32,bf16x6 restricts the list to those precisions (default: all five)."""
 import hashlib
 import os
 import subprocess
@@ -68,32 +70,71 @@ def child():
         torch.cuda.synchronize()
         if rect == 1:
             ref = gathered_ref(A, B, src_index(gather, geo), mask)
-            out(name, prec, f"f64 ok {int(close(c, ref, 5e-5 if prec == 'f16x3' else 2e-2))}")
+            out(name, prec, f"f64 ok {int(close(c, ref, 2e-2 if prec == 'f16' else 5e-5))}")
         else:
             out(name, prec, f"sha C {sha(c)}")
 
-    for prec in ("f16x3", "f16"):
+    def nn(name, prec, conv, K, N, mask, rect=0, bias=False):
+        """C = sum_t A[src_t] @ B_t, B [taps][K][N]: the exact kernel's BMODE = 1, whatever the precision; conv None = plain"""
+        geo = geo_of(2, conv) if conv else None
+        M, rows_a, taps = (geo[0] * geo[3] * geo[4], geo[0] * geo[1] * geo[2], 9) if conv else (129, 129, 1)
+        A, B = rnd(rows_a, K, seed=31), rnd(taps, K, N, seed=32) / 3
+        bi = rnd(N, seed=33) if bias else None
+        c = torch.zeros(M, N, device=dev)
+        ops.gemm("nn", A.to(dev), B.to(dev), c, M=M, N=N, K=K, lda=K, ldb=N, ldc=N, bias=bi.to(dev) if bias else None, taps=taps, mask=mask,
+                 tap_stride_b=K * N, gather=2 if conv else 0, geo=geo, rect=rect)
+        torch.cuda.synchronize()
+        if rect == 1:
+            out(name, prec, f"f64 ok {int(close(c, gathered_ref(A, B.transpose(1, 2), src_index(2, geo), mask), 5e-5))}")
+        else:
+            out(name, prec, f"sha C {sha(c)}")
+
+    wanted = [p for p in os.environ.get("GLF_AB_PRECISIONS", "f32,bf16x6,f16x3,f16,bf16").split(",") if p]
+    for prec in [p for p in ("f32", "bf16x6", "f16x3", "f16") if p in wanted]:
         ops.set_precision(prec)
+        split16 = prec in ("f16x3", "f16")
         for K, tile in ((32, 128), (288, 256)):
             for N in (132, 70):
                 plain(f"plain_m{tile + 1}_n{N}_k{K}_bias", prec, tile + 1, N, K, bias=True)
                 plain(f"plain_m{tile + 1}_n{N}_k{K}_accumulate", prec, tile + 1, N, K, accumulate=True)
             plain(f"grouped_m{4 * tile + 1}_n900_k{K}", prec, 4 * tile + 1, 900, K)
-            plain(f"colstats_m{2 * tile + 3}_k{K}", prec, 2 * tile + 3, 132, K, bias=True, colstats=True, bitwise=False)
-            plain(f"colstats_m{tile - 5}_k{K}_one_tile", prec, tile - 5, 132, K, bias=True, colstats=True)
-            plain(f"epi_m{tile + 1}_n132_k{K}", prec, tile + 1, 132, K, epi=True)
+            if split16:
+                plain(f"colstats_m{2 * tile + 3}_k{K}", prec, 2 * tile + 3, 132, K, bias=True, colstats=True, bitwise=False)
+                plain(f"colstats_m{tile - 5}_k{K}_one_tile", prec, tile - 5, 132, K, bias=True, colstats=True)
+                plain(f"epi_m{tile + 1}_n132_k{K}", prec, tile + 1, 132, K, epi=True)
         for K in (32, 64):
             for g in (1, 2):
                 gathered(f"census_g{g}_k{K}", prec, g, (1, 28, 28, 3, 1, 12, 12), K, 72, NO_CENTRE)
-                gathered(f"region_g{g}_k{K}_accumulate", prec, g, (1, 28, 28, 3, 1, 12, 12), K, 72, REGION_MASK[g], rect=2, accumulate=True)
+                if split16:
+                    gathered(f"region_g{g}_k{K}_accumulate", prec, g, (1, 28, 28, 3, 1, 12, 12), K, 72, REGION_MASK[g], rect=2, accumulate=True)
                 gathered(f"rect1_g{g}_k{K}", prec, g, (1, 28, 28, 3, 1, 24, 24), K, 72, NO_CENTRE, rect=1)
             gathered(f"dgrad_s2_k{K}", prec, 2, (1, 55, 55, 3, 2, 1, 1), K, 72, NO_CENTRE)
+        if not split16:
+            # what the split-fp16 precisions never reach: a K tail (every precision's fallback to the exact kernel), three images
+            # of a non-square map, and the NN form of the exact kernel
+            plain("plain_m129_n70_k33_bias", prec, 129, 70, 33, bias=True)
+            for g in (1, 2):
+                gathered(f"census_3img_g{g}_k32", prec, g, (3, 28, 20, 3, 1, 12, 12), 32, 72, 0x1FF)
+                gathered(f"rect1_3img_g{g}_k32", prec, g, (3, 28, 20, 3, 1, 12, 12), 32, 72, 0x1FF, rect=1)
+            gathered("dgrad_s2_2img_k33", prec, 2, (2, 23, 23, 3, 2, 1, 1), 33, 72, 0x1FF)
+            nn("nn_plain_k33_bias", prec, None, 33, 70, 1, bias=True)
+            nn("nn_census_3img_k32", prec, (3, 28, 20, 3, 1, 12, 12), 32, 72, 0x1FF)
+            nn("nn_dgrad_s2_k32", prec, (1, 55, 55, 3, 2, 1, 1), 32, 72, NO_CENTRE)
+            nn("nn_rect1_3img_k32", prec, (3, 28, 20, 3, 1, 12, 12), 32, 72, 0x1FF, rect=1)
         # the model's own shapes (f16s4_probe.py): plain projections with pre-split weights, activations pre-split or not
         g = torch.Generator(device=dev).manual_seed(0)
         drnd = lambda *s: torch.rand(*s, device=dev, generator=g) * 2 - 1
         for M, N, K in [(193600, 256, 64), (193600, 64, 256), (193600, 64, 64), (50176, 512, 128), (50176, 128, 512), (50176, 1024, 256),
                         (50176, 256, 1024), (50176, 2048, 512), (50176, 512, 2048), (50176, 256, 1280), (50176, 256, 2048), (150528, 3072, 2048)]:
+            if not split16 and M * N * K > 1 << 36:
+                continue                                   # the largest one takes the exact kernel 20 s
             A, B, c = drnd(M, K), drnd(N, K), torch.empty(M, N, device=dev)
+            if not split16:
+                ops.gemm("nt", A, B, c, M=M, N=N, K=K, lda=K, ldb=K, ldc=N)
+                torch.cuda.synchronize()
+                out(f"model_nt_{M}_{N}_{K}", prec, f"sha C {sha(c)}")
+                del A, B, c
+                continue
             ama, amb = ops.amax_of(A), ops.amax_of(B)
             Ap, Bp = ops.packed_of(A, ama), ops.packed_of(B, amb)
             for pa in (False, True):
@@ -109,6 +150,8 @@ def child():
             torch.cuda.synchronize()
             out(f"model_conv3x3_{nimg * hh * hh}_{cout}_{cin}", prec, f"sha y {sha(y)} dx {sha(x.grad)}")
             del x, w, y
+    if "bf16" not in wanted:
+        return
     ops.set_precision("bf16")
     BF = torch.bfloat16
 

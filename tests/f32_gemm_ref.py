@@ -496,6 +496,7 @@ SPLIT16 = ("f16x3", "f16")
 NO_CENTRE = 0x1EF                      # 3x3 with a hole: 8 taps x K = 32 = 256 -> the 4-wave kernel
 _D12, _D24 = (1, 28, 28, 3, 1, 12, 12), (1, 28, 28, 3, 1, 24, 24)
 _S1, _S2 = (2, 13, 17, 3, 1, 1, 1), (1, 55, 55, 3, 2, 1, 1)
+_D12_3, _S2_2 = (3, 28, 20, 3, 1, 12, 12), (2, 23, 23, 3, 2, 1, 1)
 
 NT_CASES = {
     # geometry, under every precision: K = 32 -> bf16x6 8-wave / split-fp16 4-wave, K = 288 -> 8-wave; f32 -> the exact rows kernel
@@ -536,6 +537,15 @@ NT_CASES = {
     "g2_d12_rect2_acc": rows_case(gather=2, conv=_D12, N=70, K=64, rect=2, accumulate=True, precs=SPLIT16),
     "g1_d24_rect2": rows_case(gather=1, conv=_D24, N=72, K=32, rect=2, precs=SPLIT16),
     "g2_d24_rect2": rows_case(gather=2, conv=_D24, N=72, K=32, rect=2, bias=True, alpha=0.5, precs=SPLIT16),
+    # three images of a non-square map: a thread's rows (32 or 64 apart) wrap several lines of a rectangle and cross images.
+    # rect 1: the corner taps have 16 x 8 rectangles = 384 rows (three full 128-row tiles; one full and one ragged 256-row tile),
+    # the centre tap 1 680 rows (ragged in both tile heights); rect 0: the census runs on tiles that straddle two images
+    "g1_3img_d12_rect1": rows_case(gather=1, conv=_D12_3, N=72, K=32, rect=1),
+    "g2_3img_d12_rect1": rows_case(gather=2, conv=_D12_3, N=72, K=32, rect=1),
+    "g1_3img_d12_rect0": rows_case(gather=1, conv=_D12_3, N=72, K=32, tap_mask=NO_CENTRE),
+    "g2_3img_d12_rect0": rows_case(gather=2, conv=_D12_3, N=72, K=32),
+    # the dgrad of a strided conv over two images (the one gather without the fast form), 1 058 rows: a ragged last tile in both heights
+    "g2_s2_2img_23to12": rows_case(gather=2, conv=_S2_2, N=72, K=32),
 }
 # the split-fp16 kernels with pre-split operands: plain and gather x (a, b, both) x 4-wave and 8-wave
 for _k, _w in ((32, "4w"), (288, "8w")):
@@ -559,6 +569,7 @@ NN_CASES = {
     "nn_plain": rows_case(129, 70, 33, mode="nn", precs=_NNP),
     "nn_g2_s1": rows_case(mode="nn", gather=2, conv=_S1, N=72, K=32, bias=True, precs=_NNP),
     "nn_g2_d24_rect1": rows_case(mode="nn", gather=2, conv=_D24, N=72, K=32, rect=1, precs=_NNP),
+    "nn_g2_3img_d12_rect1": rows_case(mode="nn", gather=2, conv=_D12_3, N=72, K=32, rect=1, precs=_NNP),
     "nn_b3_alpha_bias_acc": rows_case(127, 132, 52, mode="nn", batch=3, alpha=0.5, bias=True, accumulate=True, precs=_NNP),
 }
 _W5 = (2, 16, 12, 3, 1, 5, 5)
